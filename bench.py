@@ -2,9 +2,17 @@
 """Headline benchmark: SVI steps/s of the `bean run` hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--config metric|tiling|survival] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
 
 One "step" is one full SVI step (draw, ELBO, gradient, ClippedAdam; ``bean/model/run.py:376-377``) over
 a synthetic screen that is already resident in HBM.
+
+A plain run times only the leg ``value`` reports: it sets up, runs W untimed and K timed steps and
+prints the JSON line.  ``--full`` adds everything else described below: the other leg, the ``roofline``
+and ``sustained`` objects, the CPU baseline and, for ``--config metric`` at N = 1, ``other_configs``.
+``--dump-outputs DIR`` writes what the timed leg hands its caller after its last step (see
+``dump_outputs``) as ``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared output
+for output.
 
 ``--gpus N`` with N > 1 works with or without a launcher: under ``torch.distributed.run`` (RANK /
 WORLD_SIZE in the environment) this process is one rank; started bare, it starts the N ranks itself as
@@ -16,7 +24,7 @@ before anything touches the GPU, and passes rank 0's JSON line and the exit code
   tiling    tiling sorting MultiMixtureNormal, 50k guides / ~193k edited alleles x 5 reps     [configs[2]]
   survival  survival MixtureNormal, 100k guides x 6 timepoints x 3 replicates                 [configs[4]]
 
-Every run times TWO legs in the same process group (``--no-strong`` skips the second):
+A ``--full`` run times TWO legs in the same process group (``--no-strong`` skips the second):
   weak    every rank holds its own screen of the configured size; steps of one such screen summed over
           ranks.  This is ``value`` (``--scaling weak``, the default) and the ``weak`` object.
   strong  ONE screen - 500k-guide variant sorting (BASELINE configs[3]) for ``metric``, the 50k-guide
@@ -27,8 +35,9 @@ Every run times TWO legs in the same process group (``--no-strong`` skips the se
           parameter across shards (only the loss window is all-reduced, every 100 steps, the reference's
           reporting cadence, ``run.py:378``); tiling and survival exchange inside every step
           (``HipSVI.run_exchanged``: per-edit gradients / Dirichlet normalisers over RCCL).
-The driver's N = 1, 2, 4, 8 series therefore carries both curves; the north star's ">= 6x 1 -> 8" is
-``strong.value`` at N = 8 over ``strong.value`` at N = 1.
+A ``--full`` N = 1, 2, 4, 8 series therefore carries both curves; the north star's ">= 6x 1 -> 8" is
+``strong.value`` at N = 8 over ``strong.value`` at N = 1.  A plain run with ``--scaling strong`` times
+the strong leg alone.
 
 Rank 0 prints ONE JSON line; DESIGN.md section 4 defines the ``roofline`` and ``cpu_baseline`` objects.
 """
@@ -596,6 +605,34 @@ class Leg:
         self.eng.close()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240501
+
+
+def dump_outputs(leg, out_dir, rank, world):
+    """``--dump-outputs DIR``: what the timed leg hands its caller after its last step - the parameter store
+    (constrained values in screen order, as ``HipSVI.constrained`` gives them to ``run_inference``) and the
+    loss of every step the engine ran - as ``DIR/[rank<r>_]<name>.npy`` in float32 / float64.  If the arrays
+    together exceed 64 MB, each one is cut to a fixed, seeded sample of its flat elements (same seed, same
+    indices in every run), sized so that the files stay within the budget."""
+    import numpy as np
+
+    arrays = {f"param_{k}": v.detach().cpu().numpy() for k, v in leg.eng.constrained().items()}
+    arrays["loss"] = np.asarray(leg.eng.losses(), dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)  # (room for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in sorted(arrays.items()):
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def dry_rehearsal(args, rank, world):
     """BEAN_BENCH_REHEARSAL=dry (CPU containers, tests): the ranks rendezvous over gloo and rank 0
     prints the JSON line with null measurements - checks the launch path, measures nothing."""
@@ -605,13 +642,15 @@ def dry_rehearsal(args, rank, world):
         dist.init_process_group("gloo")
         dist.barrier()
     if rank == 0:
-        print(json.dumps({"metric": METRICS[args.config], "value": None, "unit": "steps/s", "n_gpus": world,
-                          "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True,
-                          "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-                          "rehearsal": "dry: no GPU touched, nothing measured",
-                          "config": {"workload": None, "config": args.config},
-                          "strong": {"guides": args.strong_guides or STRONG_GUIDES[args.config], "value": None,
-                                     "ms_per_step": None}}), flush=True)
+        out = {"metric": METRICS[args.config], "value": None, "unit": "steps/s", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True,
+               "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+               "rehearsal": "dry: no GPU touched, nothing measured",
+               "config": {"workload": None, "config": args.config}}
+        if args.scaling == "strong" or (args.full and not args.no_strong):
+            out["strong"] = {"guides": args.strong_guides or STRONG_GUIDES[args.config], "value": None,
+                             "ms_per_step": None}
+        print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
@@ -630,15 +669,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", choices=("metric", "tiling", "survival"), default="metric")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
-                    help="which leg `value` reports; the other one is still run (see --no-strong)")
+                    help="which leg `value` reports; with --full the other one is run too (see --no-strong)")
     ap.add_argument("--guides", type=int, default=0, help="guides per GPU of the weak leg")
     ap.add_argument("--strong-guides", type=int, default=0, help="guides of the one screen of the strong leg")
-    ap.add_argument("--no-strong", action="store_true", help="skip the strong leg (weak `value` only)")
+    ap.add_argument("--no-strong", action="store_true", help="--full: skip the strong leg (weak `value` only)")
     ap.add_argument("--graph-chunk", type=int, default=64)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="N = 1, --config metric: skip the tiling and survival legs (`other_configs`)")
     ap.add_argument("--scale-by-acc", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the other leg, roofline, sustained fit, CPU baseline and other configurations; a plain "
+                         "run times only the leg `value` reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed leg computed (parameters after its last step, losses) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -674,27 +718,37 @@ def main():
     total = args.warmup + args.steps
     weak_guides = args.guides or DEFAULT_GUIDES[args.config]
     strong_guides = args.strong_guides or STRONG_GUIDES[args.config]
-    want_strong = not args.no_strong or args.scaling == "strong"
+    report_strong = args.scaling == "strong"
+    # a plain run times the one leg `value` reports; the other leg and everything else is --full's
+    want_weak = args.full or not report_strong
+    want_strong = report_strong or (args.full and not args.no_strong)
     # at one rank the strong leg of tiling / survival IS the weak leg (same screen, nothing to cut)
     same_leg = world == 1 and strong_guides == weak_guides and not args.scale_by_acc
 
-    weak_closed = False
-    weak = Leg(args, args.config, False, weak_guides, rank, world, dev, total)
-    dt_weak = weak.timed(args.steps, args.warmup)
-    losses = weak.eng.losses()
-    std_size = weak_guides == DEFAULT_GUIDES[args.config] and not args.scale_by_acc
-    roof = roofline_object(args.config, weak, weak_guides, std_size) if rank == 0 else None
-    sustained = weak.sustained() if (rank == 0 and world == 1) else None
-    if rank != 0:
-        weak.kernel_profile()  # (every rank runs the same launches: the legs stay in step)
-    strong_obj = None
+    weak = sleg = roof = sustained = strong_obj = None
+    losses = []
+    if want_weak or (want_strong and same_leg):
+        weak = Leg(args, args.config, False, weak_guides, rank, world, dev, total)
+        dt_weak = weak.timed(args.steps, args.warmup)
+        losses = weak.eng.losses()
+        if args.dump_outputs and (not report_strong or same_leg):
+            dump_outputs(weak, args.dump_outputs, rank, world)
+        if args.full:
+            std_size = weak_guides == DEFAULT_GUIDES[args.config] and not args.scale_by_acc
+            roof = roofline_object(args.config, weak, weak_guides, std_size) if rank == 0 else None
+            sustained = weak.sustained() if (rank == 0 and world == 1) else None
+            if rank != 0:
+                weak.kernel_profile()  # (every rank runs the same launches: the legs stay in step)
     if want_strong:
         if same_leg:
             sleg, dt_strong = weak, dt_weak
         else:
-            weak.close()
+            if weak is not None:
+                weak.close()
             sleg = Leg(args, args.config, True, strong_guides, rank, world, dev, total)
             dt_strong = sleg.timed(args.steps, args.warmup)
+            if args.dump_outputs and report_strong:
+                dump_outputs(sleg, args.dump_outputs, rank, world)
         strong_obj = {
             "guides": strong_guides,
             "guides_this_rank": int(sleg.data.n_guides),
@@ -705,11 +759,13 @@ def main():
             "exchange": sleg.exchange,
             "final_loss": sleg.eng.losses()[-1] if rank == 0 else None,
         }
+        if weak is None:
+            losses = sleg.eng.losses()
         if sleg is not weak:
             sleg.close()
+    head = sleg if report_strong else weak
 
     if rank == 0:
-        report_strong = args.scaling == "strong"
         value = strong_obj["value"] if report_strong else world * args.steps / dt_weak
         ms = strong_obj["ms_per_step"] if report_strong else dt_weak / args.steps * 1e3
         metric = METRICS[args.config]
@@ -734,8 +790,8 @@ def main():
                 "config": args.config,
                 "guides": strong_guides if report_strong else weak_guides,
                 "guides_this_rank": strong_obj["guides_this_rank"] if report_strong else int(weak.data.n_guides),
-                "n_reps": int(weak.data.n_reps),
-                "n_condits": int(weak.data.n_condits),
+                "n_reps": int(head.data.n_reps),
+                "n_condits": int(head.data.n_condits),
                 "parallelism": (f"one screen guide-sharded x{world}" if report_strong
                                 else f"one screen per GPU x{world}")
                                + f", loss all-reduce every {LOSS_SYNC_EVERY} steps",
@@ -744,8 +800,9 @@ def main():
                                  else "steps of one screen, summed over ranks"),
                 "final_loss": losses[-1] if losses else None,
             },
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         if sustained is not None:
             out["sustained"] = sustained
         if strong_obj is not None:
@@ -753,14 +810,13 @@ def main():
         if not report_strong:
             out["weak"] = {"guides_per_gpu": weak_guides, "value": world * args.steps / dt_weak,
                            "ms_per_step": dt_weak / args.steps * 1e3}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(weak.family, weak.shard_cpu, weak.loss_fn, weak.loss_kw, weak.init_fn)
             out["config"]["gpu_over_cpu"] = (world * args.steps / dt_weak) / out["cpu_baseline"]["value"]
-        if world == 1 and args.config == "metric" and not args.no_other_configs and not args.scale_by_acc:
+        if (args.full and world == 1 and args.config == "metric" and not args.no_other_configs
+                and not args.scale_by_acc):
             # BASELINE configs[2] and configs[4] on the same line, same --steps / --warmup
-            if not (want_strong and not same_leg):
-                weak.close()
-                weak_closed = True
+            weak.close()
             out["other_configs"] = {c: other_config(args, c, rank, dev) for c in ("tiling", "survival")}
             out["other_configs"]["tiling_acc"] = other_config(args, "tiling", rank, dev, acc=True)
             out["other_configs"]["readme_shape"] = readme_shape(args, dev)
@@ -768,8 +824,8 @@ def main():
             # number the reference does publish is on another shape and is compared there
             out["vs_baseline_readme_shape"] = out["other_configs"]["readme_shape"]["vs_baseline"]
         print(json.dumps(out), flush=True)
-    if not (want_strong and not same_leg) and not weak_closed:
-        weak.close()
+    if weak is not None:
+        weak.close()  # (closing twice is a no-op)
     if world > 1:
         dist.destroy_process_group()
 

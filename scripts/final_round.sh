@@ -28,9 +28,11 @@ else
   for cs in tiling/1 tiling/8 survival/1 survival/8; do
     XCHG_CASES=$cs step 200 python scripts/time_exchange.py >> gpurun_out/exchange.log 2>&1
   done
-  step 400 python bench.py > gpurun_out/bench_metric.json 2> gpurun_out/bench_metric.err
-  step 300 python bench.py --config tiling --steps 500 --warmup 50 > gpurun_out/bench_tiling.json 2> gpurun_out/bench_tiling.err
-  step 300 python bench.py --config survival --steps 1000 --warmup 50 > gpurun_out/bench_survival.json 2> gpurun_out/bench_survival.err
-  step 300 python bench.py --steps 20 --warmup 5 > gpurun_out/bench_short.json 2> gpurun_out/bench_short.err
-  tail -c 700 gpurun_out/bench_metric.json; echo; tail -c 300 gpurun_out/bench_short.json
+  # the full bench lines (other leg, roofline, sustained fit, CPU baseline, other configurations) into $BENCH_OUT
+  BENCH_OUT=${BENCH_OUT:-bench_out}; mkdir -p "$BENCH_OUT"
+  step 400 python bench.py --full > "$BENCH_OUT/bench_metric.json" 2> "$BENCH_OUT/bench_metric.err"
+  step 300 python bench.py --full --config tiling --steps 500 --warmup 50 > "$BENCH_OUT/bench_tiling.json" 2> "$BENCH_OUT/bench_tiling.err"
+  step 300 python bench.py --full --config survival --steps 1000 --warmup 50 > "$BENCH_OUT/bench_survival.json" 2> "$BENCH_OUT/bench_survival.err"
+  step 300 python bench.py --full --steps 20 --warmup 5 > "$BENCH_OUT/bench_short.json" 2> "$BENCH_OUT/bench_short.err"
+  tail -c 700 "$BENCH_OUT/bench_metric.json"; echo; tail -c 300 "$BENCH_OUT/bench_short.json"
 fi

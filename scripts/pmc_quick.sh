@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --steps 10 --warmup 2 --graph-chunk 0 --no-cpu-baseline > $OUT/bench.json 2> $OUT/err.log
+rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --full --steps 10 --warmup 2 --graph-chunk 0 --no-cpu-baseline > $OUT/bench.json 2> $OUT/err.log
 python3 - <<PY
 import csv,glob,collections
 agg=collections.defaultdict(list); dur=collections.defaultdict(list)

@@ -3,7 +3,7 @@
 TAG=${1:-dev}
 REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-B="python3 $REPO/bench.py --config tiling --steps 12 --warmup 3 --graph-chunk 0 --no-cpu-baseline --no-strong --no-other-configs"
+B="python3 $REPO/bench.py --full --config tiling --steps 12 --warmup 3 --graph-chunk 0 --no-cpu-baseline --no-strong --no-other-configs"
 i=0
 for set in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM" \
            "SQ_IFETCH SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA SQ_INSTS_VALU SQ_BUSY_CYCLES"; do

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_mix_$CONFIG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $REPO/bench.py --config $CONFIG --no-cpu-baseline --steps 20 --warmup 4 --graph-chunk 0"
+B="python3 $REPO/bench.py --full --config $CONFIG --no-cpu-baseline --steps 20 --warmup 4 --graph-chunk 0"
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT --kernel-trace --output-format csv -d $OUT/a -- $B > $OUT/a.json 2> $OUT/a.err
 rocprofv3 --pmc SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_INSTS_SMEM --kernel-trace --output-format csv -d $OUT/b -- $B > $OUT/b.json 2> $OUT/b.err
 cd $REPO && python3 - "$OUT" <<'PY'

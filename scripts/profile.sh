@@ -13,7 +13,7 @@ OUT=$REPO/gpurun_out/prof_$TAG$SUF
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 BASE=${CONFIG%_acc}; ACC=""; [ "$BASE" != "$CONFIG" ] && ACC="--scale-by-acc"
-B="python3 $REPO/bench.py --config $BASE $ACC --no-cpu-baseline --no-strong --no-other-configs"
+B="python3 $REPO/bench.py --full --config $BASE $ACC --no-cpu-baseline --no-strong --no-other-configs"
 # pass 1: per-kernel time (graph replay, as the bench runs it)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- $B --steps 400 --warmup 50 > $OUT/bench_kt.json 2> $OUT/kt.err
 # pass 2..4: PMC counters, eager launches

@@ -4,7 +4,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/trace_short
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -- python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-strong --no-other-configs > $OUT/bench.json 2> $OUT/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -- python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-strong --no-other-configs > $OUT/bench.json 2> $OUT/err.txt
 cd $REPO && python3 - <<'PY'
 import csv, glob
 f = glob.glob("gpurun_out/trace_short/kt/**/*kernel_trace.csv", recursive=True)[0]
