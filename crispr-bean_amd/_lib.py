@@ -84,6 +84,10 @@ BUF = {
     "X0_IN": 104, "EPS_U_IN": 105, "X0_OUT": 106, "EPS_U_OUT": 107, "PRIOR_IA": 108, "XCHG_COV": 109, "GUIDE_IDS": 110,
     "LOSS_HIST": 112,
 }
+MAX_MEMBERS = 64  # BEAN_HIP_MAX_MEMBERS
+# the seed-ensemble entry points: a library named by BEAN_HIP_LIB may be an older build without them (timing a parent
+# build beside this one, scripts/time_ensemble.py); such a library serves single fits only
+ENSEMBLE_SYMBOLS = ("bean_hip_ensemble_supported", "bean_hip_set_members", "bean_hip_svi_run_ensemble")
 PARAM_ORDER = ("mu_loc", "mu_scale", "sd_loc", "sd_scale", "alpha_pi", "noise_loc", "noise_scale", "q0")
 
 # every symbol include/bean_hip.h declares: (name, restype, argtypes)
@@ -98,6 +102,9 @@ SYMBOLS = [
     ("bean_hip_adam", c_int32, [c_void_p, c_uint64, c_void_p]),
     ("bean_hip_svi_run", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_int32, c_void_p]),
     ("bean_hip_svi_resume", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_int32, c_void_p]),
+    ("bean_hip_ensemble_supported", c_int32, [c_void_p]),
+    ("bean_hip_set_members", c_int32, [c_void_p, c_int32]),
+    ("bean_hip_svi_run_ensemble", c_int32, [c_void_p, POINTER(c_uint64), c_int32, c_uint64, c_uint64, c_int32, c_void_p]),
     ("bean_hip_sharded_begin", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
     ("bean_hip_sharded_sums", c_int32, [c_void_p, c_void_p]),
     ("bean_hip_sharded_guide", c_int32, [c_void_p, c_void_p]),
@@ -241,6 +248,8 @@ def load(amax=8):
         )
     lib = ctypes.CDLL(LIB_PATH)
     for name, res, args in SYMBOLS:
+        if name in ENSEMBLE_SYMBOLS and os.environ.get("BEAN_HIP_LIB") and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -8,11 +8,23 @@ import sys
 from ..model.parser import parse_args as attach_run_args
 
 
+def _positive_int(text: str) -> int:
+    value = int(text)
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {value}")
+    return value
+
+
 def get_parser():
     parser = argparse.ArgumentParser(prog="bean")
     sub = parser.add_subparsers(dest="subcommand", help="bean subcommands")
     run = sub.add_parser("run", help="Quantify variant effect sizes from screen data (MI355X)")
     attach_run_args(run)
+    # this project's own switches (the reference's flag table, model/parser.py, stays the reference's)
+    own = run.add_argument_group("crispr-bean_amd")
+    own.add_argument("--n-seeds", dest="n_seeds", type=_positive_int, default=1,
+                     help="Fit this many seeds (101, 102, ...) of the main model at once and report their moment-matched "
+                          "average, with the between-seed spread of mu in the columns mu_seed_sd / n_seeds (default 1: one fit).")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))

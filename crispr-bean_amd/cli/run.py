@@ -131,6 +131,8 @@ def main(args, return_data=False):
         model = partial(model, prior_params=_check_prior_params(args.prior_params, ndata))
 
     info(f"Running inference for {model_label}...")
+    n_seeds = int(getattr(args, "n_seeds", 1) or 1)
+    seed_sd = None
     save_dict = dict()
     param_history_dict_negctrl = None
     if args.load_existing:
@@ -157,8 +159,20 @@ def main(args, return_data=False):
                                                param_history_dict_negctrl["mu_scale"].detach().mean()))
     if not args.load_existing:
         save_dict["data"] = ndata
-        param_history_dict, save_dict_model = deepcopy(run_inference(model, guide, ndata, num_steps=args.n_iter))
-        save_dict.update(save_dict_model)
+        if n_seeds > 1:
+            # a seed ensemble: member 0 is the fit a run without --n-seeds does; the tables come from the combination
+            from ..model.ensemble import combine_ensemble
+            from ..model.run import SEED, run_inference_ensemble
+
+            members = run_inference_ensemble(model, guide, ndata, [SEED + k for k in range(n_seeds)], num_steps=args.n_iter)
+            param_history_dict, spread = combine_ensemble(members)
+            seed_sd = spread["mu_seed_sd"]
+            save_dict["params"] = {k: v.detach().cpu() for k, v in param_history_dict.items()}
+            save_dict["loss"] = members[0][1]["loss"]
+            save_dict["ensemble"] = [{"params": out["params"], "loss": out["loss"]} for _, out in members]
+        else:
+            param_history_dict, save_dict_model = deepcopy(run_inference(model, guide, ndata, num_steps=args.n_iter))
+            save_dict.update(save_dict_model)
     if rank != 0:
         return prefix
     outfile = f"{prefix}/bean_element[sgRNA]_result.{model_label}{args.result_suffix}.csv"
@@ -180,6 +194,7 @@ def main(args, return_data=False):
         sd_is_fitted=(args.selection == "sorting"),
         sample_covariates=getattr(ndata, "sample_covariates", None),
         is_survival_screen=(args.selection == "survival"),
+        **({"seed_sd": seed_sd, "n_seeds": n_seeds} if seed_sd is not None else {}),
     )
     info("Done!")
     return prefix

@@ -95,6 +95,19 @@ struct bean_hip_ctx {
     size_t async_ws_ints;
     unsigned long long* async_stamps;  // diagnostic builds (-DBEAN_ASYNC_STAMP): the last call's item timeline
     size_t async_stamp_words;
+    // seed ensemble (bean_ensemble.hpp): K members stepped by the same launches.  Member 0 is `d` itself; member k >= 1
+    // has the k-th private copy of the workspace (member_ws), of tsum_buf and of loss_acc, and the k-th part of the
+    // member-major parameter / gradient / moment / loss_hist buffers
+    int n_members;
+    bool bound_any;            // a buffer has been bound: bean_hip_set_members comes too late
+    char* member_ws;           // (K - 1) copies of the workspace, member_ws_stride bytes apart
+    size_t member_ws_stride;
+    size_t tsum_stride;        // doubles of tsum per member
+    DevArgs* members_dev;      // device: DevArgs of the K members
+    std::vector<DevArgs> members_host;
+    std::vector<uint64_t> member_seeds;
+    bool members_dirty;        // members_dev is older than the bound buffers / the seeds
+    std::vector<hipGraphExec_t> graphs_ens;  // [k]: 2^k {k_param_ens, k_guide_wave2_ens} pairs
 };
 
 extern "C" const char* bean_hip_version(void) {
@@ -260,6 +273,10 @@ static void drop_graph(bean_hip_ctx* c) {
     for (hipGraphExec_t g : c->graphs_resume)
         if (g) (void)hipGraphExecDestroy(g);
     c->graphs_resume.clear();
+    for (hipGraphExec_t g : c->graphs_ens)
+        if (g) (void)hipGraphExecDestroy(g);
+    c->graphs_ens.clear();
+    c->members_dirty = true;
     c->resume_ok = false;  // (called whenever a buffer, the shape-dependent state or the seed changes)
 }
 
@@ -366,6 +383,13 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
     c->async_ws_ints = 0;
     c->async_stamps = nullptr;
     c->async_stamp_words = 0;
+    c->n_members = 1;
+    c->bound_any = false;
+    c->member_ws = nullptr;
+    c->member_ws_stride = 0;
+    c->tsum_stride = 0;
+    c->members_dev = nullptr;
+    c->members_dirty = true;
     c->loss_acc = nullptr;
     c->profile = false;
     c->profile_param = false;
@@ -659,6 +683,8 @@ extern "C" int bean_hip_destroy(bean_hip_ctx* c) {
     if (c->dargs_dev) (void)hipFree(c->dargs_dev);
     if (c->async_ws) (void)hipFree(c->async_ws);
     if (c->loss_acc) (void)hipFree(c->loss_acc);
+    if (c->member_ws) (void)hipFree(c->member_ws);
+    if (c->members_dev) (void)hipFree(c->members_dev);
     delete c;
     return 0;
 }
@@ -670,19 +696,26 @@ extern "C" int bean_hip_bind(bean_hip_ctx* c, int slot, void* ptr, uint64_t nbyt
         const uint64_t want = expected_bytes(c->shape, slot);
         if (want == 0)
             return fail("bean_hip_bind: slot " + std::to_string(slot) + " is not used by this shape");
+        const uint64_t K = (uint64_t)c->n_members;
         if (slot == BEAN_BUF_LOSS_HIST) {
             if (nbytes < 8 || nbytes % 8) return fail("bean_hip_bind: loss_hist must hold >= 1 double");
-            if (nbytes / 8 != c->loss_capacity || !c->loss_acc) {
+            if (nbytes % (8 * K)) return fail("bean_hip_bind: loss_hist of " + std::to_string(K) + " members is (members, capacity) doubles");
+            // (the accumulators of all members in one allocation, member-major like loss_hist itself)
+            if (nbytes / 8 / K != c->loss_capacity || !c->loss_acc) {
                 if (c->loss_acc) (void)hipFree(c->loss_acc);
                 c->loss_acc = nullptr;
                 HIP_OK(hipMalloc((void**)&c->loss_acc, (nbytes / 8) * kLossSub * kLossWords * sizeof(long long)));
                 HIP_OK(hipMemset(c->loss_acc, 0, (nbytes / 8) * kLossSub * kLossWords * sizeof(long long)));
             }
-            c->loss_capacity = nbytes / 8;
-        } else if (nbytes != want) {
+            c->loss_capacity = nbytes / 8 / K;
+        } else if (slot >= BEAN_BUF_P_MU_LOC && slot < BEAN_BUF_V_MU_LOC + 16 && nbytes != want * K) {
+            return fail("bean_hip_bind: slot " + std::to_string(slot) + " expects " + std::to_string(want * K) +
+                        " bytes (" + std::to_string(K) + " member(s)), got " + std::to_string(nbytes));
+        } else if (!(slot >= BEAN_BUF_P_MU_LOC && slot < BEAN_BUF_V_MU_LOC + 16) && nbytes != want) {
             return fail("bean_hip_bind: slot " + std::to_string(slot) + " expects " + std::to_string(want) +
                         " bytes, got " + std::to_string(nbytes));
         }
+        c->bound_any = true;
     }
     c->slot_ptr[slot] = ptr;
     c->slot_bytes[slot] = ptr ? nbytes : 0;
@@ -773,7 +806,9 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
             // per-target-part sums of d/dmu_t, d/dy_t (k_guide_wave2 -> k_param) and where each target's lie
             // no target longer than a tile (thin mode): two fixed slots per target, no descriptor to read
             c->d.tsum_direct = (!c->d.wide_targets && c->shape.max_target_len >= 1 && c->shape.max_target_len <= 64) ? 1 : 0;
-            const size_t n_sum = c->d.tsum_direct ? (size_t)2 * c->d.R * 2 * c->d.T : (size_t)2 * c->d.R * c->d.n_tiles * nt;
+            const size_t n_sum1 = c->d.tsum_direct ? (size_t)2 * c->d.R * 2 * c->d.T : (size_t)2 * c->d.R * c->d.n_tiles * nt;
+            c->tsum_stride = n_sum1;
+            const size_t n_sum = n_sum1 * (size_t)c->n_members;  // (an ensemble: one part per member)
             if (c->tsum_buf) (void)hipFree(c->tsum_buf);
             c->tsum_buf = nullptr;
             HIP_OK(hipMalloc((void**)&c->tsum_buf, n_sum * sizeof(double)));
@@ -897,6 +932,20 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         }
     }
 #endif
+    if (c->n_members > 1) {
+        // every member's private workspace starts as a copy of the one just prepared: the data-only parts (the
+        // constant, the bin edges, the accessibility factors, the kPNrg row) are then there for all of them
+        for (int k = 1; k < c->n_members; ++k)
+            HIP_OK(hipMemcpyAsync(c->member_ws + (size_t)(k - 1) * c->member_ws_stride, c->workspace, c->workspace_bytes,
+                                  hipMemcpyDeviceToDevice, stream));
+        const bool acc = (c->d.flags & kAcc) != 0;
+        const size_t lds = guide_wave2_lds(c->d.B, c->d.tile_targets);
+        const void* fn = c->d.family == kMixture ? (acc ? (const void*)k_guide_wave2_ens<kMixture, true> : (const void*)k_guide_wave2_ens<kMixture, false>)
+                                                 : (const void*)k_guide_wave2_ens<kNormal, false>;
+        if (lds > 65536) HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIP_OK(hipStreamSynchronize(stream));
+        drop_graph(c);
+    }
     c->prepared = true;
     return 0;
 }
@@ -1454,11 +1503,14 @@ static void enqueue_fused(bean_hip_ctx* c, hipStream_t stream, uint64_t n, int f
 #endif
 }
 
-static int capture_pairs(bean_hip_ctx* c, hipStream_t stream, uint64_t n, hipGraphExec_t* out, bool fused = false) {
+static void enqueue_pairs_ens(bean_hip_ctx* c, hipStream_t stream, uint64_t n);
+static int capture_pairs(bean_hip_ctx* c, hipStream_t stream, uint64_t n, hipGraphExec_t* out, bool fused = false,
+                         bool ens = false) {
     hipGraph_t graph = nullptr;
     HIP_OK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
     const bool fresh_was = c->alleles_fresh;  // (a capture runs nothing; these graphs begin with a PREP launch)
-    if (fused) enqueue_fused(c, stream, n);
+    if (ens) enqueue_pairs_ens(c, stream, n);
+    else if (fused) enqueue_fused(c, stream, n);
     else enqueue_pairs(c, stream, n);
     c->alleles_fresh = fresh_was;
     hipError_t e = hipStreamEndCapture(stream, &graph);
@@ -1829,6 +1881,201 @@ extern "C" int bean_hip_svi_run(bean_hip_ctx* c, uint64_t seed, uint64_t first_s
         launch_param<true, true, false>(c, stream);
     }
     launch_finalize(c, stream, first_step, n_steps, false);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- seed ensembles (bean_ensemble.hpp): the pair path with a member axis, gridDim.y = K
+static bool ensemble_shape_ok(const bean_hip_ctx* c) {
+    const bean_hip_shape& s = c->shape;
+    return c->wave_guide && c->wave2 && !is_survival(s) && s.n_sample_covariates == 0 &&
+           (s.family == BEAN_FAMILY_NORMAL || s.family == BEAN_FAMILY_MIXTURE_NORMAL) && !c->async_step && !c->fused_step &&
+           !c->tile_svi && s.guide_offset == 0 && s.target_offset == 0 &&
+           (s.n_guides_total == 0 || s.n_guides_total == s.n_guides) &&
+           !(s.flags & (BEAN_FLAG_NOT_LOSS_OWNER | BEAN_FLAG_DUMP_PI));
+}
+
+extern "C" int bean_hip_ensemble_supported(const bean_hip_ctx* c) {
+    if (!c) return fail("bean_hip_ensemble_supported: null handle");
+    return ensemble_shape_ok(c) ? 1 : 0;
+}
+
+extern "C" int bean_hip_set_members(bean_hip_ctx* c, int32_t n_members) {
+    if (!c) return fail("bean_hip_set_members: null handle");
+    if (n_members < 1 || n_members > BEAN_HIP_MAX_MEMBERS)
+        return fail("bean_hip_set_members: n_members must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) + "]");
+    if (!ensemble_shape_ok(c))
+        return fail("bean_hip_set_members: the batched kernels do not take this shape (bean_hip_ensemble_supported): "
+                    "fit its seeds one after the other");
+    if (c->bound_any) return fail("bean_hip_set_members: call it after bean_hip_create and before any bean_hip_bind");
+    static_assert(BEAN_HIP_MAX_MEMBERS == kEnsembleMaxMembers, "the header's cap is the kernels'");
+    if (c->member_ws) (void)hipFree(c->member_ws);
+    c->member_ws = nullptr;
+    if (c->members_dev) (void)hipFree(c->members_dev);
+    c->members_dev = nullptr;
+    c->n_members = 1;
+    c->member_ws_stride = (size_t)((c->workspace_bytes + 255) / 256 * 256);
+    if (n_members > 1) HIP_OK(hipMalloc((void**)&c->member_ws, (size_t)(n_members - 1) * c->member_ws_stride));
+    HIP_OK(hipMalloc((void**)&c->members_dev, (size_t)n_members * sizeof(DevArgs)));
+    c->n_members = n_members;
+    c->member_seeds.clear();
+    c->prepared = false;
+    drop_graph(c);
+    return 0;
+}
+
+// DevArgs of member k: c->d with everything a step writes moved to the member's own part
+static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
+    DevArgs m = c->d;
+    m.seed = seed;
+    m.tgrad = nullptr;
+    if (k == 0) return m;
+    const char* w0 = (const char*)c->workspace;
+    const char* w1 = w0 + c->workspace_bytes;
+    const ptrdiff_t off = (c->member_ws + (size_t)(k - 1) * c->member_ws_stride) - (char*)c->workspace;
+#define BEAN_WS(f)                                                                  \
+    do {                                                                            \
+        const char* q_ = (const char*)m.f;                                          \
+        if (q_ && q_ >= w0 && q_ < w1) m.f = (decltype(m.f))(const_cast<char*>(q_) + off); \
+    } while (0)
+    BEAN_WS(tabP); BEAN_WS(tabPmu); BEAN_WS(tabPy); BEAN_WS(P0); BEAN_WS(mu_t); BEAN_WS(y_t); BEAN_WS(eps_mu); BEAN_WS(eps_sd);
+    BEAN_WS(part); BEAN_WS(mu_a); BEAN_WS(sig_a); BEAN_WS(lpn); BEAN_WS(eps_noise); BEAN_WS(kacc); BEAN_WS(loss_const);
+    BEAN_WS(const_acc); BEAN_WS(tile_ctr); BEAN_WS(bnd_ctr); BEAN_WS(ue_z); BEAN_WS(ue_idx); BEAN_WS(dbg); BEAN_WS(wrow);
+    BEAN_WS(nobs); BEAN_WS(rrow); BEAN_WS(pi_ws); BEAN_WS(gpi_ws); BEAN_WS(trow); BEAN_WS(dgq); BEAN_WS(dgq_t); BEAN_WS(lpart);
+    BEAN_WS(q0_ctr); BEAN_WS(ctrA); BEAN_WS(ctrB);
+#undef BEAN_WS
+    for (int i = 0; i < 8; ++i) {
+        const size_t n = (size_t)(expected_bytes(c->shape, BEAN_BUF_P_MU_LOC + i) / 4) * (size_t)k;
+        if (m.p[i]) m.p[i] += n;
+        if (m.g[i]) m.g[i] += n;
+        if (m.m[i]) m.m[i] += n;
+        if (m.v[i]) m.v[i] += n;
+    }
+    m.loss_hist += (size_t)k * c->loss_capacity;
+    m.loss_acc += (size_t)k * c->loss_capacity * kLossSub * kLossWords;
+    if (m.tsum) m.tsum += (size_t)k * c->tsum_stride;
+    return m;
+}
+
+static int ens_kind(const bean_hip_ctx* c) {
+    const DevArgs& d = c->d;
+    const bool kind1 = !d.survival && d.family != kMultiMixture && !d.wide_targets && !d.n_cov && d.wrow && d.rows_v2 &&
+                       !d.rrow && !d.surv_q0lik && !d.not_loss_owner && d.lpart && (d.dgq || d.family != kMixture) && d.tsum;
+    return (kind1 && !param_generic_only()) ? 1 : 0;
+}
+
+template <bool FINISH, bool ADAM, bool PREP>
+static void launch_param_ens(bean_hip_ctx* c, hipStream_t stream) {
+    int ntb, nb;
+    grid_param(c, ntb, nb);
+    const dim3 grid((unsigned)nb, (unsigned)c->n_members), block(kParamBlock);
+    const DevArgs* mem = c->members_dev;
+    if (ens_kind(c) == 1) hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 1>), grid, block, 0, stream, mem, ntb);
+    else hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 0>), grid, block, 0, stream, mem, ntb);
+}
+
+static void launch_guide_ens(bean_hip_ctx* c, hipStream_t stream) {
+    const DevArgs& d = c->d;
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)c->n_members), block(64);
+    const size_t lds = guide_wave2_lds(d.B, d.tile_targets);
+    const DevArgs* mem = c->members_dev;
+    if (d.family == kMixture) {
+        if (d.flags & kAcc) hipLaunchKernelGGL((k_guide_wave2_ens<kMixture, true>), grid, block, lds, stream, mem);
+        else hipLaunchKernelGGL((k_guide_wave2_ens<kMixture, false>), grid, block, lds, stream, mem);
+    } else {
+        hipLaunchKernelGGL((k_guide_wave2_ens<kNormal, false>), grid, block, lds, stream, mem);
+    }
+}
+
+static void enqueue_pairs_ens(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
+    for (uint64_t i = 0; i < n; ++i) {
+        launch_param_ens<true, true, true>(c, stream);
+        launch_guide_ens(c, stream);
+    }
+}
+
+extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
+                                         uint64_t n_steps, int32_t graph_chunk, void* stream_) {
+    if (!c) return fail("bean_hip_svi_run_ensemble: null handle");
+    if (!seeds) return fail("bean_hip_svi_run_ensemble: null seeds");
+    if (n_seeds != c->n_members)
+        return fail("bean_hip_svi_run_ensemble: " + std::to_string(n_seeds) + " seeds for " + std::to_string(c->n_members) +
+                    " member(s) (bean_hip_set_members)");
+    if (!ensemble_shape_ok(c))
+        return fail("bean_hip_svi_run_ensemble: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
+    // (a handle that never heard of members is an ensemble of one)
+    if (!c->members_dev) HIP_OK(hipMalloc((void**)&c->members_dev, (size_t)c->n_members * sizeof(DevArgs)));
+    if (!c->prepared) return fail("bean_hip_svi_run_ensemble: call bean_hip_prepare first");
+    if (check_bound(c, false, true)) return -1;
+    const DevArgs& dd = c->d;
+    if (dd.eps_mu_in || dd.eps_sd_in || dd.pi_in || dd.eps_noise_in || dd.eps_mu_out || dd.eps_sd_out || dd.pi_out ||
+        dd.eps_noise_out)
+        return fail("bean_hip_svi_run_ensemble: injected or dumped noise belongs to single fits");
+    if (n_steps == 0) return 0;
+    if (first_step + n_steps > c->loss_capacity)
+        return fail("bean_hip_svi_run_ensemble: loss_hist too small for first_step + n_steps");
+    hipStream_t stream = (hipStream_t)stream_;
+    c->resume_ok = false;
+    const int K = c->n_members;
+    bool same = !c->members_dirty && (int)c->member_seeds.size() == K;
+    for (int k = 0; same && k < K; ++k) same = c->member_seeds[(size_t)k] == seeds[k];
+    if (!same) {
+        // (the launches - captured ones too - hold the ADDRESS of this array: new seeds need no new graphs)
+        HIP_OK(hipStreamSynchronize(stream));  // no launch in flight reads the array while it changes
+        c->members_host.resize((size_t)K);
+        c->member_seeds.assign(seeds, seeds + K);
+        for (int k = 0; k < K; ++k) c->members_host[(size_t)k] = member_args(c, k, seeds[k]);
+        HIP_OK(hipMemcpyAsync(c->members_dev, c->members_host.data(), (size_t)K * sizeof(DevArgs), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        c->members_dirty = false;
+    }
+    const bool use_graph = graph_chunk > 0 && stream != nullptr;
+    if (use_graph) {
+        int kmax = 0;
+        while ((2ull << kmax) <= (uint64_t)graph_chunk && kmax < 10) ++kmax;
+        if ((int)c->graphs_ens.size() != kmax + 1) {
+            for (hipGraphExec_t g : c->graphs_ens)
+                if (g) (void)hipGraphExecDestroy(g);
+            c->graphs_ens.clear();
+            for (int k = 0; k <= kmax; ++k) {
+                hipGraphExec_t ge = nullptr;
+                if (capture_pairs(c, stream, 1ull << k, &ge, false, true)) {
+                    for (hipGraphExec_t g : c->graphs_ens)
+                        if (g) (void)hipGraphExecDestroy(g);
+                    c->graphs_ens.clear();
+                    return -1;
+                }
+                c->graphs_ens.push_back(ge);
+            }
+        }
+    }
+    {
+        const uint64_t words = n_steps * kLossSub * kLossWords;
+        unsigned blocks = (unsigned)((words + 255) / 256);
+        if (blocks < 1) blocks = 1;
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(k_set_step_ens, dim3(blocks, (unsigned)K), dim3(256), 0, stream, (const DevArgs*)c->members_dev,
+                           (unsigned long long)first_step, (unsigned long long)first_step, (unsigned long long)n_steps);
+    }
+    launch_param_ens<false, false, true>(c, stream);
+    launch_guide_ens(c, stream);
+    uint64_t pairs = n_steps - 1;
+    if (use_graph) {  // (the decomposition of bean_hip_svi_run: smallest graphs first, one or two pairs launched directly)
+        const int kmax = (int)c->graphs_ens.size() - 1;
+        const uint64_t big = pairs >> kmax;
+        const uint64_t rest = pairs - (big << kmax);
+        for (int k = 0; k < kmax; ++k)
+            if (rest & (1ull << k)) {
+                if (k < 2) enqueue_pairs_ens(c, stream, 1ull << k);
+                else HIP_OK(hipGraphLaunch(c->graphs_ens[k], stream));
+            }
+        for (uint64_t i = 0; i < big; ++i) HIP_OK(hipGraphLaunch(c->graphs_ens[kmax], stream));
+        pairs = 0;
+    }
+    enqueue_pairs_ens(c, stream, pairs);
+    launch_param_ens<true, true, false>(c, stream);
+    hipLaunchKernelGGL(k_loss_finalize_ens, dim3((unsigned)((n_steps + 3) / 4), (unsigned)K), dim3(n_steps == 1 ? 64 : 256), 0,
+                       stream, (const DevArgs*)c->members_dev, (unsigned long long)first_step, (unsigned long long)n_steps, 0);
     HIP_OK(hipGetLastError());
     return 0;
 }

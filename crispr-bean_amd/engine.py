@@ -36,6 +36,10 @@ def _quantile_edges(upper: torch.Tensor, lower: torch.Tensor):
     return z_hi, z_lo
 
 
+class EnsembleUnsupported(ValueError):
+    """``HipSVI(..., n_members=K)`` on a shape the batched kernels do not take (``bean_hip_ensemble_supported``)."""
+
+
 class HipSVI:
     """One model family bound to one screen on one GPU."""
 
@@ -65,6 +69,7 @@ class HipSVI:
         alpha_prior: float = 1.0,
         lib_variant: Optional[str] = None,
         guide_ids: Optional[torch.Tensor] = None,
+        n_members: int = 1,
     ):
         if family not in _lib.FAMILY:
             raise ValueError(f"unknown model family {family!r}")
@@ -201,6 +206,21 @@ class HipSVI:
         with torch.cuda.device(dev):
             self._check(self.lib.bean_hip_create(ctypes.byref(shape), ctypes.byref(handle)), "create")
         self._h = handle
+        # seed ensemble: K fits of this screen stepped by the same launches (bean_hip_svi_run_ensemble); parameters,
+        # moments, gradients and the loss history get a leading member axis.  1: the single-fit engine.
+        self.n_members = int(n_members)
+        if self.n_members != 1:
+            if not 1 <= self.n_members <= _lib.MAX_MEMBERS:
+                self.lib.bean_hip_destroy(self._h)
+                self._h = None
+                raise ValueError(f"n_members must be in [1, {_lib.MAX_MEMBERS}]")
+            if not self.ensemble_supported:
+                self.lib.bean_hip_destroy(self._h)
+                self._h = None
+                raise EnsembleUnsupported(f"the batched kernels do not take this shape ({family}): fit its seeds one "
+                                          "after the other (run_inference_ensemble does)")
+            with torch.cuda.device(dev):
+                self._check(self.lib.bean_hip_set_members(self._h, self.n_members), "set_members")
         self._keep: Dict[str, torch.Tensor] = {}
         self.stream = torch.cuda.Stream(device=dev)
 
@@ -340,6 +360,8 @@ class HipSVI:
             if name not in init:
                 continue
             p = init[name].to(dev, torch.float32).contiguous()
+            if self.n_members != 1:  # member-major: every member starts from the single fit's initial values
+                p = p.unsqueeze(0).repeat(self.n_members, *([1] * p.dim())).contiguous()
             self.unconstrained[name] = p
             self.grads[name] = torch.zeros_like(p)
             self._m[name] = torch.zeros_like(p)
@@ -349,7 +371,8 @@ class HipSVI:
             self._bind_slot(_lib.BUF["M"] + i, self._m[name], f"M.{name}")
             self._bind_slot(_lib.BUF["V"] + i, self._v[name], f"V.{name}")
         cap = int(loss_capacity) if loss_capacity is not None else self.num_steps + 8
-        self.loss_hist = torch.zeros(max(cap, 1), dtype=torch.float64, device=dev)
+        self.loss_hist = torch.zeros(max(cap, 1) if self.n_members == 1 else (self.n_members, max(cap, 1)),
+                                     dtype=torch.float64, device=dev)
         self._bind("LOSS_HIST", self.loss_hist)
         self._noise_out: Dict[str, torch.Tensor] = {}
         if dump_noise:
@@ -686,6 +709,26 @@ class HipSVI:
         self._resume_versions = versions
         self.steps_done = first + n_steps
 
+    @property
+    def ensemble_supported(self) -> bool:
+        """Whether the batched kernels take this engine's shape (``bean_hip_ensemble_supported``)."""
+        return self.lib.bean_hip_ensemble_supported(self._h) == 1
+
+    def run_ensemble(self, n_steps: int, seeds, graph_chunk: int = 50, first_step: Optional[int] = None):
+        """Enqueue ``n_steps`` SVI steps of all ``n_members`` fits, member k with ``seeds[k]`` (no host
+        synchronisation).  Member k is, bit for bit, a single engine's ``run(n_steps, seed=seeds[k])``;
+        stepping in windows gives the bits of one call."""
+        seeds = [int(s) for s in seeds]
+        first = self.steps_done if first_step is None else int(first_step)
+        if first + n_steps > self.loss_hist.shape[-1]:
+            raise ValueError("loss history too small: raise num_steps / loss_capacity")
+        arr = (ctypes.c_uint64 * max(len(seeds), 1))(*seeds)
+        with self._on_stream():
+            self._check(self.lib.bean_hip_svi_run_ensemble(self._h, arr, len(seeds), first, int(n_steps), int(graph_chunk),
+                                                           self._sptr()), "svi_run_ensemble")
+        self._resume_broken = True  # (a following run(resume=True) does not continue this call)
+        self.steps_done = first + n_steps
+
     def _tensor_versions(self):
         return tuple(t._version for d in (self.unconstrained, self._m, self._v) for t in d.values())
 
@@ -695,7 +738,10 @@ class HipSVI:
         self._resume_broken = True
 
     def losses(self):
+        """The loss history: a list of ``steps_done`` floats; of an ensemble a ``(n_members, steps_done)`` array."""
         torch.cuda.synchronize(self.device)
+        if self.n_members != 1:
+            return self.loss_hist[:, : self.steps_done].cpu().numpy()
         return self.loss_hist[: self.steps_done].cpu().tolist()
 
     def set_profile(self, enable):
@@ -732,10 +778,18 @@ class HipSVI:
         with self._on_stream():
             return {k: v.clone() for k, v in self.unconstrained.items()}
 
-    def constrained(self, snapshot: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-        """Constrained parameter values, as ``pyro.get_param_store()[name]`` (of ``snapshot`` if given)."""
+    def constrained(self, snapshot: Optional[Dict[str, torch.Tensor]] = None,
+                    member: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Constrained parameter values, as ``pyro.get_param_store()[name]`` (of ``snapshot`` if given); of an
+        ensemble, those of ``member``."""
         torch.cuda.synchronize(self.device)
         src = self.unconstrained if snapshot is None else snapshot
+        if self.n_members != 1:
+            if member is None or not 0 <= int(member) < self.n_members:
+                raise ValueError(f"an ensemble of {self.n_members}: constrained(member=k), 0 <= k < {self.n_members}")
+            src = {k: v[int(member)] for k, v in src.items()}
+        elif member not in (None, 0):
+            raise ValueError("a single fit has member 0 only")
         out = {k: (v.exp() if k in POSITIVE else v.clone()) for k, v in src.items()}
         if self.survival and self.family == "MultiMixtureNormal":
             # the reference's tiling survival guide registers this parameter and never uses it

@@ -165,14 +165,28 @@ def write_result_table(
     sample_covariates: Optional[List[str]] = None,
     return_result: bool = False,
     is_survival_screen: bool = False,
+    seed_sd=None,
+    n_seeds: Optional[int] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
-    and files; the steps are the helpers above)."""
+    and files; the steps are the helpers above).
+
+    ``seed_sd`` / ``n_seeds`` (a seed ensemble, ``model/ensemble.py``): the element table gets the columns
+    ``mu_seed_sd`` - the between-seed standard deviation of every target's ``mu`` - and ``n_seeds``.  Left at ``None``
+    the tables are exactly those of a single fit."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
     element = pd.concat([target_info_df.reset_index(), fitted.reset_index(drop=True)], axis=1)
+    if seed_sd is not None or n_seeds is not None:
+        if seed_sd is None or n_seeds is None:
+            raise ValueError("seed_sd and n_seeds go together")
+        spread = np.asarray(seed_sd.detach().cpu() if hasattr(seed_sd, "detach") else seed_sd, dtype=np.float64).reshape(-1)
+        if len(spread) != len(element):
+            raise ValueError(f"seed_sd has {len(spread)} entries for {len(element)} targets")
+        element["mu_seed_sd"] = spread
+        element["n_seeds"] = int(n_seeds)
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

@@ -191,6 +191,80 @@ def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000
     return store, out
 
 
+def run_inference_ensemble(model, guide, data, seeds, initial_lr=0.01, gamma=0.1, num_steps=2000,
+                           report_every: int = 100, verbose: bool = True):
+    """``len(seeds)`` independent SVI fits of one screen, member k with the random streams of ``seeds[k]``.
+
+    Returns a list of ``(param_store, {"loss", "params"})`` pairs, each exactly what
+    ``run_inference(..., seed=seeds[k])`` returns - bit for bit.  Where the batched kernels take the shape (the
+    sorting variant families: ``bean_hip_ensemble_supported``) all members are stepped by the same launches; every
+    other family (tiling, survival, ControlNormal, sample covariates, screens large enough to fill the GPU with one
+    fit) is fitted seed after seed through ``run_inference``.  A non-finite loss of ANY member halts the fit at the
+    end of its report window with the ``ValueError`` of ``run_inference``; message and dump file
+    (``tmp_result.member<k>.pkl``) name the member.  Not combined with guide sharding over several ranks."""
+    import torch.distributed as dist
+
+    from .. import parallel
+    from .._lib import MAX_MEMBERS
+    from ..engine import EnsembleUnsupported
+
+    seeds = [int(s) for s in seeds]
+    if not seeds:
+        raise ValueError("run_inference_ensemble needs at least one seed")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError("run_inference_ensemble does not combine with guide sharding over several ranks")
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+
+    def one_after_the_other():
+        return [run_inference(model, guide, data, seed=s, report_every=report_every, verbose=verbose, **common)
+                for s in seeds]
+
+    spec = _resolve(model)
+    if (spec.family in ("MultiMixtureNormal", "ControlNormal") or spec.selection == "survival"
+            or len(seeds) > MAX_MEMBERS):
+        return one_after_the_other()
+    device = torch.device("cuda", torch.cuda.current_device())
+    try:
+        eng = build_engine(model, guide, data.to(device), device=device, n_guides_total=data.n_guides,
+                           n_members=len(seeds), **common)
+    except EnsembleUnsupported:
+        return one_after_the_other()
+    try:
+        done = 0
+        while done < num_steps:
+            k = min(report_every, num_steps - done)
+            window_start = eng.snapshot()  # what a halt inside this window dumps
+            eng.run_ensemble(k, seeds)
+            windows = eng.loss_hist[:, done:done + k]
+            for member in range(len(seeds)):
+                try:
+                    parallel.check_window_finite(windows[member], done)
+                except FloatingPointError as exc:
+                    name = f"tmp_result.member{member}.pkl"
+                    error(f"Error occurred during fitting (member {member}, seed {seeds[member]}). "
+                          f"Saving temporary output at {name}.")
+                    with open(name, "wb") as handle:
+                        dump = {n: v.cpu() for n, v in eng.constrained(window_start, member=member).items()}
+                        pkl.dump({"param": dump, "member": member, "seed": seeds[member]}, handle)
+                    raise ValueError(
+                        f"Fitting halted for command: {' '.join(sys.argv)} with following error: \n "
+                        f"member {member} (seed {seeds[member]}): {exc}"
+                    )
+            if verbose:
+                print(f"loss {' '.join(str(float(v)) for v in windows[:, 0])} @ iter {done}")
+            done += k
+        losses = eng.losses()
+        results = []
+        for member in range(len(seeds)):
+            constrained = eng.constrained(member=member)
+            constrained = {n: v.clone() for n, v in constrained.items()}
+            results.append((ParamStore(constrained),
+                            {"loss": losses[member].tolist(), "params": {n: v.detach().cpu() for n, v in constrained.items()}}))
+    finally:
+        eng.close()
+    return results
+
+
 def identify_model_guide(args):
     """Model label and (model, guide) descriptors for the parsed ``bean run``
     arguments (``bean/model/run.py:399-457``), including the reference's

@@ -251,6 +251,36 @@ int bean_hip_adam(bean_hip_ctx* ctx, uint64_t t, void* stream);
 int bean_hip_svi_run(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_step,
                      uint64_t n_steps, int32_t graph_chunk, void* stream);
 
+/* Seed ensembles: K independent fits of the SAME screen, stepped by the same launches (the grids get a member
+ * axis; the data is bound once and read by all members).  Member k is, bit for bit, the fit that
+ * bean_hip_svi_run(seed = seeds[k]) produces on a handle of its own.
+ *
+ *   bean_hip_ensemble_supported   1 if the batched kernels take this handle's shape, 0 if not: the sorting variant
+ *                                 families on the two-launches-per-step path (Normal without sample covariates,
+ *                                 MixtureNormal with or without accessibility scaling / fit_noise / X_bcmatch /
+ *                                 --prior-params), unsharded.  Not: tiling, survival, ControlNormal, sample
+ *                                 covariates, screens large enough for the one-launch stepper, BEAN_FLAG_DUMP_PI.
+ *                                 Callers fit the seeds of such a shape one after the other.
+ *   bean_hip_set_members          after bean_hip_create, before ANY bean_hip_bind; 1 <= n_members <=
+ *                                 BEAN_HIP_MAX_MEMBERS.  From then on the slots BEAN_BUF_P_*, G_*, M_*, V_* expect
+ *                                 n_members times their single-fit size, member-major ((K, T), (K, G, A), ...), and
+ *                                 BEAN_BUF_LOSS_HIST holds (K, capacity) doubles; bean_hip_bind checks these sizes.
+ *                                 The handle allocates a private workspace per member.  The single-fit entry points
+ *                                 (bean_hip_elbo_grad, bean_hip_svi_run, ...) keep working and address member 0.
+ *   bean_hip_svi_run_ensemble     the loop of bean_hip_svi_run for all members: `seeds` is a HOST array of n_seeds ==
+ *                                 n_members values; loss of member k, step s in loss_hist[k * capacity + s].  A call
+ *                                 with first_step = the previous call's first_step + n_steps continues the fits
+ *                                 (windows give the bits of one call).  Injected / dumped noise is refused.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched): a null handle; set_members on a shape that
+ * is not supported, after a bind, with n_members outside [1, BEAN_HIP_MAX_MEMBERS]; run_ensemble with n_seeds !=
+ * n_members or null seeds. */
+#define BEAN_HIP_MAX_MEMBERS 64
+int bean_hip_ensemble_supported(const bean_hip_ctx* ctx);
+int bean_hip_set_members(bean_hip_ctx* ctx, int32_t n_members);
+int bean_hip_svi_run_ensemble(bean_hip_ctx* ctx, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
+                              uint64_t n_steps, int32_t graph_chunk, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
