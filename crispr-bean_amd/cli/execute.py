@@ -25,6 +25,12 @@ def get_parser():
     own.add_argument("--n-seeds", dest="n_seeds", type=_positive_int, default=1,
                      help="Fit this many seeds (101, 102, ...) of the main model at once and report their moment-matched "
                           "average, with the between-seed spread of mu in the columns mu_seed_sd / n_seeds (default 1: one fit).")
+    own.add_argument("--jackknife-replicates", dest="jackknife_replicates", action="store_true",
+                     help="Next to the fit of the screen, fit it once per replicate with that replicate masked (same seed) "
+                          "and report, per target, the jackknife standard error of mu and the replicate whose removal "
+                          "moves it most: columns mu_jk_se / mu_jk_max_shift / mu_jk_max_shift_rep / n_jk.  The two numeric "
+                          "columns are on the scale of the column mu (the raw posterior mean), not of mu_scaled / mu_adj "
+                          "that --fit-negctrl adds.  Not combined with --n-seeds > 1 or --load-existing.")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))
@@ -32,6 +38,14 @@ def get_parser():
 
     attach_qc_args(sub.add_parser("qc", help="QC of the screen: mask low-quality samples and outlier guides"))
     return parser
+
+
+def check_run_switches(parser, args):
+    """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
+    if getattr(args, "jackknife_replicates", False) and int(getattr(args, "n_seeds", 1) or 1) > 1:
+        parser.error("--jackknife-replicates fits every member with the same seed and does not combine with --n-seeds > 1.")
+    if getattr(args, "jackknife_replicates", False) and getattr(args, "load_existing", False):
+        parser.error("--jackknife-replicates needs the leave-one-replicate-out fits and does not combine with --load-existing.")
 
 
 def main(argv=None):
@@ -50,6 +64,7 @@ def main(argv=None):
     if args.subcommand != "run":
         parser.print_help()
         return 2
+    check_run_switches(parser, args)
     from .run import main as run_main
 
     try:

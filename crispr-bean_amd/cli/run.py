@@ -49,6 +49,15 @@ def _init_distributed():
     return dist.get_rank(), dist.get_world_size()
 
 
+def _replicate_names(ndata):
+    """Names of the screen's replicates in the order of the tensors' replicate axis (the samples are sorted by
+    replicate, then condition)."""
+    samples = ndata.screen.samples
+    col = "_rc" if "_rc" in samples.columns else "replicate"
+    names = list(dict.fromkeys(samples[col].astype(str))) if col in samples.columns else []
+    return names if len(names) == int(ndata.n_reps) else [str(r) for r in range(int(ndata.n_reps))]
+
+
 def main(args, return_data=False):
     rank, world = (0, 1) if return_data else _init_distributed()
     if rank != 0:  # one banner / one log / one set of tables
@@ -132,7 +141,13 @@ def main(args, return_data=False):
 
     info(f"Running inference for {model_label}...")
     n_seeds = int(getattr(args, "n_seeds", 1) or 1)
+    jackknife = bool(getattr(args, "jackknife_replicates", False))
+    if jackknife and n_seeds > 1:
+        raise ValueError("--jackknife-replicates fits every member with the same seed and does not combine with --n-seeds > 1.")
+    if jackknife and args.load_existing:
+        raise ValueError("--jackknife-replicates needs the leave-one-replicate-out fits and does not combine with --load-existing.")
     seed_sd = None
+    jk = None
     save_dict = dict()
     param_history_dict_negctrl = None
     if args.load_existing:
@@ -170,6 +185,18 @@ def main(args, return_data=False):
             save_dict["params"] = {k: v.detach().cpu() for k, v in param_history_dict.items()}
             save_dict["loss"] = members[0][1]["loss"]
             save_dict["ensemble"] = [{"params": out["params"], "loss": out["loss"]} for _, out in members]
+        elif jackknife:
+            # a replicate jackknife: member 0 is the fit a run without the flag does, and the tables come from it
+            from ..model.jackknife import jackknife_summary
+            from ..model.run import run_inference_jackknife
+
+            full, loo, left_out = run_inference_jackknife(model, guide, ndata, num_steps=args.n_iter)
+            names = _replicate_names(ndata)
+            jk = jackknife_summary(full, loo, left_out, names)
+            param_history_dict, save_dict_model = deepcopy(full)
+            save_dict.update(save_dict_model)
+            save_dict["jackknife"] = [{"left_out": names[r], "params": out["params"], "loss": out["loss"]}
+                                      for r, (_, out) in zip(left_out, loo)]
         else:
             param_history_dict, save_dict_model = deepcopy(run_inference(model, guide, ndata, num_steps=args.n_iter))
             save_dict.update(save_dict_model)
@@ -195,6 +222,7 @@ def main(args, return_data=False):
         sample_covariates=getattr(ndata, "sample_covariates", None),
         is_survival_screen=(args.selection == "survival"),
         **({"seed_sd": seed_sd, "n_seeds": n_seeds} if seed_sd is not None else {}),
+        **({"jackknife": jk} if jk is not None else {}),
     )
     info("Done!")
     return prefix

@@ -8,7 +8,8 @@
 // The members' arguments are an array of K DevArgs in global memory (bean_hip_ctx::members_dev).  They differ in what a
 // step writes - parameters, gradients, moments, the workspace (each member has a whole private copy of it, taken behind
 // bean_hip_prepare, so the data-only rows in it are there for everybody), tsum, the loss accumulators, its row of
-// loss_hist - and in the seed; every data pointer, toff, g2t and tdesc are the same K times.  A block reads its member's
+// loss_hist - and in the seed; every data pointer, toff, g2t and tdesc are the same K times (with per-member masks bound,
+// bean_hip_bind_member_masks, `rg` and `smask` point at the member's slice: see k_prepare_ens).  A block reads its member's
 // copy through the scalar cache into SGPRs (dev_args_in_sgprs: nothing in a launch writes the array), which is where a
 // kernel argument lives, and runs the body the single-fit kernel runs.  The single-fit kernels themselves are the same
 // code objects as before (DESIGN.md lists their register figures side by side).
@@ -46,6 +47,17 @@ void k_guide_wave2_ens(const DevArgs* members) {
         wave_loss_out(c, ctr.slot, blockIdx.x, tot);
         if (blockIdx.x == 0) publish_ctr(c, ctr);  // (the member's own counters)
     }
+}
+
+// Per-member masks (bean_hip_bind_member_masks): members may also differ in `rg` and `smask`, the two mask arrays the
+// kernels above already read through the member's DevArgs.  Three data-only words that k_prepare leaves depend on `rg` -
+// the loss constant, the kPNrg row and nobs - so bean_hip_prepare runs k_prepare's body once per member, each on its own
+// masks and into its own workspace copy (whose const_acc the host has zeroed; P0 and the bin edges come out as before).
+__global__ __launch_bounds__(256) void k_prepare_ens(const DevArgs* members) {
+    const DevArgs c = dev_args_in_sgprs(members + blockIdx.y);
+#define BEAN_PREPARE_BODY_INCLUDED_BY_KERNEL
+#include "bean_prepare_body.hpp"
+#undef BEAN_PREPARE_BODY_INCLUDED_BY_KERNEL
 }
 
 __global__ __launch_bounds__(256) void k_loss_finalize_ens(const DevArgs* members, unsigned long long first,

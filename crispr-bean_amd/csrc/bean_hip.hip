@@ -108,6 +108,11 @@ struct bean_hip_ctx {
     std::vector<uint64_t> member_seeds;
     bool members_dirty;        // members_dev is older than the bound buffers / the seeds
     std::vector<hipGraphExec_t> graphs_ens;  // [k]: 2^k {k_param_ens, k_guide_wave2_ens} pairs
+    // per-member masks (bean_hip_bind_member_masks): (K, R, G) uint8 and (K, R, B) float64 of the caller, member-major;
+    // null: every member reads the shared BEAN_BUF_REPGUIDE / BEAN_BUF_SAMPLE_MASK
+    bool members_set;          // bean_hip_set_members has been called
+    const uint8_t* member_rg;
+    const double* member_smask;
 };
 
 extern "C" const char* bean_hip_version(void) {
@@ -390,6 +395,9 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
     c->tsum_stride = 0;
     c->members_dev = nullptr;
     c->members_dirty = true;
+    c->members_set = false;
+    c->member_rg = nullptr;
+    c->member_smask = nullptr;
     c->loss_acc = nullptr;
     c->profile = false;
     c->profile_param = false;
@@ -765,6 +773,8 @@ static int check_bound(bean_hip_ctx* c, bool need_grads, bool need_moments) {
     return 0;
 }
 
+static int upload_members(bean_hip_ctx* c, const uint64_t* seeds, hipStream_t stream);
+
 extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
     if (!c) return fail("bean_hip_prepare: null handle");
     if (check_bound(c, false, false)) return -1;
@@ -945,6 +955,22 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         if (lds > 65536) HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_OK(hipStreamSynchronize(stream));
         drop_graph(c);
+    }
+    if (c->member_rg) {
+        // per-member masks: the constant, the kPNrg row and nobs depend on `rg`, so k_prepare's body runs again, once
+        // per member, on the member's masks and into its own workspace copy (member 0's is the workspace itself)
+        // (the array is uploaded with the seeds known so far - zeros before the first run - and is then current: a
+        // bean_hip_svi_run_ensemble with those seeds does not upload it again)
+        const int K = c->n_members;
+        if ((int)c->member_seeds.size() != K) c->member_seeds.assign((size_t)K, 0);
+        if (upload_members(c, c->member_seeds.data(), stream)) return -1;
+        c->members_dirty = false;
+        for (int k = 0; k < K; ++k)
+            HIP_OK(hipMemsetAsync(c->members_host[(size_t)k].const_acc, 0, kLossWords * sizeof(long long), stream));
+        hipLaunchKernelGGL(k_prepare_ens, dim3((unsigned)((n + 255) / 256), (unsigned)K), dim3(256), 0, stream,
+                           (const DevArgs*)c->members_dev);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(stream));
     }
     c->prepared = true;
     return 0;
@@ -1918,17 +1944,25 @@ extern "C" int bean_hip_set_members(bean_hip_ctx* c, int32_t n_members) {
     if (n_members > 1) HIP_OK(hipMalloc((void**)&c->member_ws, (size_t)(n_members - 1) * c->member_ws_stride));
     HIP_OK(hipMalloc((void**)&c->members_dev, (size_t)n_members * sizeof(DevArgs)));
     c->n_members = n_members;
+    c->members_set = true;
+    c->member_rg = nullptr;  // (sized for another K)
+    c->member_smask = nullptr;
     c->member_seeds.clear();
     c->prepared = false;
     drop_graph(c);
     return 0;
 }
 
-// DevArgs of member k: c->d with everything a step writes moved to the member's own part
+// DevArgs of member k: c->d with everything a step writes moved to the member's own part, and the two masks at the
+// member's slice when per-member masks are bound
 static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
     DevArgs m = c->d;
     m.seed = seed;
     m.tgrad = nullptr;
+    if (c->member_rg) {  // per-member masks (bean_hip_bind_member_masks); member 0 reads its slice too
+        m.rg = c->member_rg + (size_t)k * (size_t)c->d.R * (size_t)c->d.G;
+        m.smask = c->member_smask + (size_t)k * (size_t)c->d.R * (size_t)c->d.B;
+    }
     if (k == 0) return m;
     const char* w0 = (const char*)c->workspace;
     const char* w1 = w0 + c->workspace_bytes;
@@ -1955,6 +1989,43 @@ static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
     m.loss_acc += (size_t)k * c->loss_capacity * kLossSub * kLossWords;
     if (m.tsum) m.tsum += (size_t)k * c->tsum_stride;
     return m;
+}
+
+// the members' arguments, as they are now, to the device array the `_ens` launches read
+static int upload_members(bean_hip_ctx* c, const uint64_t* seeds, hipStream_t stream) {
+    const int K = c->n_members;
+    HIP_OK(hipStreamSynchronize(stream));  // no launch in flight reads the array while it changes
+    c->members_host.resize((size_t)K);
+    for (int k = 0; k < K; ++k) c->members_host[(size_t)k] = member_args(c, k, seeds[k]);
+    HIP_OK(hipMemcpyAsync(c->members_dev, c->members_host.data(), (size_t)K * sizeof(DevArgs), hipMemcpyHostToDevice, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+extern "C" int bean_hip_bind_member_masks(bean_hip_ctx* c, const void* repguide, uint64_t repguide_bytes,
+                                          const void* sample_mask, uint64_t sample_mask_bytes) {
+    if (!c) return fail("bean_hip_bind_member_masks: null handle");
+    if (!ensemble_shape_ok(c))
+        return fail("bean_hip_bind_member_masks: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
+    if (!c->members_set) return fail("bean_hip_bind_member_masks: call bean_hip_set_members first");
+    if ((repguide == nullptr) != (sample_mask == nullptr))
+        return fail("bean_hip_bind_member_masks: the two masks go together (both, or null for both)");
+    if (repguide) {
+        const uint64_t K = (uint64_t)c->n_members;
+        const uint64_t want_rg = K * (uint64_t)c->d.R * (uint64_t)c->d.G;
+        const uint64_t want_sm = K * (uint64_t)c->d.R * (uint64_t)c->d.B * sizeof(double);
+        if (repguide_bytes != want_rg)
+            return fail("bean_hip_bind_member_masks: repguide expects " + std::to_string(want_rg) + " bytes (" +
+                        std::to_string(K) + " member(s)), got " + std::to_string(repguide_bytes));
+        if (sample_mask_bytes != want_sm)
+            return fail("bean_hip_bind_member_masks: sample_mask expects " + std::to_string(want_sm) + " bytes (" +
+                        std::to_string(K) + " member(s)), got " + std::to_string(sample_mask_bytes));
+    }
+    c->member_rg = (const uint8_t*)repguide;
+    c->member_smask = (const double*)sample_mask;
+    drop_graph(c);        // (members_dev is older than the masks now)
+    c->prepared = false;  // the data-only constants are stale: bean_hip_prepare comes next
+    return 0;
 }
 
 static int ens_kind(const bean_hip_ctx* c) {
@@ -2021,12 +2092,8 @@ extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds,
     for (int k = 0; same && k < K; ++k) same = c->member_seeds[(size_t)k] == seeds[k];
     if (!same) {
         // (the launches - captured ones too - hold the ADDRESS of this array: new seeds need no new graphs)
-        HIP_OK(hipStreamSynchronize(stream));  // no launch in flight reads the array while it changes
-        c->members_host.resize((size_t)K);
+        if (upload_members(c, seeds, stream)) return -1;
         c->member_seeds.assign(seeds, seeds + K);
-        for (int k = 0; k < K; ++k) c->members_host[(size_t)k] = member_args(c, k, seeds[k]);
-        HIP_OK(hipMemcpyAsync(c->members_dev, c->members_host.data(), (size_t)K * sizeof(DevArgs), hipMemcpyHostToDevice, stream));
-        HIP_OK(hipStreamSynchronize(stream));
         c->members_dirty = false;
     }
     const bool use_graph = graph_chunk > 0 && stream != nullptr;

@@ -70,9 +70,24 @@ class HipSVI:
         lib_variant: Optional[str] = None,
         guide_ids: Optional[torch.Tensor] = None,
         n_members: int = 1,
+        member_masks=None,
     ):
         if family not in _lib.FAMILY:
             raise ValueError(f"unknown model family {family!r}")
+        if member_masks is not None:
+            # per-member masks (bean_hip_bind_member_masks): checked before the library is touched
+            if int(n_members) == 1:
+                raise ValueError("member_masks belongs to an ensemble: n_members > 1")
+            try:
+                m_rg, m_sm = member_masks
+            except (TypeError, ValueError):
+                raise ValueError("member_masks is a pair (repguide (K, R, G) bool, sample_mask (K, R, B))") from None
+            m_rg, m_sm = torch.as_tensor(m_rg), torch.as_tensor(m_sm)
+            want_rg = (int(n_members), data.n_reps, data.n_guides)
+            want_sm = (int(n_members), data.n_reps, data.n_condits)
+            if tuple(m_rg.shape) != want_rg or tuple(m_sm.shape) != want_sm:
+                raise ValueError(f"member_masks: repguide {tuple(m_rg.shape)} / sample_mask {tuple(m_sm.shape)} for "
+                                 f"{int(n_members)} members, expected {want_rg} / {want_sm}")
         survival = getattr(data, "selection", "sorting") == "survival"
         surv_normal = survival and family == "Normal"
         self.surv_normal = surv_normal
@@ -400,6 +415,15 @@ class HipSVI:
                 self._noise_out["eps_cov"] = torch.zeros(self.n_cov, dtype=torch.float64, device=dev)
                 self._bind("EPS_NOISE_OUT", self._noise_out["eps_cov"])
         self.steps_done = 0
+        self.member_masks = member_masks is not None
+        if member_masks is not None:
+            # member k reads its (R, G) / (R, B) slice where a single fit reads REPGUIDE / SAMPLE_MASK
+            rg_k = (m_rg != 0).to(dev, torch.uint8).contiguous()
+            sm_k = f64(m_sm)
+            self._keep["MEMBER_REPGUIDE"], self._keep["MEMBER_SAMPLE_MASK"] = rg_k, sm_k
+            self._check(self.lib.bean_hip_bind_member_masks(
+                self._h, ctypes.c_void_p(rg_k.data_ptr()), rg_k.numel(), ctypes.c_void_p(sm_k.data_ptr()),
+                sm_k.numel() * 8), "bind_member_masks")
         with self._on_stream():
             self._check(self.lib.bean_hip_prepare(self._h, self._sptr()), "prepare")
 

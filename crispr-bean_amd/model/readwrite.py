@@ -167,6 +167,7 @@ def write_result_table(
     is_survival_screen: bool = False,
     seed_sd=None,
     n_seeds: Optional[int] = None,
+    jackknife: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -174,7 +175,13 @@ def write_result_table(
 
     ``seed_sd`` / ``n_seeds`` (a seed ensemble, ``model/ensemble.py``): the element table gets the columns
     ``mu_seed_sd`` - the between-seed standard deviation of every target's ``mu`` - and ``n_seeds``.  Left at ``None``
-    the tables are exactly those of a single fit."""
+    the tables are exactly those of a single fit.
+
+    ``jackknife`` (a replicate jackknife, ``model/jackknife.py::jackknife_summary``): the element table gets exactly the
+    columns ``mu_jk_se``, ``mu_jk_max_shift``, ``mu_jk_max_shift_rep`` and ``n_jk``; every other column and the sgRNA
+    table are those of the run without it.  ``mu_jk_se`` and ``mu_jk_max_shift`` are statistics of the fits' ``mu_loc``,
+    i.e. on the scale of the column ``mu``: with ``negctrl_params`` (``--fit-negctrl``) they are NOT rescaled with
+    ``mu_scaled`` (divide by the control fit's sd to compare), nor stretched like ``mu_sd_adj``."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -187,6 +194,15 @@ def write_result_table(
             raise ValueError(f"seed_sd has {len(spread)} entries for {len(element)} targets")
         element["mu_seed_sd"] = spread
         element["n_seeds"] = int(n_seeds)
+    if jackknife is not None:
+        flat = lambda v: np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)  # noqa: E731
+        se, shift, reps = flat(jackknife["mu_jk_se"]), flat(jackknife["mu_jk_max_shift"]), list(jackknife["mu_jk_max_shift_rep"])
+        if not len(se) == len(shift) == len(reps) == len(element):
+            raise ValueError(f"the jackknife summary has {len(se)} entries for {len(element)} targets")
+        element["mu_jk_se"] = se
+        element["mu_jk_max_shift"] = shift
+        element["mu_jk_max_shift_rep"] = reps
+        element["n_jk"] = int(jackknife["n_jk"])
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

@@ -191,6 +191,71 @@ def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000
     return store, out
 
 
+def _fit_members(model, guide, data, seeds, what, tag, dump_extra, common, report_every, verbose, member_masks=None):
+    """The batched fit behind ``run_inference_ensemble`` and ``run_inference_jackknife``: ``len(seeds)`` members of one
+    engine (member k with ``seeds[k]`` and, if given, its slice of ``member_masks``), stepped in report windows.
+    Returns the list of ``(param_store, {"loss", "params"})`` pairs, or ``None`` where the batched kernels do not take
+    the shape (the caller then fits one after the other).  A non-finite loss of any member halts the fit at the end
+    of its report window with the ``ValueError`` of ``run_inference``: the message names ``what[k]``, the parameters
+    as they were at the start of the window go to ``tmp_result.<tag[k]>.pkl`` together with ``dump_extra[k]``."""
+    from .. import parallel
+    from .._lib import MAX_MEMBERS
+    from ..engine import EnsembleUnsupported
+
+    n = len(seeds)
+    spec = _resolve(model)
+    if spec.family in ("MultiMixtureNormal", "ControlNormal") or spec.selection == "survival" or n > MAX_MEMBERS:
+        return None
+    device = torch.device("cuda", torch.cuda.current_device())
+    extra = {} if member_masks is None else {"member_masks": member_masks}
+    try:
+        eng = build_engine(model, guide, data.to(device), device=device, n_guides_total=data.n_guides,
+                           n_members=n, **extra, **common)
+    except EnsembleUnsupported:
+        return None
+    num_steps = common["num_steps"]
+    try:
+        done = 0
+        while done < num_steps:
+            k = min(report_every, num_steps - done)
+            window_start = eng.snapshot()  # what a halt inside this window dumps
+            eng.run_ensemble(k, seeds)
+            windows = eng.loss_hist[:, done:done + k]
+            for member in range(n):
+                try:
+                    parallel.check_window_finite(windows[member], done)
+                except FloatingPointError as exc:
+                    name = f"tmp_result.{tag[member]}.pkl"
+                    error(f"Error occurred during fitting ({what[member]}, seed {seeds[member]}). "
+                          f"Saving temporary output at {name}.")
+                    with open(name, "wb") as handle:
+                        dump = {p: v.cpu() for p, v in eng.constrained(window_start, member=member).items()}
+                        pkl.dump({"param": dump, **dump_extra[member]}, handle)
+                    raise ValueError(
+                        f"Fitting halted for command: {' '.join(sys.argv)} with following error: \n "
+                        f"{what[member]} (seed {seeds[member]}): {exc}"
+                    )
+            if verbose:
+                print(f"loss {' '.join(str(float(v)) for v in windows[:, 0])} @ iter {done}")
+            done += k
+        losses = eng.losses()
+        results = []
+        for member in range(n):
+            constrained = {p: v.clone() for p, v in eng.constrained(member=member).items()}
+            results.append((ParamStore(constrained),
+                            {"loss": losses[member].tolist(), "params": {p: v.detach().cpu() for p, v in constrained.items()}}))
+    finally:
+        eng.close()
+    return results
+
+
+def _single_rank_only(who):
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError(f"{who} does not combine with guide sharding over several ranks")
+
+
 def run_inference_ensemble(model, guide, data, seeds, initial_lr=0.01, gamma=0.1, num_steps=2000,
                            report_every: int = 100, verbose: bool = True):
     """``len(seeds)`` independent SVI fits of one screen, member k with the random streams of ``seeds[k]``.
@@ -202,67 +267,54 @@ def run_inference_ensemble(model, guide, data, seeds, initial_lr=0.01, gamma=0.1
     fit) is fitted seed after seed through ``run_inference``.  A non-finite loss of ANY member halts the fit at the
     end of its report window with the ``ValueError`` of ``run_inference``; message and dump file
     (``tmp_result.member<k>.pkl``) name the member.  Not combined with guide sharding over several ranks."""
-    import torch.distributed as dist
-
-    from .. import parallel
-    from .._lib import MAX_MEMBERS
-    from ..engine import EnsembleUnsupported
-
     seeds = [int(s) for s in seeds]
     if not seeds:
         raise ValueError("run_inference_ensemble needs at least one seed")
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        raise ValueError("run_inference_ensemble does not combine with guide sharding over several ranks")
+    _single_rank_only("run_inference_ensemble")
     common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
-
-    def one_after_the_other():
-        return [run_inference(model, guide, data, seed=s, report_every=report_every, verbose=verbose, **common)
-                for s in seeds]
-
-    spec = _resolve(model)
-    if (spec.family in ("MultiMixtureNormal", "ControlNormal") or spec.selection == "survival"
-            or len(seeds) > MAX_MEMBERS):
-        return one_after_the_other()
-    device = torch.device("cuda", torch.cuda.current_device())
-    try:
-        eng = build_engine(model, guide, data.to(device), device=device, n_guides_total=data.n_guides,
-                           n_members=len(seeds), **common)
-    except EnsembleUnsupported:
-        return one_after_the_other()
-    try:
-        done = 0
-        while done < num_steps:
-            k = min(report_every, num_steps - done)
-            window_start = eng.snapshot()  # what a halt inside this window dumps
-            eng.run_ensemble(k, seeds)
-            windows = eng.loss_hist[:, done:done + k]
-            for member in range(len(seeds)):
-                try:
-                    parallel.check_window_finite(windows[member], done)
-                except FloatingPointError as exc:
-                    name = f"tmp_result.member{member}.pkl"
-                    error(f"Error occurred during fitting (member {member}, seed {seeds[member]}). "
-                          f"Saving temporary output at {name}.")
-                    with open(name, "wb") as handle:
-                        dump = {n: v.cpu() for n, v in eng.constrained(window_start, member=member).items()}
-                        pkl.dump({"param": dump, "member": member, "seed": seeds[member]}, handle)
-                    raise ValueError(
-                        f"Fitting halted for command: {' '.join(sys.argv)} with following error: \n "
-                        f"member {member} (seed {seeds[member]}): {exc}"
-                    )
-            if verbose:
-                print(f"loss {' '.join(str(float(v)) for v in windows[:, 0])} @ iter {done}")
-            done += k
-        losses = eng.losses()
-        results = []
-        for member in range(len(seeds)):
-            constrained = eng.constrained(member=member)
-            constrained = {n: v.clone() for n, v in constrained.items()}
-            results.append((ParamStore(constrained),
-                            {"loss": losses[member].tolist(), "params": {n: v.detach().cpu() for n, v in constrained.items()}}))
-    finally:
-        eng.close()
+    members = range(len(seeds))
+    results = _fit_members(model, guide, data, seeds, what=[f"member {k}" for k in members],
+                           tag=[f"member{k}" for k in members],
+                           dump_extra=[{"member": k, "seed": seeds[k]} for k in members],
+                           common=common, report_every=report_every, verbose=verbose)
+    if results is None:  # one after the other
+        results = [run_inference(model, guide, data, seed=s, report_every=report_every, verbose=verbose, **common)
+                   for s in seeds]
     return results
+
+
+def run_inference_jackknife(model, guide, data, seed: int = SEED, initial_lr=0.01, gamma=0.1, num_steps=2000,
+                            report_every: int = 100, verbose: bool = True):
+    """Replicate jackknife: the fit of the screen and one fit per replicate with that replicate masked
+    (``model/jackknife.py``), all with the same ``seed`` - common random numbers, so the fits differ through the data
+    and not through the stream.
+
+    Returns ``(full, loo, left_out)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns, ``loo[j]``
+    exactly what it returns for ``leave_out(data, left_out[j])`` - bit for bit - and ``left_out`` lists the replicates
+    that are not already fully masked (fewer than two: ``ValueError``).  Where the batched kernels take the shape
+    (``bean_hip_ensemble_supported``) the 1 + len(left_out) fits are members of one engine that differ in their masks
+    only (``HipSVI(member_masks=...)``, member 0 = the screen's own masks) and are stepped by the same launches, in
+    report windows; every other family (tiling, survival, ControlNormal, sample covariates, screens large enough for
+    the one-launch stepper) is fitted mask after mask through ``run_inference``.  A non-finite loss of any member halts
+    the fit at the end of its report window with the ``ValueError`` of ``run_inference``; message and dump file
+    (``tmp_result.full.pkl`` / ``tmp_result.without_replicate<r>.pkl``, with ``"left_out": r``) name the left-out
+    replicate.  Not combined with guide sharding over several ranks."""
+    from .jackknife import candidate_replicates, leave_out, member_masks
+
+    _single_rank_only("run_inference_jackknife")
+    left_out = candidate_replicates(data)
+    seed = int(seed)
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+    results = _fit_members(model, guide, data, [seed] * (1 + len(left_out)),
+                           what=["the full screen"] + [f"replicate {r} left out" for r in left_out],
+                           tag=["full"] + [f"without_replicate{r}" for r in left_out],
+                           dump_extra=[{"left_out": r, "seed": seed} for r in [None] + list(left_out)],
+                           common=common, report_every=report_every, verbose=verbose,
+                           member_masks=member_masks(data, left_out))
+    if results is None:  # one after the other
+        results = [run_inference(model, guide, d, seed=seed, report_every=report_every, verbose=verbose, **common)
+                   for d in [data] + [leave_out(data, r) for r in left_out]]
+    return results[0], results[1:], left_out
 
 
 def identify_model_guide(args):

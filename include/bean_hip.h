@@ -272,12 +272,33 @@ int bean_hip_svi_run(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_step,
  *                                 with first_step = the previous call's first_step + n_steps continues the fits
  *                                 (windows give the bits of one call).  Injected / dumped noise is refused.
  *
+ *   bean_hip_bind_member_masks    per-member masks: the members may also differ in the two mask arrays (a replicate
+ *                                 jackknife: member j is the screen with one replicate masked).  `repguide` is
+ *                                 (K, R, G) uint8 and `sample_mask` (K, R, B) float64, member-major like the
+ *                                 parameters, device memory the caller keeps alive; member k reads its slice where a
+ *                                 single fit reads BEAN_BUF_REPGUIDE / BEAN_BUF_SAMPLE_MASK.  Those two slots stay
+ *                                 bound and the single-fit entry points (which address member 0) keep reading THEM,
+ *                                 while the data-only words in member 0's workspace are then those of member 0's
+ *                                 slice: on a handle with member masks the single-fit entry points are only
+ *                                 meaningful if member 0's slice equals the shared masks (the jackknife binds it so;
+ *                                 the library does not compare the arrays).  Allowed after bean_hip_set_members and before
+ *                                 bean_hip_prepare: a call marks the handle unprepared, and the following
+ *                                 bean_hip_prepare computes the data-only words that depend on the repguide mask (the
+ *                                 loss constant, the number of unmasked replicates per guide) once per member.
+ *                                 Member k is then, bit for bit, bean_hip_svi_run on a handle of its own whose
+ *                                 BEAN_BUF_REPGUIDE / BEAN_BUF_SAMPLE_MASK are member k's slices (counts, size
+ *                                 factors and every other buffer as bound here).  Null for both returns the handle
+ *                                 to shared masks (prepare again).  The byte counts are checked against K.
+ *
  * Errors (status < 0, message in bean_hip_last_error(), nothing launched): a null handle; set_members on a shape that
  * is not supported, after a bind, with n_members outside [1, BEAN_HIP_MAX_MEMBERS]; run_ensemble with n_seeds !=
- * n_members or null seeds. */
+ * n_members or null seeds; bind_member_masks on a shape that is not supported, before set_members, with one mask null
+ * and the other not, or with byte counts other than K R G and 8 K R B (the message states K). */
 #define BEAN_HIP_MAX_MEMBERS 64
 int bean_hip_ensemble_supported(const bean_hip_ctx* ctx);
 int bean_hip_set_members(bean_hip_ctx* ctx, int32_t n_members);
+int bean_hip_bind_member_masks(bean_hip_ctx* ctx, const void* repguide, uint64_t repguide_bytes,
+                               const void* sample_mask, uint64_t sample_mask_bytes);
 int bean_hip_svi_run_ensemble(bean_hip_ctx* ctx, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
                               uint64_t n_steps, int32_t graph_chunk, void* stream);
 
