@@ -1,4 +1,17 @@
 // libbean_hip.so: C ABI over the BEAN SVI kernels (see include/bean_hip.h).
+//
+// Contents, in this order:
+//   context              bean_hip_ctx, the kernel-template dispatch, expected_bytes, sync_devargs, the graph caches
+//   create/bind/prepare  bean_hip_create ... bean_hip_prepare
+//   launches             launch_timed, launch_param, launch_guide and its forms, set_step / finalize, elbo_grad / adam
+//   stepping             what the entry points share (begin_steps / first_draw / mark_resumable, the noise predicates,
+//                        capture_graph / build_ladder / replay_pairs), the whole-call launches (k_svi_tile,
+//                        k_svi_async), then bean_hip_svi_run, the seed ensemble (_run_ensemble), bean_hip_svi_resume
+//   sharded / comm       bean_hip_sharded_*, bean_hip_comm_*, bean_hip_svi_run_exchanged
+//   introspection        step_bytes, dominant_kernel*, profile, diagnostics
+// Which entry point replays which graph ladder: the table in DESIGN.md, section 1.
+// (Kernel templates are instantiated in the order this file first names them, and that is their order in the code
+// object: moving a launcher moves device code, which scripts/kernel_resources_diff.py and a disassembly diff then show.)
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdio.h>
@@ -8,6 +21,7 @@
 #include <rccl/rccl.h>  // types and enums only: the functions are resolved with dlsym (bean_hip_comm_*)
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/bean_hip.h"
@@ -27,6 +41,7 @@ static int fail(const std::string& msg) {
             return fail(std::string(#expr) + ": " + hipGetErrorString(e_));          \
     } while (0)
 
+// ------------------------------------------------------------------ context
 struct bean_hip_ctx {
     bean_hip_shape shape;
     DevArgs d;
@@ -132,6 +147,27 @@ static bool is_surv_normal(const bean_hip_shape& s) {
 }
 static bool is_mixture(const bean_hip_shape& s) {
     return s.family == BEAN_FAMILY_MIXTURE_NORMAL || s.family == BEAN_FAMILY_MULTI_MIXTURE;
+}
+
+// The kernel-template dispatch, once each: f is a generic lambda that names its kernel as k<fam(), acc()>.
+// family x accessibility of the variant kernels: <kMixture, true>, <kMixture, false>, <kNormal, false>
+template <typename F>
+static auto with_family_acc(const DevArgs& d, F&& f) {
+    if (d.family == kMixture) {
+        if (d.flags & kAcc) return f(std::integral_constant<int, kMixture>{}, std::true_type{});
+        return f(std::integral_constant<int, kMixture>{}, std::false_type{});
+    }
+    return f(std::integral_constant<int, kNormal>{}, std::false_type{});
+}
+// accessibility x survival of the tiling kernels
+template <typename F>
+static auto with_acc_surv(const DevArgs& d, F&& f) {
+    if (d.survival) {
+        if (d.flags & kAcc) return f(std::true_type{}, std::true_type{});
+        return f(std::false_type{}, std::true_type{});
+    }
+    if (d.flags & kAcc) return f(std::true_type{}, std::false_type{});
+    return f(std::false_type{}, std::false_type{});
 }
 
 // Bytes the shape implies for a slot (0 = slot not used by this shape).
@@ -265,22 +301,18 @@ static void sync_devargs(bean_hip_ctx* c) {
     if (d.pi_out && (c->shape.flags & BEAN_FLAG_DUMP_PI)) d.flags |= kDumpPi;
 }
 
+static void destroy_graphs(std::vector<hipGraphExec_t>& graphs) {
+    for (hipGraphExec_t g : graphs)
+        if (g) (void)hipGraphExecDestroy(g);
+    graphs.clear();
+}
+
 static void drop_graph(bean_hip_ctx* c) {
-    for (hipGraphExec_t g : c->graphs)
-        if (g) (void)hipGraphExecDestroy(g);
-    c->graphs.clear();
-    for (hipGraphExec_t g : c->graphs_fused)
-        if (g) (void)hipGraphExecDestroy(g);
-    c->graphs_fused.clear();
-    for (hipGraphExec_t g : c->graphs_xchg)
-        if (g) (void)hipGraphExecDestroy(g);
-    c->graphs_xchg.clear();
-    for (hipGraphExec_t g : c->graphs_resume)
-        if (g) (void)hipGraphExecDestroy(g);
-    c->graphs_resume.clear();
-    for (hipGraphExec_t g : c->graphs_ens)
-        if (g) (void)hipGraphExecDestroy(g);
-    c->graphs_ens.clear();
+    destroy_graphs(c->graphs);
+    destroy_graphs(c->graphs_fused);
+    destroy_graphs(c->graphs_xchg);
+    destroy_graphs(c->graphs_resume);
+    destroy_graphs(c->graphs_ens);
     c->members_dirty = true;
     c->resume_ok = false;  // (called whenever a buffer, the shape-dependent state or the seed changes)
 }
@@ -293,6 +325,7 @@ static void drop_graph_on_seed_change(bean_hip_ctx* c, unsigned long long seed) 
     if (any && c->graph_seed != seed) drop_graph(c);
 }
 
+// ------------------------------------------------------------------ create / bind / prepare
 extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
     if (!s || !out) return fail("bean_hip_create: null argument");
     if (s->selection != BEAN_SELECTION_SORTING && s->selection != BEAN_SELECTION_SURVIVAL)
@@ -881,17 +914,14 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         const void* fn = nullptr;
         if (c->wave_guide && c->wave2) {
             lds = guide_wave2_lds(d.B, d.tile_targets);
-            fn = d.family == kMixture ? (acc ? (const void*)k_guide_wave2<kMixture, true> : (const void*)k_guide_wave2<kMixture, false>)
-                                      : (const void*)k_guide_wave2<kNormal, false>;
+            fn = with_family_acc(d, [](auto fam, auto ac) { return (const void*)k_guide_wave2<fam(), ac()>; });
         } else if (c->tiling_rep || c->tiling_wave) {
             const size_t nt = c->tiling_rep ? 64u * c->tiling_rep_w : 64u;
             lds = guide_tiling_lds(d.B, acc, nt, !c->tiling_rep);
             if (c->tiling_rep)
-                fn = d.survival ? (acc ? (const void*)k_guide_tiling_rep<true, true> : (const void*)k_guide_tiling_rep<false, true>)
-                                : (acc ? (const void*)k_guide_tiling_rep<true, false> : (const void*)k_guide_tiling_rep<false, false>);
+                fn = with_acc_surv(d, [](auto ac, auto surv) { return (const void*)k_guide_tiling_rep<ac(), surv()>; });
             else
-                fn = d.survival ? (acc ? (const void*)k_guide_tiling_wave<true, true> : (const void*)k_guide_tiling_wave<false, true>)
-                                : (acc ? (const void*)k_guide_tiling_wave<true, false> : (const void*)k_guide_tiling_wave<false, false>);
+                fn = with_acc_surv(d, [](auto ac, auto surv) { return (const void*)k_guide_tiling_wave<ac(), surv()>; });
         }
         if (lds > kLdsPerWorkgroupMax)
             return fail("bean_hip_prepare: " + std::to_string(d.B) + " conditions x " + std::to_string(d.tile_targets) +
@@ -948,10 +978,8 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         for (int k = 1; k < c->n_members; ++k)
             HIP_OK(hipMemcpyAsync(c->member_ws + (size_t)(k - 1) * c->member_ws_stride, c->workspace, c->workspace_bytes,
                                   hipMemcpyDeviceToDevice, stream));
-        const bool acc = (c->d.flags & kAcc) != 0;
         const size_t lds = guide_wave2_lds(c->d.B, c->d.tile_targets);
-        const void* fn = c->d.family == kMixture ? (acc ? (const void*)k_guide_wave2_ens<kMixture, true> : (const void*)k_guide_wave2_ens<kMixture, false>)
-                                                 : (const void*)k_guide_wave2_ens<kNormal, false>;
+        const void* fn = with_family_acc(c->d, [](auto fam, auto ac) { return (const void*)k_guide_wave2_ens<fam(), ac()>; });
         if (lds > 65536) HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIP_OK(hipStreamSynchronize(stream));
         drop_graph(c);
@@ -977,6 +1005,41 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
 }
 
 // ------------------------------------------------------------------ launches
+// a profile run that times the guide kernel (mode 1; mode 2 times k_param instead), up to 4096 timed launches
+static bool prof_guide(const bean_hip_ctx* c) { return c->profile && !c->profile_param && c->ev.size() < 8192; }
+
+// One kernel launch.  prof: between two events that carry the kernel's own begin / end timestamps
+// (hipExtLaunchKernelGGL), i.e. the duration rocprofv3 --kernel-trace reports, without the dispatch gap; the pair goes
+// to c->ev.  (A launch that covers several SVI steps adds their number to c->ev_steps itself.)
+template <typename... KArgs, typename... Args>
+static void launch_timed(bean_hip_ctx* c, bool prof, void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds,
+                         hipStream_t stream, Args&&... args) {
+    if (!prof) {
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, static_cast<KArgs>(args)...);
+        return;
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, e0, e1, 0, static_cast<KArgs>(args)...);
+    c->ev.push_back(e0);
+    c->ev.push_back(e1);
+}
+
+// The forms that take several launches (the block forms, the split form's k_lik) and k_guide_tiling_wide are timed from
+// the stream instead: what lies between the two records.  span_begin says whether the run is timed.
+static bool span_begin(bean_hip_ctx* c, hipStream_t stream) {
+    if (!prof_guide(c)) return false;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, stream);
+    c->ev.push_back(e0);
+    c->ev.push_back(e1);
+    return true;
+}
+static void span_end(bean_hip_ctx* c, hipStream_t stream) { (void)hipEventRecord(c->ev.back(), stream); }
+
 static void grid_param(const bean_hip_ctx* c, int& n_target_blocks, int& n_blocks) {
     const DevArgs& d = c->d;
     n_target_blocks = d.wide_targets ? d.T : (int)(((long)d.T * d.lpt + kParamBlock - 1) / kParamBlock);
@@ -1031,13 +1094,6 @@ static void launch_param(bean_hip_ctx* c, hipStream_t stream, const double* tgra
     const bool generic_only = param_generic_only();
     const int kind = generic_only ? 0 : (kind1 ? 1 : (kind2 ? 2 : (kind3 ? 3 : 0)));
     const bool prof = c->profile && c->profile_param && FINISH && PREP && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-    }
     // allele blocks (k_param<..., 3>, sorting): k_allele's work as the tail of this grid
     const int nab = (PREP && kind == 3) ? param_allele_blocks(c, d) : 0;
     if (PREP) c->alleles_fresh = nab > 0;
@@ -1052,18 +1108,13 @@ static void launch_param(bean_hip_ctx* c, hipStream_t stream, const double* tgra
         d.q0_blk0 = ahead_env >= 0 && ahead_env < ngb ? ahead_env : ngb;
     }
     const dim3 grid(nb + nab), block(kParamBlock);
-#define BEAN_LAUNCH_PARAM(K)                                                                                    \
-    do {                                                                                                         \
-        if (prof) hipExtLaunchKernelGGL((k_param<FINISH, ADAM, PREP, K>), grid, block, 0, stream, e0, e1, 0, d, ntb); \
-        else hipLaunchKernelGGL((k_param<FINISH, ADAM, PREP, K>), grid, block, 0, stream, d, ntb);              \
-    } while (0)
+    auto go = [&](auto knd) { launch_timed(c, prof, k_param<FINISH, ADAM, PREP, knd()>, grid, block, 0, stream, d, ntb); };
     switch (kind) {
-        case 1: BEAN_LAUNCH_PARAM(1); break;
-        case 2: BEAN_LAUNCH_PARAM(2); break;
-        case 3: BEAN_LAUNCH_PARAM(3); break;
-        default: BEAN_LAUNCH_PARAM(0); break;
+        case 1: go(std::integral_constant<int, 1>{}); break;
+        case 2: go(std::integral_constant<int, 2>{}); break;
+        case 3: go(std::integral_constant<int, 3>{}); break;
+        default: go(std::integral_constant<int, 0>{}); break;
     }
-#undef BEAN_LAUNCH_PARAM
 }
 
 #ifdef BEAN_AB_KERNELS  // block forms and the split form: A/B references
@@ -1071,27 +1122,15 @@ template <int B>
 static void launch_guide_b(bean_hip_ctx* c, hipStream_t stream, dim3 grid, dim3 block, size_t lds) {
     const DevArgs& d = c->d;
     if (d.survival && d.family != kMultiMixture) {
-        if (d.family == kMixture) {
-            if (d.flags & kAcc)
-                hipLaunchKernelGGL((k_guide_survival<B, kMixture, true>), grid, block, lds, stream, d);
-            else
-                hipLaunchKernelGGL((k_guide_survival<B, kMixture, false>), grid, block, lds, stream, d);
-        } else {
-            hipLaunchKernelGGL((k_guide_survival<B, kNormal, false>), grid, block, lds, stream, d);
-        }
+        with_family_acc(d, [&](auto fam, auto acc) {
+            hipLaunchKernelGGL((k_guide_survival<B, fam(), acc()>), grid, block, lds, stream, d);
+        });
     } else if (d.family == kMultiMixture) {
 #if BEAN_AMAX <= 8
         const size_t tl = ((size_t)kTNumPart * 64 + 16) * sizeof(double);
-        if (d.survival) {
-            if (d.flags & kAcc)
-                hipLaunchKernelGGL((k_guide_tiling<B, true, true>), grid, block, tl, stream, d);
-            else
-                hipLaunchKernelGGL((k_guide_tiling<B, false, true>), grid, block, tl, stream, d);
-        } else if (d.flags & kAcc) {
-            hipLaunchKernelGGL((k_guide_tiling<B, true, false>), grid, block, tl, stream, d);
-        } else {
-            hipLaunchKernelGGL((k_guide_tiling<B, false, false>), grid, block, tl, stream, d);
-        }
+        with_acc_surv(d, [&](auto acc, auto surv) {
+            hipLaunchKernelGGL((k_guide_tiling<B, acc(), surv()>), grid, block, tl, stream, d);
+        });
 #endif
     }
 }
@@ -1100,14 +1139,9 @@ static int waves_per_block(const bean_hip_ctx* c) { return c->d.R < 8 ? c->d.R :
 
 static void launch_lik(bean_hip_ctx* c, hipStream_t stream, dim3 grid, dim3 block, size_t lds) {
     const DevArgs& d = c->d;
-    if (d.family == kMixture) {
-        if (d.flags & kAcc)
-            hipLaunchKernelGGL((k_lik<true, true>), grid, block, lds, stream, d);
-        else
-            hipLaunchKernelGGL((k_lik<true, false>), grid, block, lds, stream, d);
-    } else {
-        hipLaunchKernelGGL((k_lik<false, false>), grid, block, lds, stream, d);
-    }
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_lik<fam() == kMixture, acc()>), grid, block, lds, stream, d);
+    });
 }
 
 // sorting variant families as three launches (see bean_kernels.hpp, "split form")
@@ -1121,19 +1155,9 @@ static void launch_guide_split(bean_hip_ctx* c, hipStream_t stream) {
         const long n = (long)d.R * d.G;
         hipLaunchKernelGGL(k_sample_pi, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d);
     }
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        (void)hipEventRecord(e0, stream);
-    }
+    const bool prof = span_begin(c, stream);
     launch_lik(c, stream, dim3((d.G + 63) / 64, d.R), dim3(64 * nlik), 0);
-    if (prof) {
-        (void)hipEventRecord(e1, stream);
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-    }
+    if (prof) span_end(c, stream);
     if (mix) {
         const size_t l3 = ((size_t)rep_waves * 7 * 64 + 16) * sizeof(double);
         hipLaunchKernelGGL(k_pi_terms, grid, dim3(64 * rep_waves), l3, stream, d);
@@ -1150,31 +1174,9 @@ static void launch_guide_wave2(bean_hip_ctx* c, hipStream_t stream) {
     // BEAN_HIP_LDS_PAD (bytes; experiments only): a larger LDS request lowers the number of resident waves
     static const size_t lds_pad = getenv("BEAN_HIP_LDS_PAD") ? (size_t)atol(getenv("BEAN_HIP_LDS_PAD")) : 0;
     const size_t lds = guide_wave2_lds(d.B, d.tile_targets) + lds_pad;
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        if (d.family == kMixture) {
-            if (d.flags & kAcc)
-                hipExtLaunchKernelGGL((k_guide_wave2<kMixture, true>), grid, block, lds, stream, e0, e1, 0, d);
-            else
-                hipExtLaunchKernelGGL((k_guide_wave2<kMixture, false>), grid, block, lds, stream, e0, e1, 0, d);
-        } else {
-            hipExtLaunchKernelGGL((k_guide_wave2<kNormal, false>), grid, block, lds, stream, e0, e1, 0, d);
-        }
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-        return;
-    }
-    if (d.family == kMixture) {
-        if (d.flags & kAcc)
-            hipLaunchKernelGGL((k_guide_wave2<kMixture, true>), grid, block, lds, stream, d);
-        else
-            hipLaunchKernelGGL((k_guide_wave2<kMixture, false>), grid, block, lds, stream, d);
-    } else {
-        hipLaunchKernelGGL((k_guide_wave2<kNormal, false>), grid, block, lds, stream, d);
-    }
+    with_family_acc(d, [&](auto fam, auto acc) {
+        launch_timed(c, prof_guide(c), k_guide_wave2<fam(), acc()>, grid, block, lds, stream, d);
+    });
 }
 
 #ifdef BEAN_AB_KERNELS
@@ -1184,33 +1186,9 @@ static void launch_guide_wave(bean_hip_ctx* c, hipStream_t stream) {
     const dim3 grid((d.G + 63) / 64, d.R), block(64);
     const size_t lds = ((size_t)3 * d.B * d.tile_targets + (size_t)kWaveMisc * 64) * sizeof(double) +
                        (size_t)2 * d.B * 64 * sizeof(float);
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        // profile mode: the events carry the kernel's own begin / end timestamps (hipExtLaunchKernelGGL),
-        // i.e. the duration rocprofv3 --kernel-trace reports, without the dispatch gap
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        if (d.family == kMixture) {
-            if (d.flags & kAcc)
-                hipExtLaunchKernelGGL((k_guide_wave<kMixture, true>), grid, block, lds, stream, e0, e1, 0, d);
-            else
-                hipExtLaunchKernelGGL((k_guide_wave<kMixture, false>), grid, block, lds, stream, e0, e1, 0, d);
-        } else {
-            hipExtLaunchKernelGGL((k_guide_wave<kNormal, false>), grid, block, lds, stream, e0, e1, 0, d);
-        }
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-        return;
-    }
-    if (d.family == kMixture) {
-        if (d.flags & kAcc)
-            hipLaunchKernelGGL((k_guide_wave<kMixture, true>), grid, block, lds, stream, d);
-        else
-            hipLaunchKernelGGL((k_guide_wave<kMixture, false>), grid, block, lds, stream, d);
-    } else {
-        hipLaunchKernelGGL((k_guide_wave<kNormal, false>), grid, block, lds, stream, d);
-    }
+    with_family_acc(d, [&](auto fam, auto acc) {
+        launch_timed(c, prof_guide(c), k_guide_wave<fam(), acc()>, grid, block, lds, stream, d);
+    });
 }
 
 #endif  // BEAN_AB_KERNELS
@@ -1221,27 +1199,9 @@ static void launch_guide_tiling_wave(bean_hip_ctx* c, hipStream_t stream) {
     const bool acc = (d.flags & kAcc) != 0;
     const dim3 grid((unsigned)(((d.G + 63) / 64 + 7) / 8 * 8) * (unsigned)d.R), block(64);
     const size_t lds = guide_tiling_lds(d.B, acc, 64, true);
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    if (prof) {  // events with the kernel's own timestamps, as in launch_guide_wave
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        if (d.survival) {
-            if (acc) hipExtLaunchKernelGGL((k_guide_tiling_wave<true, true>), grid, block, lds, stream, e0, e1, 0, d);
-            else hipExtLaunchKernelGGL((k_guide_tiling_wave<false, true>), grid, block, lds, stream, e0, e1, 0, d);
-        } else {
-            if (acc) hipExtLaunchKernelGGL((k_guide_tiling_wave<true, false>), grid, block, lds, stream, e0, e1, 0, d);
-            else hipExtLaunchKernelGGL((k_guide_tiling_wave<false, false>), grid, block, lds, stream, e0, e1, 0, d);
-        }
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-    } else if (d.survival) {
-        if (acc) hipLaunchKernelGGL((k_guide_tiling_wave<true, true>), grid, block, lds, stream, d);
-        else hipLaunchKernelGGL((k_guide_tiling_wave<false, true>), grid, block, lds, stream, d);
-    } else {
-        if (acc) hipLaunchKernelGGL((k_guide_tiling_wave<true, false>), grid, block, lds, stream, d);
-        else hipLaunchKernelGGL((k_guide_tiling_wave<false, false>), grid, block, lds, stream, d);
-    }
+    with_acc_surv(d, [&](auto ac, auto surv) {
+        launch_timed(c, prof_guide(c), k_guide_tiling_wave<ac(), surv()>, grid, block, lds, stream, d);
+    });
     hipLaunchKernelGGL(k_sum_trow, dim3((d.G + 255) / 256, kTNumPart), dim3(256), 0, stream, d);
 }
 
@@ -1266,62 +1226,21 @@ static void launch_guide_tiling_rep(bean_hip_ctx* c, hipStream_t stream) {
     if (prio_mode) gw |= 1 << 16;
     const dim3 grid(n_wg), block(nt);
     const size_t lds = guide_tiling_lds(d.B, acc, (size_t)nt, false);
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {  // events with the kernel's own timestamps
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-    }
-#define BEAN_LAUNCH_TREP(ACC_, SURV_)                                                                              \
-    do {                                                                                                          \
-        if (prof) hipExtLaunchKernelGGL((k_guide_tiling_rep<ACC_, SURV_>), grid, block, lds, stream, e0, e1, 0, d, gw); \
-        else hipLaunchKernelGGL((k_guide_tiling_rep<ACC_, SURV_>), grid, block, lds, stream, d, gw);              \
-    } while (0)
-    if (d.survival) {
-        if (acc) BEAN_LAUNCH_TREP(true, true);
-        else BEAN_LAUNCH_TREP(false, true);
-    } else {
-        if (acc) BEAN_LAUNCH_TREP(true, false);
-        else BEAN_LAUNCH_TREP(false, false);
-    }
-#undef BEAN_LAUNCH_TREP
+    with_acc_surv(d, [&](auto ac, auto surv) {
+        launch_timed(c, prof_guide(c), k_guide_tiling_rep<ac(), surv()>, grid, block, lds, stream, d, gw);
+    });
 }
 
 #ifdef BEAN_AB_KERNELS
-// survival variant families, one wave per (guide tile, replicate) (bean_survival_v2.hpp)
 // One SVI step in one launch (bean_step_v2.hpp); `flip` alternates the step-counter buffers.
 static void launch_step_wave2(bean_hip_ctx* c, hipStream_t stream, int flip) {
     const DevArgs& d = c->d;
     const int tiles = d.n_tiles;
     const dim3 grid((unsigned)((tiles + 7) / 8 * 8) * (unsigned)d.R), block(64);
     const size_t lds = guide_wave2_lds(d.B, d.tile_targets);
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        if (d.family == kMixture) {
-            if (d.flags & kAcc)
-                hipExtLaunchKernelGGL((k_step_wave2<kMixture, true>), grid, block, lds, stream, e0, e1, 0, d, flip);
-            else
-                hipExtLaunchKernelGGL((k_step_wave2<kMixture, false>), grid, block, lds, stream, e0, e1, 0, d, flip);
-        } else {
-            hipExtLaunchKernelGGL((k_step_wave2<kNormal, false>), grid, block, lds, stream, e0, e1, 0, d, flip);
-        }
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-        return;
-    }
-    if (d.family == kMixture) {
-        if (d.flags & kAcc)
-            hipLaunchKernelGGL((k_step_wave2<kMixture, true>), grid, block, lds, stream, d, flip);
-        else
-            hipLaunchKernelGGL((k_step_wave2<kMixture, false>), grid, block, lds, stream, d, flip);
-    } else {
-        hipLaunchKernelGGL((k_step_wave2<kNormal, false>), grid, block, lds, stream, d, flip);
-    }
+    with_family_acc(d, [&](auto fam, auto acc) {
+        launch_timed(c, prof_guide(c), k_step_wave2<fam(), acc()>, grid, block, lds, stream, d, flip);
+    });
 }
 
 #endif  // BEAN_AB_KERNELS
@@ -1332,29 +1251,9 @@ static void launch_guide_survival_wave(bean_hip_ctx* c, hipStream_t stream) {
     const int tiles = (d.G + 63) / 64;
     const dim3 grid((unsigned)((tiles + 7) / 8 * 8) * (unsigned)d.R), block(64);
     const size_t lds = guide_survival_wave_lds(d.B);
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        if (d.family == kMixture) {
-            if (d.flags & kAcc)
-                hipExtLaunchKernelGGL((k_guide_survival_wave<kMixture, true>), grid, block, lds, stream, e0, e1, 0, d);
-            else
-                hipExtLaunchKernelGGL((k_guide_survival_wave<kMixture, false>), grid, block, lds, stream, e0, e1, 0, d);
-        } else {
-            hipExtLaunchKernelGGL((k_guide_survival_wave<kNormal, false>), grid, block, lds, stream, e0, e1, 0, d);
-        }
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-    } else if (d.family == kMixture) {
-        if (d.flags & kAcc)
-            hipLaunchKernelGGL((k_guide_survival_wave<kMixture, true>), grid, block, lds, stream, d);
-        else
-            hipLaunchKernelGGL((k_guide_survival_wave<kMixture, false>), grid, block, lds, stream, d);
-    } else {
-        hipLaunchKernelGGL((k_guide_survival_wave<kNormal, false>), grid, block, lds, stream, d);
-    }
+    with_family_acc(d, [&](auto fam, auto acc) {
+        launch_timed(c, prof_guide(c), k_guide_survival_wave<fam(), acc()>, grid, block, lds, stream, d);
+    });
     if (d.surv_q0lik)  // projection term of the G-dimensional Dirichlet's pathwise gradient
         hipLaunchKernelGGL(k_sum_q, dim3(d.R), dim3(1024), 0, stream, d);
 }
@@ -1395,40 +1294,19 @@ static void launch_guide(bean_hip_ctx* c, hipStream_t stream) {
         return;
     }
     if (c->tiling_wide) {
-        const bool acc = (d.flags & kAcc) != 0;
         const dim3 gridw((unsigned)(((long)d.G + 7) / 8 * 8 * d.R)), blockw(64);
-        const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (prof) {
-            (void)hipEventCreate(&e0);
-            (void)hipEventCreate(&e1);
-            (void)hipEventRecord(e0, stream);
-        }
-        if (d.survival) {
-            if (acc) hipLaunchKernelGGL((k_guide_tiling_wide<true, true>), gridw, blockw, 0, stream, d);
-            else hipLaunchKernelGGL((k_guide_tiling_wide<false, true>), gridw, blockw, 0, stream, d);
-        } else {
-            if (acc) hipLaunchKernelGGL((k_guide_tiling_wide<true, false>), gridw, blockw, 0, stream, d);
-            else hipLaunchKernelGGL((k_guide_tiling_wide<false, false>), gridw, blockw, 0, stream, d);
-        }
-        if (prof) {
-            (void)hipEventRecord(e1, stream);
-            c->ev.push_back(e0);
-            c->ev.push_back(e1);
-        }
+        const bool prof = span_begin(c, stream);
+        with_acc_surv(d, [&](auto acc, auto surv) {
+            hipLaunchKernelGGL((k_guide_tiling_wide<acc(), surv()>), gridw, blockw, 0, stream, d);
+        });
+        if (prof) span_end(c, stream);
         return;
     }
 #ifdef BEAN_AB_KERNELS  // block forms
     const int nw = waves_per_block(c);
     const dim3 grid((d.G + 63) / 64), block(64 * nw);
     const size_t lds = ((size_t)nw * kNumPart * 64 + 16) * sizeof(double);
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (prof) {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        (void)hipEventRecord(e0, stream);
-    }
+    const bool prof = span_begin(c, stream);
     switch (d.B) {
         case 1: launch_guide_b<1>(c, stream, grid, block, lds); break;
         case 2: launch_guide_b<2>(c, stream, grid, block, lds); break;
@@ -1453,11 +1331,7 @@ static void launch_guide(bean_hip_ctx* c, hipStream_t stream) {
     }
     if (d.surv_q0lik)  // projection term of the G-dimensional Dirichlet's pathwise gradient
         hipLaunchKernelGGL(k_sum_q, dim3(d.R), dim3(1024), 0, stream, d);
-    if (prof) {
-        (void)hipEventRecord(e1, stream);
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-    }
+    if (prof) span_end(c, stream);
 #endif
 }
 
@@ -1512,6 +1386,43 @@ extern "C" int bean_hip_adam(bean_hip_ctx* c, uint64_t t, void* stream_) {
     return 0;
 }
 
+// ------------------------------------------------------------------ stepping entry points
+// ---- what they share
+// The checks every stepping entry point opens with; `who` prefixes the messages.  Returns 1 to go on; otherwise the
+// entry point's own return value: -1 (failed, bean_hip_last_error says why) or 0 (no steps asked for).
+static int begin_steps(bean_hip_ctx* c, const char* who, uint64_t first_step, uint64_t n_steps) {
+    if (!c) return fail(std::string(who) + ": null handle");
+    if (!c->prepared) return fail(std::string(who) + ": call bean_hip_prepare first");
+    if (check_bound(c, false, true)) return -1;
+    if (n_steps == 0) return 0;
+    if (first_step + n_steps > c->loss_capacity)
+        return fail(std::string(who) + ": loss_hist too small for first_step + n_steps");
+    return 1;
+}
+
+// the loss window of the call's n_steps steps to zero, then the draw and tables of its first step
+static void first_draw(bean_hip_ctx* c, hipStream_t stream, uint64_t first_step, uint64_t n_steps) {
+    launch_set_step(c, stream, first_step, first_step, n_steps);
+    launch_param<false, false, true>(c, stream);
+}
+
+// the call's last launch has drawn step `next` and filled its tables: a bean_hip_svi_resume of that step, with the same
+// seed on the same stream, goes on from there
+static void mark_resumable(bean_hip_ctx* c, uint64_t seed, uint64_t next, void* stream) {
+    c->resume_ok = true;
+    c->resume_next = next;
+    c->resume_seed = seed;
+    c->resume_stream = stream;
+}
+
+// Noise injected or dumped at every step: the eps / pi buffers every stepping path asks about.  The sites add what
+// else they look at (pi_out, x0_*, eps_u_*, kDumpPi): those sets differ from site to site, which is inherited and not
+// reviewed here.
+static bool per_step_noise(const DevArgs& d) {
+    return d.eps_mu_in || d.eps_sd_in || d.pi_in || d.eps_noise_in || d.eps_mu_out || d.eps_sd_out || d.eps_noise_out;
+}
+static bool dumps_pi(const DevArgs& d) { return (d.flags & kDumpPi) != 0; }
+
 static void enqueue_pairs(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
     for (uint64_t i = 0; i < n; ++i) {
         launch_param<true, true, true>(c, stream);
@@ -1519,8 +1430,7 @@ static void enqueue_pairs(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
     }
 }
 
-// Capture 2^k {k_param, guide} pairs into an executable graph.  On any failure the stream is taken
-// out of capture mode before returning.
+// n launches of k_step_wave2 (A/B build), the step-counter buffers alternating from flip0
 static void enqueue_fused(bean_hip_ctx* c, hipStream_t stream, uint64_t n, int flip0 = 0) {
 #ifdef BEAN_AB_KERNELS
     for (uint64_t i = 0; i < n; ++i) launch_step_wave2(c, stream, (int)((i + flip0) & 1));
@@ -1529,15 +1439,18 @@ static void enqueue_fused(bean_hip_ctx* c, hipStream_t stream, uint64_t n, int f
 #endif
 }
 
-static void enqueue_pairs_ens(bean_hip_ctx* c, hipStream_t stream, uint64_t n);
-static int capture_pairs(bean_hip_ctx* c, hipStream_t stream, uint64_t n, hipGraphExec_t* out, bool fused = false,
-                         bool ens = false) {
+// Capture what enqueue() launches on `stream` into an executable graph; enqueue returns 0 or, having called fail, -1.
+// A capture runs nothing, so the allele-table state is saved, set to what a replay will find at the graph's head
+// (head_fresh; graphs that begin with a PREP launch of k_param do not care) and restored.  Whatever fails, the stream
+// is taken out of capture mode and a partial graph destroyed before returning.
+template <typename Enqueue>
+static int capture_graph(bean_hip_ctx* c, hipStream_t stream, bool head_fresh, Enqueue&& enqueue, hipGraphExec_t* out) {
+    *out = nullptr;
     hipGraph_t graph = nullptr;
     HIP_OK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    const bool fresh_was = c->alleles_fresh;  // (a capture runs nothing; these graphs begin with a PREP launch)
-    if (ens) enqueue_pairs_ens(c, stream, n);
-    else if (fused) enqueue_fused(c, stream, n);
-    else enqueue_pairs(c, stream, n);
+    const bool fresh_was = c->alleles_fresh;
+    c->alleles_fresh = head_fresh;
+    const int rc = enqueue();
     c->alleles_fresh = fresh_was;
     hipError_t e = hipStreamEndCapture(stream, &graph);
     if (e != hipSuccess) {
@@ -1551,11 +1464,58 @@ static int capture_pairs(bean_hip_ctx* c, hipStream_t stream, uint64_t n, hipGra
         (void)hipGetLastError();
         return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
     }
-    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) {
+    int ret = rc;  // (a failed enqueue has said why)
+    if (rc == 0 && (e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0)) != hipSuccess) {
         *out = nullptr;
-        return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+        ret = fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
+    }
+    if (graph) (void)hipGraphDestroy(graph);
+    return ret;
+}
+
+// A ladder of graphs: rung k replays (base << k) units of what enqueue_n(n) launches.  The top rung is the largest
+// k <= cap whose size is within graph_chunk (rung 0 when even the base is larger).
+static int top_rung(int32_t graph_chunk, uint64_t base, int cap) {
+    int k = 0;
+    while ((base << (k + 1)) <= (uint64_t)graph_chunk && k < cap) ++k;
+    return k;
+}
+// All the rungs are instantiated at once (nothing is instantiated inside a later, possibly timed, call).  The step
+// counters live on the device, so the graphs do not depend on the step.  On failure the rungs captured so far stay in
+// `ladder`: the caller drops them its own way.
+template <typename EnqueueN>
+static int build_ladder(bean_hip_ctx* c, std::vector<hipGraphExec_t>& ladder, hipStream_t stream, int n_rungs, uint64_t base,
+                        bool head_fresh, EnqueueN&& enqueue_n) {
+    for (int k = 0; k < n_rungs; ++k) {
+        hipGraphExec_t ge = nullptr;
+        if (capture_graph(c, stream, head_fresh, [&] { return enqueue_n(base << k); }, &ge)) return -1;
+        ladder.push_back(ge);
+    }
+    return 0;
+}
+
+// `pairs` {k_param, guide} pairs as a sum of the rungs of a ladder of base 1 (bean_hip_svi_run and the ensemble).
+// Smallest graphs first: the device works on them while the host submits the larger ones (a launch of the 64-pair graph
+// costs the host more than the step or two already enqueued); the top rung is repeated.  A graph launch costs ~8.5 us
+// of idle device time at its boundary - measured on the kernel timeline of a 20-step call - so one or two pairs are
+// launched directly: six eager launches run back to back.
+template <typename EnqueueN>
+static int replay_pairs(bean_hip_ctx* c, const std::vector<hipGraphExec_t>& ladder, hipStream_t stream, uint64_t pairs,
+                        EnqueueN&& enqueue_n) {
+    const int kmax = (int)ladder.size() - 1;
+    const uint64_t big = pairs >> kmax;           // launches of the largest graph
+    const uint64_t rest = pairs - (big << kmax);  // < 2^kmax: one launch per set bit, ascending
+    for (int k = 0; k < kmax; ++k)
+        if (rest & (1ull << k)) {
+            if (k < 2) enqueue_n(1ull << k);
+            else {
+                HIP_OK(hipGraphLaunch(ladder[k], stream));
+                c->alleles_fresh = true;  // (a graph of pairs ends with a guide launch)
+            }
+        }
+    for (uint64_t i = 0; i < big; ++i) {
+        HIP_OK(hipGraphLaunch(ladder[kmax], stream));
+        c->alleles_fresh = true;
     }
     return 0;
 }
@@ -1583,24 +1543,11 @@ static int launch_svi_tile_t(bean_hip_ctx* c, hipStream_t stream, uint64_t step0
     const int blocks = c->n_tiles < c->tile_blocks ? c->n_tiles : c->tile_blocks;
     const int* tg0 = c->tile_tab;
     const int* tt0 = c->tile_tab + (c->n_tiles + 1);
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    if (prof) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        hipExtLaunchKernelGGL((k_svi_tile<FAM, ACC>), dim3(blocks), dim3(kTileThreads), lds, stream, e0, e1, 0, d, (const DevArgs*)c->dargs_dev,
-                              tg0, tt0,
-                              c->n_tiles, c->tile_ntm, c->tile_gbm, (unsigned long long)step0, (unsigned long long)slot0,
-                              (int)n_steps, prep_last ? 1 : 0, (const float*)c->step_sizes);
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-        c->ev_steps.push_back(n_steps);
-    } else {
-        hipLaunchKernelGGL((k_svi_tile<FAM, ACC>), dim3(blocks), dim3(kTileThreads), lds, stream, d, (const DevArgs*)c->dargs_dev, tg0, tt0,
-                           c->n_tiles,
-                           c->tile_ntm, c->tile_gbm, (unsigned long long)step0, (unsigned long long)slot0, (int)n_steps,
-                           prep_last ? 1 : 0, (const float*)c->step_sizes);
-    }
+    const bool prof = prof_guide(c);
+    launch_timed(c, prof, k_svi_tile<FAM, ACC>, dim3(blocks), dim3(kTileThreads), lds, stream, d, (const DevArgs*)c->dargs_dev,
+                 tg0, tt0, c->n_tiles, c->tile_ntm, c->tile_gbm, (unsigned long long)step0, (unsigned long long)slot0,
+                 (int)n_steps, prep_last ? 1 : 0, (const float*)c->step_sizes);
+    if (prof) c->ev_steps.push_back(n_steps);
     return 0;
 }
 
@@ -1619,23 +1566,20 @@ static int launch_svi_tile(bean_hip_ctx* c, hipStream_t stream, uint64_t step0, 
     if (!c->dargs_dev) HIP_OK(hipMalloc((void**)&c->dargs_dev, sizeof(DevArgs)));
     // (the kernel-argument copy and this one are the same bytes: c->d as it is now)
     hipLaunchKernelGGL(k_put_args, dim3(1), dim3(64), 0, stream, d, c->dargs_dev);
-    if (d.family == kMixture) {
-        if (d.flags & kAcc) return launch_svi_tile_t<kMixture, true>(c, stream, step0, step0, n_steps, false);
-        return launch_svi_tile_t<kMixture, false>(c, stream, step0, step0, n_steps, false);
-    }
-    return launch_svi_tile_t<kNormal, false>(c, stream, step0, step0, n_steps, false);
+    return with_family_acc(d, [&](auto fam, auto acc) {
+        return launch_svi_tile_t<fam(), acc()>(c, stream, step0, step0, n_steps, false);
+    });
 }
 
 #endif  // BEAN_AB_KERNELS
 
 // ---- all the steps of a call in one launch: bean_async_v2.hpp
-// (n_steps: the call's; a group's queue counter is an int)
+// whether a call of n_steps steps takes the one asynchronous launch (bean_async_v2.hpp; a group's queue counter is an int)
 static bool async_candidate(const bean_hip_ctx* c, uint64_t n_steps) {
     const DevArgs& d = c->d;
     const uint64_t per_group = (uint64_t)((d.n_tiles + 7) / 8) * (uint64_t)d.R;
     if (n_steps == 0 || per_group * n_steps > 2000000000ull) return false;
-    return c->async_step && !c->profile_param && !d.eps_mu_in && !d.eps_sd_in && !d.pi_in && !d.eps_noise_in &&
-           !d.eps_mu_out && !d.eps_sd_out && !d.eps_noise_out && !(d.flags & kDumpPi) && d.lpart && d.tile_ctr &&
+    return c->async_step && !c->profile_param && !per_step_noise(d) && !dumps_pi(d) && d.lpart && d.tile_ctr &&
            (d.family != kMixture || d.dgq);
 }
 
@@ -1693,20 +1637,10 @@ static int launch_svi_async_t(bean_hip_ctx* c, hipStream_t stream, const AsyncAr
     } else {
         a.n_guide_blocks = 0;
     }
-    const bool prof = c->profile && !c->profile_param && c->ev.size() < 8192;
-    if (prof) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        hipExtLaunchKernelGGL((k_svi_async<FAM, ACC>), dim3(blocks), dim3(64), lds, stream, e0, e1, 0,
-                              (const DevArgs*)c->dargs_dev, d.R, d.n_tiles, a);
-        c->ev.push_back(e0);
-        c->ev.push_back(e1);
-        c->ev_steps.push_back((uint64_t)a.n_steps);
-    } else {
-        hipLaunchKernelGGL((k_svi_async<FAM, ACC>), dim3(blocks), dim3(64), lds, stream, (const DevArgs*)c->dargs_dev, d.R,
-                           d.n_tiles, a);
-    }
+    const bool prof = prof_guide(c);
+    launch_timed(c, prof, k_svi_async<FAM, ACC>, dim3(blocks), dim3(64), lds, stream, (const DevArgs*)c->dargs_dev, d.R,
+                 d.n_tiles, a);
+    if (prof) c->ev_steps.push_back((uint64_t)a.n_steps);
     if (roles_out) *roles_out = a.n_guide_blocks;
     return 0;
 }
@@ -1773,101 +1707,61 @@ static int launch_svi_async(bean_hip_ctx* c, hipStream_t stream, uint64_t step0,
         c->async_stamp_words = words;
     }
 #endif
-    int rc;
-    if (d.family == kMixture) {
-        if (d.flags & kAcc) rc = launch_svi_async_t<kMixture, true>(c, stream, a, nullptr);
-        else rc = launch_svi_async_t<kMixture, false>(c, stream, a, nullptr);
-    } else {
-        rc = launch_svi_async_t<kNormal, false>(c, stream, a, nullptr);
-    }
-    return rc;
+    return with_family_acc(d, [&](auto fam, auto acc) { return launch_svi_async_t<fam(), acc()>(c, stream, a, nullptr); });
 }
 
 extern "C" int bean_hip_svi_run(bean_hip_ctx* c, uint64_t seed, uint64_t first_step, uint64_t n_steps,
                                 int32_t graph_chunk, void* stream_) {
-    if (!c) return fail("bean_hip_svi_run: null handle");
-    if (!c->prepared) return fail("bean_hip_svi_run: call bean_hip_prepare first");
-    if (check_bound(c, false, true)) return -1;
-    if (n_steps == 0) return 0;
-    if (first_step + n_steps > c->loss_capacity)
-        return fail("bean_hip_svi_run: loss_hist too small for first_step + n_steps");
+    const int go = begin_steps(c, "bean_hip_svi_run", first_step, n_steps);
+    if (go <= 0) return go;
     hipStream_t stream = (hipStream_t)stream_;
     drop_graph_on_seed_change(c, seed);
     c->d.seed = seed;
     c->resume_ok = false;
-    const bool tile_candidate = c->tile_svi && c->tile_ready && !c->profile_param && !c->d.eps_mu_in && !c->d.eps_sd_in &&
-                                !c->d.pi_in && !c->d.eps_noise_in && !c->d.eps_mu_out && !c->d.eps_sd_out &&
-                                !c->d.eps_noise_out && !(c->d.flags & kDumpPi);
-    const bool use_graph = graph_chunk > 0 && stream != nullptr && !c->profile && !tile_candidate;
-    // one launch per step unless per-step noise is injected or dumped, or k_param itself is being timed
     const DevArgs& dd = c->d;
-    const bool fused = c->fused_step && !c->profile_param && !dd.eps_mu_in && !dd.eps_sd_in && !dd.pi_in &&
-                       !dd.eps_noise_in && !dd.eps_mu_out && !dd.eps_sd_out && !dd.eps_noise_out;
+    // one launch for all the steps of the call (bean_tile_svi.hpp) unless per-step noise is injected or
+    // dumped, k_param is being timed, or the shape is not eligible
+    const bool tile = c->tile_svi && c->tile_ready && !c->profile_param && !per_step_noise(dd) && !dumps_pi(dd);
+    const bool use_graph = graph_chunk > 0 && stream != nullptr && !c->profile && !tile;
+    // one launch per step unless per-step noise is injected or dumped, or k_param itself is being timed
+    // (kDumpPi is not asked about here, unlike `tile` and the asynchronous path: inherited, not reviewed here)
+    const bool fused = c->fused_step && !c->profile_param && !per_step_noise(dd);
+    auto pairs_n = [&](uint64_t n) {
+        enqueue_pairs(c, stream, n);
+        return 0;
+    };
     if (use_graph) {
-        // Graphs of 1, 2, 4, ... <= graph_chunk pairs, all instantiated at the first call (nothing is
-        // instantiated inside a later, possibly timed, call); any number of pairs is then replayed
-        // as a sum of powers of two.  The step counters live on the device, so the graphs do not
-        // depend on the step.
-        int kmax = 0;
-        while ((2ull << kmax) <= (uint64_t)graph_chunk && kmax < 10) ++kmax;
-        if (fused) {
-            // graphs of 2, 4, ... <= graph_chunk launches
-            const int n_graphs = kmax > 0 ? kmax : 1;
-            if ((int)c->graphs_fused.size() != n_graphs) {
-                drop_graph(c);
-                for (int k = 0; k < n_graphs; ++k) {
-                    hipGraphExec_t ge = nullptr;
-                    if (capture_pairs(c, stream, 2ull << k, &ge, true)) {
-                        drop_graph(c);
-                        return -1;
-                    }
-                    c->graphs_fused.push_back(ge);
-                }
-                c->graph_seed = seed;
-            }
-        } else if ((int)c->graphs.size() != kmax + 1) {
+        // graphs of 1, 2, 4, ... <= graph_chunk pairs; the one-launch step: of 2, 4, ... <= graph_chunk launches
+        const int kmax = top_rung(graph_chunk, 1, 10);
+        std::vector<hipGraphExec_t>& ladder = fused ? c->graphs_fused : c->graphs;
+        const int n_rungs = fused ? (kmax > 0 ? kmax : 1) : kmax + 1;
+        if ((int)ladder.size() != n_rungs) {
             drop_graph(c);
-            for (int k = 0; k <= kmax; ++k) {
-                hipGraphExec_t ge = nullptr;
-                if (capture_pairs(c, stream, 1ull << k, &ge)) {
-                    drop_graph(c);
-                    return -1;
-                }
-                c->graphs.push_back(ge);
+            auto fused_n = [&](uint64_t n) {
+                enqueue_fused(c, stream, n);
+                return 0;
+            };
+            const int rc = fused ? build_ladder(c, ladder, stream, n_rungs, 2, c->alleles_fresh, fused_n)
+                                 : build_ladder(c, ladder, stream, n_rungs, 1, c->alleles_fresh, pairs_n);
+            if (rc) {
+                drop_graph(c);
+                return -1;
             }
             c->graph_seed = seed;
         }
     }
-    // one launch for all the steps of the call (bean_tile_svi.hpp) unless per-step noise is injected or
-    // dumped, k_param is being timed, or the shape is not eligible
-    const bool tile = c->tile_svi && c->tile_ready && !c->profile_param && !dd.eps_mu_in && !dd.eps_sd_in && !dd.pi_in &&
-                      !dd.eps_noise_in && !dd.eps_mu_out && !dd.eps_sd_out && !dd.eps_noise_out && !(dd.flags & kDumpPi);
-#ifdef BEAN_AB_KERNELS
+    first_draw(c, stream, first_step, n_steps);
     if (tile) {
-        launch_set_step(c, stream, first_step, first_step, n_steps);
-        launch_param<false, false, true>(c, stream);  // draws and tables of the first step
+#ifdef BEAN_AB_KERNELS
         if (launch_svi_tile(c, stream, first_step, n_steps)) return -1;
-        launch_finalize(c, stream, first_step, n_steps, false);
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-#else
-    (void)tile;
 #endif
-    if (async_candidate(c, n_steps) && stream != nullptr) {
+    } else if (async_candidate(c, n_steps) && stream != nullptr) {
         // one launch for the call: it also draws step first_step + n_steps, which nobody reads
-        launch_set_step(c, stream, first_step, first_step, n_steps);
-        launch_param<false, false, true>(c, stream);  // draws and tables of the first step
+        // (bean_hip_svi_resume takes this path on the null stream too: inherited, not reviewed here)
         if (launch_svi_async(c, stream, first_step, first_step, n_steps)) return -1;
-        launch_finalize(c, stream, first_step, n_steps, false);
-        HIP_OK(hipGetLastError());
-        return 0;
-    }
-    launch_set_step(c, stream, first_step, first_step, n_steps);
-    launch_param<false, false, true>(c, stream);
-    if (fused) {
+    } else if (fused) {
         // n launches of k_step_wave2 = {guide work, FINISH, PREP of the next step}; graphs hold even
-        // numbers of launches (the step counters ping-pong), an odd remainder is launched last
+        // numbers of launches (the step counters ping-pong), largest first, an odd remainder is launched last
         uint64_t left = n_steps;
         if (use_graph) {
             for (int k = (int)c->graphs_fused.size() - 1; k >= 0; --k)
@@ -1879,31 +1773,11 @@ extern "C" int bean_hip_svi_run(bean_hip_ctx* c, uint64_t seed, uint64_t first_s
         enqueue_fused(c, stream, left);
     } else {
         launch_guide(c, stream);
-        uint64_t pairs = n_steps - 1;
         if (use_graph) {
-            // smallest graphs first: the device works on them while the host submits the larger ones
-            // (a launch of the 64-pair graph costs the host more than the step or two already enqueued)
-            const int kmax = (int)c->graphs.size() - 1;
-            uint64_t big = pairs >> kmax;           // launches of the largest graph
-            uint64_t rest = pairs - (big << kmax);  // < 2^kmax: one launch per set bit, ascending
-            // (a graph launch costs ~8.5 us of idle device time at its boundary - measured on the kernel
-            // timeline of a 20-step call - so one or two pairs are launched directly: six eager launches
-            // run back to back)
-            for (int k = 0; k < kmax; ++k)
-                if (rest & (1ull << k)) {
-                    if (k < 2) enqueue_pairs(c, stream, 1ull << k);
-                    else {
-                        HIP_OK(hipGraphLaunch(c->graphs[k], stream));
-                        c->alleles_fresh = true;  // (a graph of pairs ends with a guide launch)
-                    }
-                }
-            for (uint64_t i = 0; i < big; ++i) {
-                HIP_OK(hipGraphLaunch(c->graphs[kmax], stream));
-                c->alleles_fresh = true;
-            }
-            pairs = 0;
+            if (replay_pairs(c, c->graphs, stream, n_steps - 1, pairs_n)) return -1;
+        } else {
+            enqueue_pairs(c, stream, n_steps - 1);
         }
-        enqueue_pairs(c, stream, pairs);
         launch_param<true, true, false>(c, stream);
     }
     launch_finalize(c, stream, first_step, n_steps, false);
@@ -2050,12 +1924,9 @@ static void launch_guide_ens(bean_hip_ctx* c, hipStream_t stream) {
     const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)c->n_members), block(64);
     const size_t lds = guide_wave2_lds(d.B, d.tile_targets);
     const DevArgs* mem = c->members_dev;
-    if (d.family == kMixture) {
-        if (d.flags & kAcc) hipLaunchKernelGGL((k_guide_wave2_ens<kMixture, true>), grid, block, lds, stream, mem);
-        else hipLaunchKernelGGL((k_guide_wave2_ens<kMixture, false>), grid, block, lds, stream, mem);
-    } else {
-        hipLaunchKernelGGL((k_guide_wave2_ens<kNormal, false>), grid, block, lds, stream, mem);
-    }
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_guide_wave2_ens<fam(), acc()>), grid, block, lds, stream, mem);
+    });
 }
 
 static void enqueue_pairs_ens(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
@@ -2076,15 +1947,11 @@ extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds,
         return fail("bean_hip_svi_run_ensemble: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
     // (a handle that never heard of members is an ensemble of one)
     if (!c->members_dev) HIP_OK(hipMalloc((void**)&c->members_dev, (size_t)c->n_members * sizeof(DevArgs)));
-    if (!c->prepared) return fail("bean_hip_svi_run_ensemble: call bean_hip_prepare first");
-    if (check_bound(c, false, true)) return -1;
-    const DevArgs& dd = c->d;
-    if (dd.eps_mu_in || dd.eps_sd_in || dd.pi_in || dd.eps_noise_in || dd.eps_mu_out || dd.eps_sd_out || dd.pi_out ||
-        dd.eps_noise_out)
+    // (pi_out without kDumpPi refuses here and nowhere else: inherited, not reviewed here)
+    if (per_step_noise(c->d) || c->d.pi_out)
         return fail("bean_hip_svi_run_ensemble: injected or dumped noise belongs to single fits");
-    if (n_steps == 0) return 0;
-    if (first_step + n_steps > c->loss_capacity)
-        return fail("bean_hip_svi_run_ensemble: loss_hist too small for first_step + n_steps");
+    const int go = begin_steps(c, "bean_hip_svi_run_ensemble", first_step, n_steps);
+    if (go <= 0) return go;
     hipStream_t stream = (hipStream_t)stream_;
     c->resume_ok = false;
     const int K = c->n_members;
@@ -2097,22 +1964,17 @@ extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds,
         c->members_dirty = false;
     }
     const bool use_graph = graph_chunk > 0 && stream != nullptr;
-    if (use_graph) {
-        int kmax = 0;
-        while ((2ull << kmax) <= (uint64_t)graph_chunk && kmax < 10) ++kmax;
-        if ((int)c->graphs_ens.size() != kmax + 1) {
-            for (hipGraphExec_t g : c->graphs_ens)
-                if (g) (void)hipGraphExecDestroy(g);
-            c->graphs_ens.clear();
-            for (int k = 0; k <= kmax; ++k) {
-                hipGraphExec_t ge = nullptr;
-                if (capture_pairs(c, stream, 1ull << k, &ge, false, true)) {
-                    for (hipGraphExec_t g : c->graphs_ens)
-                        if (g) (void)hipGraphExecDestroy(g);
-                    c->graphs_ens.clear();
-                    return -1;
-                }
-                c->graphs_ens.push_back(ge);
+    auto pairs_n = [&](uint64_t n) {
+        enqueue_pairs_ens(c, stream, n);
+        return 0;
+    };
+    if (use_graph) {  // the ladder of bean_hip_svi_run's pair path, of {k_param_ens, k_guide_wave2_ens} pairs
+        const int n_rungs = top_rung(graph_chunk, 1, 10) + 1;
+        if ((int)c->graphs_ens.size() != n_rungs) {
+            destroy_graphs(c->graphs_ens);
+            if (build_ladder(c, c->graphs_ens, stream, n_rungs, 1, c->alleles_fresh, pairs_n)) {
+                destroy_graphs(c->graphs_ens);
+                return -1;
             }
         }
     }
@@ -2126,20 +1988,11 @@ extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds,
     }
     launch_param_ens<false, false, true>(c, stream);
     launch_guide_ens(c, stream);
-    uint64_t pairs = n_steps - 1;
-    if (use_graph) {  // (the decomposition of bean_hip_svi_run: smallest graphs first, one or two pairs launched directly)
-        const int kmax = (int)c->graphs_ens.size() - 1;
-        const uint64_t big = pairs >> kmax;
-        const uint64_t rest = pairs - (big << kmax);
-        for (int k = 0; k < kmax; ++k)
-            if (rest & (1ull << k)) {
-                if (k < 2) enqueue_pairs_ens(c, stream, 1ull << k);
-                else HIP_OK(hipGraphLaunch(c->graphs_ens[k], stream));
-            }
-        for (uint64_t i = 0; i < big; ++i) HIP_OK(hipGraphLaunch(c->graphs_ens[kmax], stream));
-        pairs = 0;
+    if (use_graph) {
+        if (replay_pairs(c, c->graphs_ens, stream, n_steps - 1, pairs_n)) return -1;
+    } else {
+        enqueue_pairs_ens(c, stream, n_steps - 1);
     }
-    enqueue_pairs_ens(c, stream, pairs);
     launch_param_ens<true, true, false>(c, stream);
     hipLaunchKernelGGL(k_loss_finalize_ens, dim3((unsigned)((n_steps + 3) / 4), (unsigned)K), dim3(n_steps == 1 ? 64 : 256), 0,
                        stream, (const DevArgs*)c->members_dev, (unsigned long long)first_step, (unsigned long long)n_steps, 0);
@@ -2171,50 +2024,18 @@ static int launch_resume_graph(bean_hip_ctx* c, hipGraphExec_t ge, hipStream_t s
     return 0;
 }
 
-static int capture_resume_pairs(bean_hip_ctx* c, hipStream_t stream, uint64_t n, hipGraphExec_t* out) {
-    hipGraph_t graph = nullptr;
-    HIP_OK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    // the graph's first node is a guide launch: it is captured in the state a resume chain enters it with - behind a
-    // PREP launch of k_param (resume_head_state) - and a replay checks that state (launch_resume_graph)
-    const bool fresh_was = c->alleles_fresh;
-    c->alleles_fresh = c->resume_head_fresh;
-    enqueue_resume_pairs(c, stream, n);
-    c->alleles_fresh = fresh_was;
-    hipError_t e = hipStreamEndCapture(stream, &graph);
-    if (e != hipSuccess) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone) {
-            hipGraph_t junk = nullptr;
-            (void)hipStreamEndCapture(stream, &junk);
-            if (junk) (void)hipGraphDestroy(junk);
-        }
-        if (graph) (void)hipGraphDestroy(graph);
-        (void)hipGetLastError();
-        return fail(std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-    }
-    e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e != hipSuccess) {
-        *out = nullptr;
-        return fail(std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-    }
-    return 0;
-}
-
 extern "C" int bean_hip_svi_resume(bean_hip_ctx* c, uint64_t seed, uint64_t first_step, uint64_t n_steps,
                                    int32_t graph_chunk, void* stream_) {
-    if (!c) return fail("bean_hip_svi_resume: null handle");
-    if (!c->prepared) return fail("bean_hip_svi_resume: call bean_hip_prepare first");
-    const DevArgs& dd = c->d;
     // noise injected or dumped per step, a timed k_param, the opt-in steppers: the plain loop
-    if (dd.eps_mu_in || dd.eps_sd_in || dd.pi_in || dd.eps_noise_in || dd.eps_mu_out || dd.eps_sd_out || dd.eps_noise_out ||
-        dd.x0_in || dd.eps_u_in || dd.x0_out || dd.eps_u_out || (dd.flags & kDumpPi) || c->profile || c->profile_param ||
-        c->fused_step || c->tile_svi || stream_ == nullptr)
-        return bean_hip_svi_run(c, seed, first_step, n_steps, graph_chunk, stream_);
-    if (check_bound(c, false, true)) return -1;
-    if (n_steps == 0) return 0;
-    if (first_step + n_steps > c->loss_capacity)
-        return fail("bean_hip_svi_resume: loss_hist too small for first_step + n_steps");
+    // (x0_* / eps_u_* are asked about here and not in bean_hip_svi_run's own path choices: inherited, not reviewed here)
+    if (c && c->prepared) {
+        const DevArgs& dd = c->d;
+        if (per_step_noise(dd) || dd.x0_in || dd.eps_u_in || dd.x0_out || dd.eps_u_out || dumps_pi(dd) || c->profile ||
+            c->profile_param || c->fused_step || c->tile_svi || stream_ == nullptr)
+            return bean_hip_svi_run(c, seed, first_step, n_steps, graph_chunk, stream_);
+    }
+    const int go = begin_steps(c, "bean_hip_svi_resume", first_step, n_steps);
+    if (go <= 0) return go;
     hipStream_t stream = (hipStream_t)stream_;
     drop_graph_on_seed_change(c, seed);
     const bool resumed = c->resume_ok && c->resume_next == first_step && c->resume_seed == seed &&
@@ -2223,41 +2044,34 @@ extern "C" int bean_hip_svi_resume(bean_hip_ctx* c, uint64_t seed, uint64_t firs
     c->d.seed = seed;
     if (async_candidate(c, n_steps)) {
         // the whole window in one launch (bean_async_v2.hpp); windows chain exactly as the pairs do
-        if (!resumed) {
-            launch_set_step(c, stream, first_step, first_step, n_steps);
-            launch_param<false, false, true>(c, stream);  // draw and tables of the first step
-        }
+        if (!resumed) first_draw(c, stream, first_step, n_steps);
         if (launch_svi_async(c, stream, first_step, first_step, n_steps)) return -1;
         launch_finalize(c, stream, first_step, n_steps, false);
         HIP_OK(hipGetLastError());
-        c->resume_ok = true;
-        c->resume_next = first_step + n_steps;
-        c->resume_seed = seed;
-        c->resume_stream = stream_;
+        mark_resumable(c, seed, first_step + n_steps, stream_);
         return 0;
     }
     int kmax = 0;
     if (graph_chunk > 1) {
-        // graphs of 4, 8, ... <= graph_chunk pairs, all instantiated at the first call
-        while ((8ull << kmax) <= (uint64_t)graph_chunk && kmax < 8) ++kmax;
+        // graphs of 4, 8, ... <= graph_chunk {guide, k_param} pairs, each closed by its own finalize
+        kmax = top_rung(graph_chunk, 4, 8);
         if ((int)c->graphs_resume.size() != kmax + 1) {
             drop_graph(c);
+            // a graph's first node is a guide launch: it is captured in the state a resume chain enters it with - behind
+            // a PREP launch of k_param - and a replay checks that state (launch_resume_graph)
             c->resume_head_fresh = param_prep_leaves_alleles_fresh(c);
-            for (int k = 0; k <= kmax; ++k) {
-                hipGraphExec_t ge = nullptr;
-                if (capture_resume_pairs(c, stream, 4ull << k, &ge)) {
-                    drop_graph(c);
-                    return -1;
-                }
-                c->graphs_resume.push_back(ge);
+            auto resume_n = [&](uint64_t n) {
+                enqueue_resume_pairs(c, stream, n);
+                return 0;
+            };
+            if (build_ladder(c, c->graphs_resume, stream, kmax + 1, 4, c->resume_head_fresh, resume_n)) {
+                drop_graph(c);
+                return -1;
             }
             c->graph_seed = seed;
         }
     }
-    if (!resumed) {
-        launch_set_step(c, stream, first_step, first_step, n_steps);
-        launch_param<false, false, true>(c, stream);  // draw and tables of the first step
-    }
+    if (!resumed) first_draw(c, stream, first_step, n_steps);
     uint64_t left = n_steps;
     if (graph_chunk > 1 && !c->graphs_resume.empty()) {
         // one to four pairs directly - the device starts on an eager launch some 15 us sooner than on a graph
@@ -2276,17 +2090,15 @@ extern "C" int bean_hip_svi_resume(bean_hip_ctx* c, uint64_t seed, uint64_t firs
     }
     enqueue_resume_pairs(c, stream, left);
     HIP_OK(hipGetLastError());
-    // the last k_param has drawn step first_step + n_steps and filled its tables
-    c->resume_ok = true;
-    c->resume_next = first_step + n_steps;
-    c->resume_seed = seed;
-    c->resume_stream = stream_;
+    mark_resumable(c, seed, first_step + n_steps, stream_);  // (the last k_param was a PREP launch)
     return 0;
 }
 
+// ------------------------------------------------------------------ sharded / communicator
 // ---- guide-sharded stepping with exchange points (see bean_hip.h)
 extern "C" int bean_hip_sharded_begin(bean_hip_ctx* c, uint64_t seed, uint64_t first_step, uint64_t n_steps,
                                       void* stream_) {
+    // (begin_steps' checks without its early return: an empty window is checked and prepares a draw like any other)
     if (!c) return fail("bean_hip_sharded_begin: null handle");
     if (!c->prepared) return fail("bean_hip_sharded_begin: call bean_hip_prepare first");
     if (check_bound(c, false, true)) return -1;
@@ -2302,8 +2114,7 @@ extern "C" int bean_hip_sharded_begin(bean_hip_ctx* c, uint64_t seed, uint64_t f
     hipStream_t stream = (hipStream_t)stream_;
     c->d.seed = seed;
     c->resume_ok = false;
-    launch_set_step(c, stream, first_step, first_step, n_steps);
-    launch_param<false, false, true>(c, stream);
+    first_draw(c, stream, first_step, n_steps);
     c->sharded_steps = 0;
     HIP_OK(hipGetLastError());
     return 0;
@@ -2504,38 +2315,24 @@ extern "C" int bean_hip_svi_run_exchanged(bean_hip_ctx* c, uint64_t seed, uint64
     // hipGraphs of 2, 4, ... <= graph_chunk exchanged steps (never holding a run's last step, whose update
     // prepares no further draw); the remainder is enqueued directly
     if (graph_chunk > 1 && stream != nullptr && !c->profile) {
-        int kmax = 0;
-        while ((4ull << kmax) <= (uint64_t)graph_chunk && kmax < 9) ++kmax;
         if (c->graphs_xchg.empty()) {
-            for (int k = 0; k <= kmax; ++k) {
-                hipGraph_t graph = nullptr;
-                hipGraphExec_t ge = nullptr;
-                bool ok = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    // (tiling: a graph's first node is a guide launch; it is captured in the state every replay enters it
-                    // with - behind a PREP launch of k_param, bean_hip_sharded_begin's or an exchanged update's - and a
-                    // replay checks that state, as launch_resume_graph does)
-                    const bool fresh_was = c->alleles_fresh;
-                    c->resume_head_fresh = param_prep_leaves_alleles_fresh(c);
-                    c->alleles_fresh = c->resume_head_fresh;
-                    for (uint64_t i = 0; ok && i < (2ull << k); ++i) ok = enqueue_exchanged_step(c, stream, false) == 0;
-                    c->alleles_fresh = fresh_was;
-                    // the capture is ended whether or not a step failed inside it (enqueue_exchanged_step closes
-                    // its RCCL group on every path); a partial graph is destroyed below
-                    hipError_t e = hipStreamEndCapture(stream, &graph);
-                    ok = ok && e == hipSuccess && graph != nullptr;
-                }
-                if (ok) ok = hipGraphInstantiate(&ge, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (graph) (void)hipGraphDestroy(graph);
-                if (!ok) {
-                    // RCCL (or HIP) refused the capture: forget graphs, keep going eagerly
-                    (void)hipGetLastError();
-                    drop_graph(c);
-                    g_err = "bean_hip_svi_run_exchanged: the exchanged step could not be captured into a hipGraph; "
-                            "running it with eager launches";
-                    break;
-                }
-                c->graphs_xchg.push_back(ge);
+            // (tiling: a graph's first node is a guide launch; it is captured in the state every replay enters it with -
+            // behind a PREP launch of k_param, bean_hip_sharded_begin's or an exchanged update's - and a replay checks
+            // that state, as launch_resume_graph does)
+            c->resume_head_fresh = param_prep_leaves_alleles_fresh(c);
+            // the capture is ended whether or not a step failed inside it (enqueue_exchanged_step closes its RCCL
+            // group on every path, capture_graph destroys the partial graph)
+            auto steps_n = [&](uint64_t n) {
+                int rc = 0;
+                for (uint64_t i = 0; rc == 0 && i < n; ++i) rc = enqueue_exchanged_step(c, stream, false);
+                return rc;
+            };
+            if (build_ladder(c, c->graphs_xchg, stream, top_rung(graph_chunk, 2, 9) + 1, 2, c->resume_head_fresh, steps_n)) {
+                // RCCL (or HIP) refused the capture: forget graphs, keep going eagerly
+                (void)hipGetLastError();
+                drop_graph(c);
+                g_err = "bean_hip_svi_run_exchanged: the exchanged step could not be captured into a hipGraph; "
+                        "running it with eager launches";
             }
             c->graph_seed = seed;
         }
@@ -2551,6 +2348,7 @@ extern "C" int bean_hip_svi_run_exchanged(bean_hip_ctx* c, uint64_t seed, uint64
     return 0;
 }
 
+// ------------------------------------------------------------------ introspection
 extern "C" uint64_t bean_hip_step_bytes(const bean_hip_ctx* c) {
     if (!c) return 0;
     const bean_hip_shape& s = c->shape;
