@@ -467,7 +467,9 @@ __device__ __forceinline__ void adam_update(float& p, float& m, float& v, float 
     // every rounding is pinned (no implicit contraction) so that the stand-alone
     // k_adam and the fused update inside k_param produce identical bits
 #pragma clang fp contract(off)
-    const float gc = fminf(fmaxf(grad, -k.clip), k.clip);
+    // grad.clamp_(-clip, clip): a NaN gradient stays NaN (fminf / fmaxf alone would return the clip), so p, m and v
+    // become NaN, the next loss is NaN and the fit halts at its report window as the reference's does
+    const float gc = grad != grad ? grad : fminf(fmaxf(grad, -k.clip), k.clip);
     const float m9 = m * 0.9f;
     m = fmaf(gc, 0.1f, m9);            // exp_avg.mul_(b1).add_(grad, alpha=1-b1)
     const float v9 = v * 0.999f;
