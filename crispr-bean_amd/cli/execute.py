@@ -31,6 +31,18 @@ def get_parser():
                           "moves it most: columns mu_jk_se / mu_jk_max_shift / mu_jk_max_shift_rep / n_jk.  The two numeric "
                           "columns are on the scale of the column mu (the raw posterior mean), not of mu_scaled / mu_adj "
                           "that --fit-negctrl adds.  Not combined with --n-seeds > 1 or --load-existing.")
+    own.add_argument("--jackknife-guides", dest="jackknife_guides", action="store_true",
+                     help="Next to the fit of the screen, fit it once per guide position with the guide at that position "
+                          "of every target masked (same seed; in the sorting variant models one such fit holds every "
+                          "target's leave-one-guide-out fit) and report, per target, the jackknife standard error of mu "
+                          "over its guides and the guide whose removal moves it most: columns mu_gjk_se / "
+                          "mu_gjk_max_shift / mu_gjk_max_shift_guide / n_gjk, and mu_shift_left_out in the sgRNA table.  "
+                          "The numeric columns are on the scale of the column mu (the raw posterior mean); --fit-negctrl "
+                          "does not rescale them.  Variant screens only; not combined with --n-seeds > 1, "
+                          "--jackknife-replicates or --load-existing.")
+    own.add_argument("--jackknife-guides-max", dest="jackknife_guides_max", type=_positive_int, default=63,
+                     help="Targets with more guides than this take no part in --jackknife-guides (default and "
+                          "largest value 63: one member per guide position next to the full screen).")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))
@@ -46,6 +58,17 @@ def check_run_switches(parser, args):
         parser.error("--jackknife-replicates fits every member with the same seed and does not combine with --n-seeds > 1.")
     if getattr(args, "jackknife_replicates", False) and getattr(args, "load_existing", False):
         parser.error("--jackknife-replicates needs the leave-one-replicate-out fits and does not combine with --load-existing.")
+    if getattr(args, "jackknife_guides", False):
+        if int(getattr(args, "n_seeds", 1) or 1) > 1:
+            parser.error("--jackknife-guides fits every member with the same seed and does not combine with --n-seeds > 1.")
+        if getattr(args, "jackknife_replicates", False):
+            parser.error("--jackknife-guides and --jackknife-replicates are two runs: they do not combine in one.")
+        if getattr(args, "load_existing", False):
+            parser.error("--jackknife-guides needs the leave-one-guide-out fits and does not combine with --load-existing.")
+        if getattr(args, "library_design", None) == "tiling":
+            parser.error("--jackknife-guides needs targets that own their guides and does not combine with tiling.")
+        if int(getattr(args, "jackknife_guides_max", 63)) > 63:
+            parser.error("--jackknife-guides-max is at most 63.")
 
 
 def main(argv=None):

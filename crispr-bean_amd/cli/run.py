@@ -58,6 +58,21 @@ def _replicate_names(ndata):
     return names if len(names) == int(ndata.n_reps) else [str(r) for r in range(int(ndata.n_reps))]
 
 
+def check_guide_jackknife_switches(args) -> bool:
+    """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
+    if not bool(getattr(args, "jackknife_guides", False)):
+        return False
+    if int(getattr(args, "n_seeds", 1) or 1) > 1:
+        raise ValueError("--jackknife-guides fits every member with the same seed and does not combine with --n-seeds > 1.")
+    if bool(getattr(args, "jackknife_replicates", False)):
+        raise ValueError("--jackknife-guides and --jackknife-replicates are two runs: they do not combine in one.")
+    if args.load_existing:
+        raise ValueError("--jackknife-guides needs the leave-one-guide-out fits and does not combine with --load-existing.")
+    if args.library_design == "tiling":
+        raise ValueError("--jackknife-guides needs targets that own their guides and does not combine with tiling.")
+    return True
+
+
 def main(args, return_data=False):
     rank, world = (0, 1) if return_data else _init_distributed()
     if rank != 0:  # one banner / one log / one set of tables
@@ -146,8 +161,10 @@ def main(args, return_data=False):
         raise ValueError("--jackknife-replicates fits every member with the same seed and does not combine with --n-seeds > 1.")
     if jackknife and args.load_existing:
         raise ValueError("--jackknife-replicates needs the leave-one-replicate-out fits and does not combine with --load-existing.")
+    guide_jackknife = check_guide_jackknife_switches(args)
     seed_sd = None
     jk = None
+    gjk = None
     save_dict = dict()
     param_history_dict_negctrl = None
     if args.load_existing:
@@ -197,6 +214,20 @@ def main(args, return_data=False):
             save_dict.update(save_dict_model)
             save_dict["jackknife"] = [{"left_out": names[r], "params": out["params"], "loss": out["loss"]}
                                       for r, (_, out) in zip(left_out, loo)]
+        elif guide_jackknife:
+            # a guide jackknife: member 0 is the fit a run without the flag does, and the tables' columns come from it
+            from ..model.jackknife import guide_jackknife_summary
+            from ..model.run import run_inference_guide_jackknife
+
+            full, loo, positions, included = run_inference_guide_jackknife(
+                model, guide, ndata, num_steps=args.n_iter, max_positions=int(getattr(args, "jackknife_guides_max", 63)))
+            gjk = guide_jackknife_summary(full, loo, positions, included, ndata, list(guide_info_df.index))
+            param_history_dict, save_dict_model = deepcopy(full)
+            save_dict.update(save_dict_model)
+            save_dict["guide_jackknife"] = {
+                "included": included,
+                "positions": [{"position": j, "params": out["params"], "loss": out["loss"]}
+                              for j, (_, out) in zip(positions, loo)]}
         else:
             param_history_dict, save_dict_model = deepcopy(run_inference(model, guide, ndata, num_steps=args.n_iter))
             save_dict.update(save_dict_model)
@@ -223,6 +254,7 @@ def main(args, return_data=False):
         is_survival_screen=(args.selection == "survival"),
         **({"seed_sd": seed_sd, "n_seeds": n_seeds} if seed_sd is not None else {}),
         **({"jackknife": jk} if jk is not None else {}),
+        **({"guide_jackknife": gjk} if gjk is not None else {}),
     )
     info("Done!")
     return prefix

@@ -10,12 +10,20 @@ the guide side is unmasked: a masked (replicate, guide) pair still draws its ``p
 of ``q(pi)``.  A fit of the screen with the replicate absent would have no such site; the two are different models, and
 this one is the reference's.  Size factors, ``a0`` and the other derived tensors are those of the whole screen.
 
+Guide jackknife: is a hit carried by one guide (``run_inference_guide_jackknife``, ``bean run --jackknife-guides``).
+
+The same, with guides left out instead of replicates (``leave_out_guides``: the guide's column of ``repguide_mask`` is
+zero, nothing else).  In the sorting variant families without sample covariates the targets share no parameter and the
+random streams are keyed by global index, so one fit that masks position j of EVERY target gives every target t exactly
+the fit in which only guide (t, j) is masked: all G leave-one-guide-out fits are ``1 + Lmax`` members
+(``guide_positions``, ``guide_member_masks``, ``guide_jackknife_summary``).
+
 Pure torch: no GPU involved in this file.
 """
 from __future__ import annotations
 
 import copy
-from typing import Dict, List, Sequence
+from typing import Dict, List, Sequence, Tuple
 
 import torch
 
@@ -80,3 +88,108 @@ def jackknife_summary(full, loo, left_out: Sequence[int], replicate_names: Seque
     worst = shift.argmax(0)
     names = [str(replicate_names[int(left_out[int(j)])]) for j in worst.reshape(-1)]
     return {"mu_jk_se": se, "mu_jk_max_shift": shift.max(0).values, "mu_jk_max_shift_rep": names, "n_jk": n}
+
+
+# ---------------------------------------------------------------- guides
+MAX_GUIDE_POSITIONS = 63  # BEAN_HIP_MAX_MEMBERS - 1: the full screen is member 0
+
+
+def leave_out_guides(data, guides):
+    """A copy of the screen with the guides ``guides`` (indices, or one index) masked: ``repguide_mask[:, guides] =
+    False`` and nothing else touched - masked, not removed, as ``leave_out``: the guides keep their ``pi`` draws and the
+    entropy of ``q(pi)``, their counts enter no likelihood term.  ``data`` is not modified."""
+    idx = torch.as_tensor(guides, dtype=torch.int64).reshape(-1).cpu()
+    G = int(data.n_guides)
+    bad = idx[(idx < 0) | (idx >= G)]
+    if bad.numel():
+        raise ValueError(f"guide {int(bad[0])} of a screen with {G} guides")
+    out = copy.copy(data)
+    out.repguide_mask = data.repguide_mask.clone()
+    out.repguide_mask[:, idx.to(out.repguide_mask.device)] = False
+    return out
+
+
+def _guide_layout(data):
+    offsets = data.target_offsets.detach().cpu()
+    return offsets[:-1], offsets[1:] - offsets[:-1]
+
+
+def guide_positions(data, max_positions: int = MAX_GUIDE_POSITIONS) -> Tuple[List[int], torch.Tensor]:
+    """``(positions, included)`` of a guide jackknife.  ``positions`` are the j in ``[0, min(Lmax, max_positions))``,
+    Lmax the longest target; ``included`` is ``(T, len(positions))`` bool, true where target t has a guide at
+    ``target_offsets[t] + j`` that is not already masked in every replicate (leaving that one out would repeat the
+    full fit).  Targets with more than ``max_positions`` guides are left out of the jackknife entirely (their row is
+    false): a delete-one statistic over some of a target's guides would not be one.  No included pair at all, or
+    ``max_positions`` outside ``[1, 63]``, is a ``ValueError``."""
+    max_positions = int(max_positions)
+    if not 1 <= max_positions <= MAX_GUIDE_POSITIONS:
+        raise ValueError(f"a guide jackknife takes 1 to {MAX_GUIDE_POSITIONS} positions per target "
+                         f"(one member each, next to the full screen), got {max_positions}")
+    start, length = _guide_layout(data)
+    n_pos = min(int(length.max()) if length.numel() else 0, max_positions)
+    j = torch.arange(n_pos)
+    present = (j[None, :] < length[:, None]) & (length <= max_positions)[:, None]
+    alive = (data.repguide_mask.detach().cpu() != 0).any(0)
+    g = (start[:, None] + j[None, :]).clamp(max=max(int(data.n_guides) - 1, 0))
+    included = present & alive[g]
+    if not bool(included.any()):
+        raise ValueError(f"a guide jackknife needs at least one guide to leave out: no target of at most "
+                         f"{max_positions} guides has a guide that is not already fully masked")
+    return list(range(n_pos)), included
+
+
+def guides_at_position(data, j: int) -> torch.Tensor:
+    """The guide at position j of every target that has one."""
+    start, length = _guide_layout(data)
+    return (start + int(j))[length > int(j)]
+
+
+def guide_member_masks(data, positions: Sequence[int]):
+    """``(repguide (K, R, G) bool, sample_mask (K, R, B))`` of the K = 1 + len(positions) fits: member 0 has the
+    screen's own masks, member 1 + j masks the guide at position ``positions[j]`` of every target that has one;
+    ``sample_mask`` is the screen's, K times."""
+    screens = [data] + [leave_out_guides(data, guides_at_position(data, j)) for j in positions]
+    return (torch.stack([s.repguide_mask != 0 for s in screens]), torch.stack([data.sample_mask] * len(screens)))
+
+
+def guide_jackknife_summary(full, loo, positions: Sequence[int], included, data, guide_names: Sequence) -> Dict[str, object]:
+    """Delete-one-guide summary of ``mu_loc`` (float64).  ``loo[i]`` is the fit that leaves position ``positions[i]``
+    out everywhere; target t reads ITS ``mu_loc`` from it: ``m_tj``, for the included j of t, ``n_t`` their count,
+    ``mbar_t`` their mean.
+
+    * ``mu_gjk_se[t] = sqrt((n_t - 1) / n_t * sum_j (m_tj - mbar_t)^2)``;
+    * ``mu_gjk_max_shift[t] = max_j |m_tj - mu_loc_full[t]|`` and ``mu_gjk_max_shift_guide``, the name of the guide
+      whose removal moves the target that far, a list with one name per target;
+    * ``n_gjk[t] = n_t`` (int64);
+    * ``mu_shift_left_out[g] = m_tj - mu_loc_full[t]`` of guide g = (t, j), NaN for guides that were not left out.
+
+    The first three are ``(T,)``; targets with ``n_t < 2`` get NaN, the empty name, and their ``n_t``."""
+    included = torch.as_tensor(included).detach().cpu().bool()
+    T, n_pos = included.shape
+    if n_pos != len(positions) or n_pos != len(loo):
+        raise ValueError(f"guide_jackknife_summary needs one fit per position, got {len(loo)} fits, {len(positions)} "
+                         f"positions and {n_pos} columns of `included`")
+    centre = _mu_loc(full).reshape(-1)
+    if centre.numel() != T:
+        raise ValueError(f"`included` has {T} targets, mu_loc {centre.numel()}")
+    start, _ = _guide_layout(data)
+    nan = float("nan")
+    m = torch.stack([_mu_loc(r).reshape(-1) for r in loo], dim=1) if n_pos else torch.zeros(T, 0, dtype=torch.float64)
+    n = included.sum(1)
+    enough = n >= 2
+    nf = n.clamp(min=1).to(torch.float64)
+    zero = torch.zeros((), dtype=torch.float64)
+    mbar = torch.where(included, m, zero).sum(1) / nf
+    ss = torch.where(included, (m - mbar[:, None]) ** 2, zero).sum(1)
+    shift = m - centre[:, None]
+    size = torch.where(included, shift.abs(), torch.full((), -1.0, dtype=torch.float64))
+    worst = size.argmax(1) if n_pos else torch.zeros(T, dtype=torch.int64)
+    se = torch.where(enough, torch.sqrt((nf - 1) / nf * ss), torch.full((), nan, dtype=torch.float64))
+    far = torch.where(enough, size.max(1).values if n_pos else torch.zeros(T, dtype=torch.float64),
+                      torch.full((), nan, dtype=torch.float64))
+    names = [str(guide_names[int(start[t]) + int(positions[int(worst[t])])]) if bool(enough[t]) else "" for t in range(T)]
+    per_guide = torch.full((int(data.n_guides),), nan, dtype=torch.float64)
+    t_idx, i_idx = torch.nonzero(included, as_tuple=True)
+    per_guide[start[t_idx] + torch.as_tensor(list(positions), dtype=torch.int64)[i_idx]] = shift[t_idx, i_idx]
+    return {"mu_gjk_se": se, "mu_gjk_max_shift": far, "mu_gjk_max_shift_guide": names, "n_gjk": n.to(torch.int64),
+            "mu_shift_left_out": per_guide}

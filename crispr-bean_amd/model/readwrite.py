@@ -168,6 +168,7 @@ def write_result_table(
     seed_sd=None,
     n_seeds: Optional[int] = None,
     jackknife: Optional[dict] = None,
+    guide_jackknife: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -181,7 +182,13 @@ def write_result_table(
     columns ``mu_jk_se``, ``mu_jk_max_shift``, ``mu_jk_max_shift_rep`` and ``n_jk``; every other column and the sgRNA
     table are those of the run without it.  ``mu_jk_se`` and ``mu_jk_max_shift`` are statistics of the fits' ``mu_loc``,
     i.e. on the scale of the column ``mu``: with ``negctrl_params`` (``--fit-negctrl``) they are NOT rescaled with
-    ``mu_scaled`` (divide by the control fit's sd to compare), nor stretched like ``mu_sd_adj``."""
+    ``mu_scaled`` (divide by the control fit's sd to compare), nor stretched like ``mu_sd_adj``.
+
+    ``guide_jackknife`` (a guide jackknife, ``model/jackknife.py::guide_jackknife_summary``): the element table gets
+    exactly the columns ``mu_gjk_se``, ``mu_gjk_max_shift``, ``mu_gjk_max_shift_guide`` and ``n_gjk``, the sgRNA table
+    the column ``mu_shift_left_out``; every other column of both is that of the run without it, and with ``None`` both
+    tables are byte for byte what they were.  As the replicate columns, the numeric ones are on the scale of ``mu`` and
+    are not rescaled with ``negctrl_params``."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -203,6 +210,19 @@ def write_result_table(
         element["mu_jk_max_shift"] = shift
         element["mu_jk_max_shift_rep"] = reps
         element["n_jk"] = int(jackknife["n_jk"])
+    if guide_jackknife is not None:
+        flat = lambda v: np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)  # noqa: E731
+        gj = guide_jackknife
+        se, shift, names = flat(gj["mu_gjk_se"]), flat(gj["mu_gjk_max_shift"]), list(gj["mu_gjk_max_shift_guide"])
+        count, per_guide = flat(gj["n_gjk"]).astype(np.int64), flat(gj["mu_shift_left_out"])
+        if not len(se) == len(shift) == len(names) == len(count) == len(element):
+            raise ValueError(f"the guide jackknife summary has {len(se)} entries for {len(element)} targets")
+        if len(per_guide) != len(guide_info_df):
+            raise ValueError(f"the guide jackknife summary has {len(per_guide)} entries for {len(guide_info_df)} guides")
+        element["mu_gjk_se"] = se
+        element["mu_gjk_max_shift"] = shift
+        element["mu_gjk_max_shift_guide"] = names
+        element["n_gjk"] = count
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always
@@ -212,6 +232,8 @@ def write_result_table(
     else:
         element = _ranked(add_credible_interval(element, "mu", "mu_sd"), "mu_z")
     _guide_editing_columns(guide_info_df, param_hist_dict, guide_acc)
+    if guide_jackknife is not None:
+        guide_info_df["mu_shift_left_out"] = per_guide
     guide_info_df.to_csv(f"{prefix}bean_sgRNA_result.{model_label}{suffix}.csv")
     if return_result:
         return element

@@ -317,6 +317,60 @@ def run_inference_jackknife(model, guide, data, seed: int = SEED, initial_lr=0.0
     return results[0], results[1:], left_out
 
 
+def run_inference_guide_jackknife(model, guide, data, seed: int = SEED, initial_lr=0.01, gamma=0.1, num_steps=2000,
+                                  report_every: int = 100, verbose: bool = True, max_positions: int = 63):
+    """Guide jackknife: the fit of the screen and, for every position j a target's guides can have, one fit with the
+    guide at position j of EVERY target masked (``model/jackknife.py``), all with the same ``seed`` - common random
+    numbers.
+
+    Returns ``(full, loo, positions, included)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns,
+    ``loo[i]`` exactly what it returns for ``leave_out_guides(data, <the guides at positions[i]>)`` - bit for bit -
+    and ``positions`` / ``included`` are those of ``guide_positions(data, max_positions)`` (no included pair:
+    ``ValueError``; targets with more than ``max_positions`` guides take no part, their number is logged).
+
+    In the sorting variant families the batched kernels take (``Normal`` without sample covariates, ``MixtureNormal``
+    in all its options) the targets share no parameter and the streams are keyed by global index: target t's slice of
+    ``loo[i]`` is, bit for bit, its slice of the fit with only guide (t, positions[i]) masked, and a target without a
+    guide at that position keeps the full fit's bits.  There the 1 + len(positions) fits are members of one engine
+    that differ in ``repguide_mask`` only and are stepped by the same launches, in report windows
+    (``bean_hip_ensemble_supported``).  Everywhere else the masks are fitted one after the other through
+    ``run_inference``, with the same return value - but survival variant screens couple their targets through ``q0``
+    and sorting ``Normal`` with sample covariates through ``mu_cov``: a member is then "position j left out
+    everywhere", NOT a set of single-guide fits.  Tiling families are refused (an edit's guides are not a target's
+    guides), as are several ranks.  A non-finite loss of any member halts the fit at the end of its report window with
+    the ``ValueError`` of ``run_inference``; message and dump file (``tmp_result.full.pkl`` /
+    ``tmp_result.without_guide_position<j>.pkl``, with ``"left_out_position": j``) name the position."""
+    from .jackknife import guides_at_position, guide_member_masks, guide_positions, leave_out_guides
+
+    spec = _resolve(model)
+    if spec.family == "MultiMixtureNormal" or getattr(data, "library_design", "variant") == "tiling":
+        raise ValueError("a guide jackknife needs targets that own their guides: not defined for tiling screens "
+                         "(an edit's guides are not a target's guides)")
+    _single_rank_only("run_inference_guide_jackknife")
+    positions, included = guide_positions(data, max_positions)
+    n_long = int((data.target_lengths.detach().cpu() > int(max_positions)).sum())
+    if n_long:
+        info(f"Guide jackknife: {n_long} target(s) with more than {int(max_positions)} guides take no part.")
+    seed = int(seed)
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+    what = ["the full screen"] + [f"guides at position {j} of their targets left out" for j in positions]
+    results = _fit_members(model, guide, data, [seed] * (1 + len(positions)), what=what,
+                           tag=["full"] + [f"without_guide_position{j}" for j in positions],
+                           dump_extra=[{"left_out_position": j, "seed": seed} for j in [None] + list(positions)],
+                           common=common, report_every=report_every, verbose=verbose,
+                           member_masks=guide_member_masks(data, positions))
+    if results is None:  # one after the other
+        results = []
+        for label, d in zip(what, [data] + [leave_out_guides(data, guides_at_position(data, j)) for j in positions]):
+            try:
+                results.append(run_inference(model, guide, d, seed=seed, report_every=report_every, verbose=verbose, **common))
+            except ValueError as exc:
+                if "Fitting halted" not in str(exc):
+                    raise
+                raise ValueError(f"{exc} ({label})") from exc
+    return results[0], results[1:], positions, included
+
+
 def identify_model_guide(args):
     """Model label and (model, guide) descriptors for the parsed ``bean run``
     arguments (``bean/model/run.py:399-457``), including the reference's
