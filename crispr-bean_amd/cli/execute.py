@@ -43,6 +43,16 @@ def get_parser():
     own.add_argument("--jackknife-guides-max", dest="jackknife_guides_max", type=_positive_int, default=63,
                      help="Targets with more guides than this take no part in --jackknife-guides (default and "
                           "largest value 63: one member per guide position next to the full screen).")
+    own.add_argument("--jackknife-samples", dest="jackknife_samples", action="store_true",
+                     help="Next to the fit of the screen, fit it once per sorted sample (one condition of one replicate) "
+                          "with that sample masked as --sample-mask-col masks it (same seed) and report, per target, how "
+                          "far the removal of one sample moves mu and which sample does: columns mu_sjk_max_shift / "
+                          "mu_sjk_max_shift_sample / n_sjk, on the scale of the column mu; and, per sample, its influence "
+                          "over all targets in bean_sample_influence.<model>.csv.  No standard error is reported: samples "
+                          "of different bins are not exchangeable.  Not combined with --jackknife-conditions, "
+                          "--jackknife-replicates, --jackknife-guides, --n-seeds > 1 or --load-existing.")
+    own.add_argument("--jackknife-conditions", dest="jackknife_conditions", action="store_true",
+                     help="As --jackknife-samples, leaving out one condition (that bin of every replicate) per fit.")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))
@@ -69,6 +79,21 @@ def check_run_switches(parser, args):
             parser.error("--jackknife-guides needs targets that own their guides and does not combine with tiling.")
         if int(getattr(args, "jackknife_guides_max", 63)) > 63:
             parser.error("--jackknife-guides-max is at most 63.")
+
+
+    for flag, attr in (("--jackknife-samples", "jackknife_samples"), ("--jackknife-conditions", "jackknife_conditions")):
+        if not getattr(args, attr, False):
+            continue
+        if getattr(args, "jackknife_samples", False) and getattr(args, "jackknife_conditions", False):
+            parser.error("--jackknife-samples and --jackknife-conditions are two runs: they do not combine in one.")
+        if getattr(args, "jackknife_replicates", False):
+            parser.error(f"{flag} and --jackknife-replicates are two runs: they do not combine in one.")
+        if getattr(args, "jackknife_guides", False):
+            parser.error(f"{flag} and --jackknife-guides are two runs: they do not combine in one.")
+        if int(getattr(args, "n_seeds", 1) or 1) > 1:
+            parser.error(f"{flag} fits every member with the same seed and does not combine with --n-seeds > 1.")
+        if getattr(args, "load_existing", False):
+            parser.error(f"{flag} needs the leave-one-out fits and does not combine with --load-existing.")
 
 
 def main(argv=None):

@@ -73,6 +73,44 @@ def check_guide_jackknife_switches(args) -> bool:
     return True
 
 
+def check_sample_jackknife_switches(args):
+    """``"sample"`` / ``"condition"`` if --jackknife-samples / --jackknife-conditions is set, else None; the
+    combinations they are refused with raise (the parser refuses them first)."""
+    by_sample = bool(getattr(args, "jackknife_samples", False))
+    by_condition = bool(getattr(args, "jackknife_conditions", False))
+    if not (by_sample or by_condition):
+        return None
+    if by_sample and by_condition:
+        raise ValueError("--jackknife-samples and --jackknife-conditions are two runs: they do not combine in one.")
+    flag = "--jackknife-samples" if by_sample else "--jackknife-conditions"
+    if bool(getattr(args, "jackknife_replicates", False)):
+        raise ValueError(f"{flag} and --jackknife-replicates are two runs: they do not combine in one.")
+    if bool(getattr(args, "jackknife_guides", False)):
+        raise ValueError(f"{flag} and --jackknife-guides are two runs: they do not combine in one.")
+    if int(getattr(args, "n_seeds", 1) or 1) > 1:
+        raise ValueError(f"{flag} fits every member with the same seed and does not combine with --n-seeds > 1.")
+    if args.load_existing:
+        raise ValueError(f"{flag} needs the leave-one-out fits and does not combine with --load-existing.")
+    return "sample" if by_sample else "condition"
+
+
+def _sample_group_names(ndata, groups, fallback, by, condition_column):
+    """Names of a sample jackknife's groups: the sample table row the tensor builder put at (r, b) - the samples are
+    sorted by replicate, then condition - or the condition's label; ``fallback`` (``r{r}_c{b}`` / ``c{b}``) where the
+    screen's sample table does not have that layout."""
+    samples = getattr(getattr(ndata, "screen", None), "samples", None)
+    R, B = int(ndata.n_reps), int(ndata.n_condits)
+    if samples is None or len(samples) != R * B:
+        return list(fallback)
+    if by == "sample":
+        names = [str(samples.index[g[0][0] * B + g[0][1]]) for g in groups]
+    elif condition_column in samples.columns:
+        names = [str(samples[condition_column].iloc[g[0][1]]) for g in groups]
+    else:
+        return list(fallback)
+    return names if len(set(names)) == len(names) else list(fallback)
+
+
 def main(args, return_data=False):
     rank, world = (0, 1) if return_data else _init_distributed()
     if rank != 0:  # one banner / one log / one set of tables
@@ -162,6 +200,8 @@ def main(args, return_data=False):
     if jackknife and args.load_existing:
         raise ValueError("--jackknife-replicates needs the leave-one-replicate-out fits and does not combine with --load-existing.")
     guide_jackknife = check_guide_jackknife_switches(args)
+    sample_jackknife = check_sample_jackknife_switches(args)
+    sjk = None
     seed_sd = None
     jk = None
     gjk = None
@@ -228,6 +268,20 @@ def main(args, return_data=False):
                 "included": included,
                 "positions": [{"position": j, "params": out["params"], "loss": out["loss"]}
                               for j, (_, out) in zip(positions, loo)]}
+        elif sample_jackknife:
+            # a sample jackknife: member 0 is the fit a run without the flag does, and the tables' columns come from it
+            from ..model.jackknife import sample_jackknife_summary
+            from ..model.run import run_inference_sample_jackknife
+
+            full, loo, groups, fallback = run_inference_sample_jackknife(model, guide, ndata, by=sample_jackknife,
+                                                                         num_steps=args.n_iter)
+            names = _sample_group_names(ndata, groups, fallback, sample_jackknife, args.condition_col)
+            sjk = sample_jackknife_summary(full, loo, groups, names)
+            param_history_dict, save_dict_model = deepcopy(full)
+            save_dict.update(save_dict_model)
+            save_dict["sample_jackknife"] = [
+                {"left_out": name, "pairs": [list(p) for p in g], "params": out["params"], "loss": out["loss"]}
+                for name, g, (_, out) in zip(names, groups, loo)]
         else:
             param_history_dict, save_dict_model = deepcopy(run_inference(model, guide, ndata, num_steps=args.n_iter))
             save_dict.update(save_dict_model)
@@ -255,6 +309,7 @@ def main(args, return_data=False):
         **({"seed_sd": seed_sd, "n_seeds": n_seeds} if seed_sd is not None else {}),
         **({"jackknife": jk} if jk is not None else {}),
         **({"guide_jackknife": gjk} if gjk is not None else {}),
+        **({"sample_jackknife": sjk} if sjk is not None else {}),
     )
     info("Done!")
     return prefix

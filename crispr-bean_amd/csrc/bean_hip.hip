@@ -128,6 +128,10 @@ struct bean_hip_ctx {
     bool members_set;          // bean_hip_set_members has been called
     const uint8_t* member_rg;
     const double* member_smask;
+    // per-member counts (bean_hip_bind_member_counts): (K, R, B, G) float32 of the caller, member-major; null: every
+    // member reads the shared BEAN_BUF_X / BEAN_BUF_X_BC
+    const float* member_x;
+    const float* member_xbc;
 };
 
 extern "C" const char* bean_hip_version(void) {
@@ -431,6 +435,8 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
     c->members_set = false;
     c->member_rg = nullptr;
     c->member_smask = nullptr;
+    c->member_x = nullptr;
+    c->member_xbc = nullptr;
     c->loss_acc = nullptr;
     c->profile = false;
     c->profile_param = false;
@@ -984,9 +990,10 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         HIP_OK(hipStreamSynchronize(stream));
         drop_graph(c);
     }
-    if (c->member_rg) {
-        // per-member masks: the constant, the kPNrg row and nobs depend on `rg`, so k_prepare's body runs again, once
-        // per member, on the member's masks and into its own workspace copy (member 0's is the workspace itself)
+    if (c->member_rg || c->member_x) {
+        // per-member masks or counts: the constant, the kPNrg row and nobs depend on `rg` and on the counts (the constant
+        // holds their log-factorials), so k_prepare's body runs again, once per member, on the member's masks and counts
+        // and into its own workspace copy (member 0's is the workspace itself)
         // (the array is uploaded with the seeds known so far - zeros before the first run - and is then current: a
         // bean_hip_svi_run_ensemble with those seeds does not upload it again)
         const int K = c->n_members;
@@ -1821,14 +1828,16 @@ extern "C" int bean_hip_set_members(bean_hip_ctx* c, int32_t n_members) {
     c->members_set = true;
     c->member_rg = nullptr;  // (sized for another K)
     c->member_smask = nullptr;
+    c->member_x = nullptr;
+    c->member_xbc = nullptr;
     c->member_seeds.clear();
     c->prepared = false;
     drop_graph(c);
     return 0;
 }
 
-// DevArgs of member k: c->d with everything a step writes moved to the member's own part, and the two masks at the
-// member's slice when per-member masks are bound
+// DevArgs of member k: c->d with everything a step writes moved to the member's own part, the two masks at the
+// member's slice when per-member masks are bound, and the counts at the member's slice when per-member counts are bound
 static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
     DevArgs m = c->d;
     m.seed = seed;
@@ -1836,6 +1845,11 @@ static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
     if (c->member_rg) {  // per-member masks (bean_hip_bind_member_masks); member 0 reads its slice too
         m.rg = c->member_rg + (size_t)k * (size_t)c->d.R * (size_t)c->d.G;
         m.smask = c->member_smask + (size_t)k * (size_t)c->d.R * (size_t)c->d.B;
+    }
+    if (c->member_x) {  // per-member counts (bean_hip_bind_member_counts); member 0 reads its slice too
+        const size_t n = (size_t)k * (size_t)c->d.R * (size_t)c->d.B * (size_t)c->d.G;
+        m.X = c->member_x + n;
+        if (c->member_xbc) m.Xbc = c->member_xbc + n;
     }
     if (k == 0) return m;
     const char* w0 = (const char*)c->workspace;
@@ -1899,6 +1913,37 @@ extern "C" int bean_hip_bind_member_masks(bean_hip_ctx* c, const void* repguide,
     c->member_smask = (const double*)sample_mask;
     drop_graph(c);        // (members_dev is older than the masks now)
     c->prepared = false;  // the data-only constants are stale: bean_hip_prepare comes next
+    return 0;
+}
+
+extern "C" int bean_hip_bind_member_counts(bean_hip_ctx* c, const void* x, uint64_t x_bytes, const void* x_bcmatch,
+                                           uint64_t x_bcmatch_bytes) {
+    if (!c) return fail("bean_hip_bind_member_counts: null handle");
+    if (!ensemble_shape_ok(c))
+        return fail("bean_hip_bind_member_counts: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
+    if (!c->members_set) return fail("bean_hip_bind_member_counts: call bean_hip_set_members first");
+    if (!x && x_bcmatch) return fail("bean_hip_bind_member_counts: x_bcmatch without x (both null returns to shared counts)");
+    if (x) {
+        const bool use_bc = (c->shape.flags & BEAN_FLAG_USE_BCMATCH) != 0;
+        if (use_bc && !x_bcmatch)
+            return fail("bean_hip_bind_member_counts: this handle uses the barcode-matched counts (BEAN_FLAG_USE_BCMATCH): "
+                        "x_bcmatch is required");
+        if (!use_bc && x_bcmatch)
+            return fail("bean_hip_bind_member_counts: this handle does not use the barcode-matched counts "
+                        "(BEAN_FLAG_USE_BCMATCH): x_bcmatch must be null");
+        const uint64_t K = (uint64_t)c->n_members;
+        const uint64_t want = K * (uint64_t)c->d.R * (uint64_t)c->d.B * (uint64_t)c->d.G * sizeof(float);
+        if (x_bytes != want)
+            return fail("bean_hip_bind_member_counts: x expects " + std::to_string(want) + " bytes (" + std::to_string(K) +
+                        " member(s)), got " + std::to_string(x_bytes));
+        if (x_bcmatch && x_bcmatch_bytes != want)
+            return fail("bean_hip_bind_member_counts: x_bcmatch expects " + std::to_string(want) + " bytes (" +
+                        std::to_string(K) + " member(s)), got " + std::to_string(x_bcmatch_bytes));
+    }
+    c->member_x = (const float*)x;
+    c->member_xbc = (const float*)x_bcmatch;
+    drop_graph(c);        // (members_dev is older than the counts now)
+    c->prepared = false;  // the loss constant holds the counts' log-factorials: bean_hip_prepare comes next
     return 0;
 }
 

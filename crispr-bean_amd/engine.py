@@ -71,6 +71,7 @@ class HipSVI:
         guide_ids: Optional[torch.Tensor] = None,
         n_members: int = 1,
         member_masks=None,
+        member_counts=None,
     ):
         if family not in _lib.FAMILY:
             raise ValueError(f"unknown model family {family!r}")
@@ -88,6 +89,28 @@ class HipSVI:
             if tuple(m_rg.shape) != want_rg or tuple(m_sm.shape) != want_sm:
                 raise ValueError(f"member_masks: repguide {tuple(m_rg.shape)} / sample_mask {tuple(m_sm.shape)} for "
                                  f"{int(n_members)} members, expected {want_rg} / {want_sm}")
+        if member_counts is not None:
+            # per-member counts (bean_hip_bind_member_counts): checked before the library is touched
+            if int(n_members) == 1:
+                raise ValueError("member_counts belongs to an ensemble: n_members > 1")
+            try:
+                m_x, m_xbc = member_counts
+            except (TypeError, ValueError):
+                raise ValueError("member_counts is a pair (X (K, R, B, G) float32, X_bcmatch (K, R, B, G) float32 or None)") from None
+            want_x = (int(n_members), data.n_reps, data.n_condits, data.n_guides)
+            needs_bc = bool(use_bcmatch) and getattr(data, "X_bcmatch_masked", None) is not None
+            if (m_xbc is not None) != needs_bc:
+                raise ValueError("member_counts: X_bcmatch goes with a fit that uses the barcode-matched counts "
+                                 f"(this one {'does' if needs_bc else 'does not'}), got "
+                                 f"{'None' if m_xbc is None else 'an array'}")
+            for name, t in (("X", m_x), ("X_bcmatch", m_xbc)):
+                if t is None:
+                    continue
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                    raise ValueError(f"member_counts: {name} must be a float32 tensor, got "
+                                     f"{t.dtype if isinstance(t, torch.Tensor) else type(t).__name__}")
+                if tuple(t.shape) != want_x:
+                    raise ValueError(f"member_counts: {name} {tuple(t.shape)} for {int(n_members)} members, expected {want_x}")
         survival = getattr(data, "selection", "sorting") == "survival"
         surv_normal = survival and family == "Normal"
         self.surv_normal = surv_normal
@@ -424,6 +447,16 @@ class HipSVI:
             self._check(self.lib.bean_hip_bind_member_masks(
                 self._h, ctypes.c_void_p(rg_k.data_ptr()), rg_k.numel(), ctypes.c_void_p(sm_k.data_ptr()),
                 sm_k.numel() * 8), "bind_member_masks")
+        self.member_counts = member_counts is not None
+        if member_counts is not None:
+            # member k reads its (R, B, G) slice where a single fit reads X / X_BC
+            x_k = f32(m_x)
+            xbc_k = None if m_xbc is None else f32(m_xbc)
+            self._keep["MEMBER_X"], self._keep["MEMBER_X_BC"] = x_k, xbc_k
+            self._check(self.lib.bean_hip_bind_member_counts(
+                self._h, ctypes.c_void_p(x_k.data_ptr()), x_k.numel() * 4,
+                None if xbc_k is None else ctypes.c_void_p(xbc_k.data_ptr()), 0 if xbc_k is None else xbc_k.numel() * 4),
+                "bind_member_counts")
         with self._on_stream():
             self._check(self.lib.bean_hip_prepare(self._h, self._sptr()), "prepare")
 

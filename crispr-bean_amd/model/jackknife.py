@@ -18,6 +18,15 @@ random streams are keyed by global index, so one fit that masks position j of EV
 the fit in which only guide (t, j) is masked: all G leave-one-guide-out fits are ``1 + Lmax`` members
 (``guide_positions``, ``guide_member_masks``, ``guide_jackknife_summary``).
 
+Sample jackknife: which single sorted sample carries or distorts a hit (``run_inference_sample_jackknife``, ``bean run
+--jackknife-samples`` / ``--jackknife-conditions``).
+
+A sample is one condition (bin) of one replicate.  ``leave_out_samples`` masks it the way the reference does through
+``--sample-mask-col``: its entry of ``sample_mask`` is zero AND its counts are zero (the reference fits ``X * sample_mask``).
+The counts matter: the (replicate, guide) site of a masked sample stays on, and the likelihood sums the counts of every
+bin whatever the sample mask says, so the members of such a jackknife differ in their data, not in their masks alone
+(``sample_member_masks``, ``sample_member_counts``, ``sample_jackknife_summary``).
+
 Pure torch: no GPU involved in this file.
 """
 from __future__ import annotations
@@ -193,3 +202,131 @@ def guide_jackknife_summary(full, loo, positions: Sequence[int], included, data,
     per_guide[start[t_idx] + torch.as_tensor(list(positions), dtype=torch.int64)[i_idx]] = shift[t_idx, i_idx]
     return {"mu_gjk_se": se, "mu_gjk_max_shift": far, "mu_gjk_max_shift_guide": names, "n_gjk": n.to(torch.int64),
             "mu_shift_left_out": per_guide}
+
+
+# ---------------------------------------------------------------- samples
+def leave_out_samples(data, pairs):
+    """A copy of the screen with the samples ``pairs`` - ``(replicate, condition)`` index pairs - masked: for every
+    ``(r, b)``, ``sample_mask[r, b] = 0``, ``X_masked[r, b, :] = 0`` and, where the screen has it,
+    ``X_bcmatch_masked[r, b, :] = 0``; nothing else is touched.  This is the screen the reference fits with those samples
+    masked through ``--sample-mask-col`` (``X_masked = X * sample_mask``), except that size factors, ``a0`` and the other
+    derived tensors stay the whole screen's - as ``leave_out`` rules for replicates, and for the same reason: the fits
+    are to differ through the left-out data alone.  Works on every data class (sorting, survival, tiling); ``data`` is
+    not modified.  An index out of range is a ``ValueError``."""
+    R, B = int(data.n_reps), int(data.n_condits)
+    clean = []
+    for pair in pairs:
+        try:
+            r, b = pair
+            r, b = int(r), int(b)
+        except (TypeError, ValueError):
+            raise ValueError(f"a sample is a (replicate, condition) pair, got {pair!r}") from None
+        if not (0 <= r < R and 0 <= b < B):
+            raise ValueError(f"sample ({r}, {b}) of a screen with {R} replicates x {B} conditions")
+        clean.append((r, b))
+    out = copy.copy(data)
+    out.sample_mask = data.sample_mask.clone()
+    out.X_masked = data.X_masked.clone()
+    has_bc = getattr(data, "X_bcmatch_masked", None) is not None
+    if has_bc:
+        out.X_bcmatch_masked = data.X_bcmatch_masked.clone()
+    for r, b in clean:
+        out.sample_mask[r, b] = 0
+        out.X_masked[r, b, :] = 0
+        if has_bc:
+            out.X_bcmatch_masked[r, b, :] = 0
+    return out
+
+
+def sample_groups(data, by: str = "sample") -> Tuple[List[List[Tuple[int, int]]], List[str]]:
+    """``(groups, names)`` of a sample jackknife: ``groups[j]`` is the list of ``(r, b)`` pairs member 1 + j leaves out,
+    ``names[j]`` its fallback name.
+
+    * ``by="sample"``: one group per ``(r, b)`` with ``sample_mask[r, b] != 0`` whose replicate is not already fully
+      masked in ``repguide_mask`` (leaving such a sample out would repeat the full fit); named ``r{r}_c{b}``.
+    * ``by="condition"``: one group per condition b, holding its candidate ``(r, b)`` over all replicates (a condition
+      without any is no group); named ``c{b}``.
+
+    The candidates are the cells of ``sample_mask``, i.e. the conditions on the screen's condition axis.  The separate
+    control / bulk tensors (``control_sample_mask``, ``X_control``, ``allele_counts_control``) are not candidates and are
+    never touched: they feed ``pi_a0`` and the edit-rate site, not a bin of the sort.  Fewer than two groups is a
+    ``ValueError``."""
+    if by not in ("sample", "condition"):
+        raise ValueError(f"sample_groups: by must be 'sample' or 'condition', got {by!r}")
+    sm = data.sample_mask.detach().cpu() != 0
+    alive = (data.repguide_mask.detach().cpu() != 0).any(1)
+    R, B = int(data.n_reps), int(data.n_condits)
+    cand = [(r, b) for r in range(R) for b in range(B) if bool(sm[r, b]) and bool(alive[r])]
+    if by == "sample":
+        groups = [[p] for p in cand]
+        names = [f"r{r}_c{b}" for r, b in cand]
+    else:
+        groups = [[p for p in cand if p[1] == b] for b in range(B)]
+        names = [f"c{b}" for b in range(B) if groups[b]]
+        groups = [g for g in groups if g]
+    if len(groups) < 2:
+        raise ValueError(f"a sample jackknife needs at least two {by}s that are not already masked, found {len(groups)}")
+    return groups, names
+
+
+def sample_member_masks(data, groups):
+    """``(repguide (K, R, G) bool, sample_mask (K, R, B))`` of the K = 1 + len(groups) fits: member 0 has the screen's
+    own masks, member 1 + j those of ``leave_out_samples(data, groups[j])`` (``repguide`` is the screen's, K times)."""
+    screens = [data] + [leave_out_samples(data, g) for g in groups]
+    return (torch.stack([data.repguide_mask != 0] * len(screens)), torch.stack([s.sample_mask for s in screens]))
+
+
+def sample_member_counts(data, groups):
+    """``(X (K, R, B, G), X_bcmatch (K, R, B, G) or None)`` of the K = 1 + len(groups) fits, float32: member 0 has the
+    screen's own ``X_masked`` / ``X_bcmatch_masked``, member 1 + j those of ``leave_out_samples(data, groups[j])``."""
+    screens = [data] + [leave_out_samples(data, g) for g in groups]
+    x = torch.stack([s.X_masked.to(torch.float32) for s in screens])
+    if getattr(data, "X_bcmatch_masked", None) is None:
+        return x, None
+    return x, torch.stack([s.X_bcmatch_masked.to(torch.float32) for s in screens])
+
+
+def _param(result, name) -> torch.Tensor:
+    store = result[0] if isinstance(result, (tuple, list)) else result
+    return store[name].detach().cpu().to(torch.float64)
+
+
+def sample_jackknife_summary(full, loo, groups, names: Sequence) -> Dict[str, object]:
+    """Leave-one-sample-out summary of ``mu_loc`` (float64).  With ``m_j`` the ``mu_loc`` of ``loo[j]``, ``c`` the full
+    fit's ``mu_loc`` and ``s`` its ``mu_scale``:
+
+    per target
+      * ``mu_sjk_max_shift = max_j |m_j - c|`` and ``mu_sjk_max_shift_sample``, the name of the group whose removal moves
+        the target that far (ties: the first such group), a list with one name per target;
+      * ``n_sjk = len(loo)``;
+
+    per group - ``influence``, a dict of lists in the order of ``groups`` (the influence table)
+      * ``left_out`` (the name), ``n_samples`` (pairs in the group),
+      * ``influence_median = median_t |m_j - c| / s`` and ``influence_max`` (the median of an even number of targets is
+        the mean of the two middle ones),
+      * ``n_targets_moved = #{t : |m_j - c| > s}``.
+
+    There is NO jackknife standard error here, on purpose: the samples of different bins are not exchangeable units (a
+    top bin and a bottom bin carry opposite information about ``mu``), so a delete-one variance over them would be a
+    number that looks like a standard error and is none."""
+    n = len(loo)
+    if n < 2 or n != len(groups) or n != len(names):
+        raise ValueError(f"sample_jackknife_summary needs at least two leave-one-out fits with their groups and names, "
+                         f"got {n} / {len(groups)} / {len(names)}")
+    m = torch.stack([_mu_loc(r).reshape(-1) for r in loo])
+    centre = _mu_loc(full).reshape(-1)
+    scale = _param(full, "mu_scale").reshape(-1)
+    shift = (m - centre).abs()
+    far, worst = shift.max(0)
+    # (torch.max leaves the index among ties open: the first group that reaches the maximum)
+    worst = (shift == far).to(torch.int64).argmax(0)
+    rel = shift / scale
+    influence = {
+        "left_out": [str(x) for x in names],
+        "n_samples": [len(g) for g in groups],
+        "influence_median": [float(torch.quantile(rel[j], 0.5)) for j in range(n)],
+        "influence_max": [float(rel[j].max()) for j in range(n)],
+        "n_targets_moved": [int((shift[j] > scale).sum()) for j in range(n)],
+    }
+    return {"mu_sjk_max_shift": far, "mu_sjk_max_shift_sample": [str(names[int(j)]) for j in worst], "n_sjk": n,
+            "influence": influence}

@@ -169,6 +169,7 @@ def write_result_table(
     n_seeds: Optional[int] = None,
     jackknife: Optional[dict] = None,
     guide_jackknife: Optional[dict] = None,
+    sample_jackknife: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -188,7 +189,13 @@ def write_result_table(
     exactly the columns ``mu_gjk_se``, ``mu_gjk_max_shift``, ``mu_gjk_max_shift_guide`` and ``n_gjk``, the sgRNA table
     the column ``mu_shift_left_out``; every other column of both is that of the run without it, and with ``None`` both
     tables are byte for byte what they were.  As the replicate columns, the numeric ones are on the scale of ``mu`` and
-    are not rescaled with ``negctrl_params``."""
+    are not rescaled with ``negctrl_params``.
+
+    ``sample_jackknife`` (a sample jackknife, ``model/jackknife.py::sample_jackknife_summary``): the element table gets
+    exactly the columns ``mu_sjk_max_shift``, ``mu_sjk_max_shift_sample`` and ``n_sjk`` (on the scale of ``mu``, not
+    rescaled), and the summary's influence table - one row per left-out sample or condition - is written next to the
+    element table as ``bean_sample_influence.<model_label><suffix>.csv``, also with ``return_result``.  With ``None``
+    both tables are byte for byte what they were and no third one is written."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -223,6 +230,14 @@ def write_result_table(
         element["mu_gjk_max_shift"] = shift
         element["mu_gjk_max_shift_guide"] = names
         element["n_gjk"] = count
+    if sample_jackknife is not None:
+        flat = lambda v: np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)  # noqa: E731
+        shift, names = flat(sample_jackknife["mu_sjk_max_shift"]), list(sample_jackknife["mu_sjk_max_shift_sample"])
+        if not len(shift) == len(names) == len(element):
+            raise ValueError(f"the sample jackknife summary has {len(shift)} entries for {len(element)} targets")
+        element["mu_sjk_max_shift"] = shift
+        element["mu_sjk_max_shift_sample"] = names
+        element["n_sjk"] = int(sample_jackknife["n_sjk"])
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always
@@ -235,6 +250,9 @@ def write_result_table(
     if guide_jackknife is not None:
         guide_info_df["mu_shift_left_out"] = per_guide
     guide_info_df.to_csv(f"{prefix}bean_sgRNA_result.{model_label}{suffix}.csv")
+    if sample_jackknife is not None:
+        pd.DataFrame(sample_jackknife["influence"]).to_csv(f"{prefix}bean_sample_influence.{model_label}{suffix}.csv",
+                                                           index=False)
     if return_result:
         return element
     element.to_csv(f"{prefix}bean_element_result.{model_label}{suffix}.csv")

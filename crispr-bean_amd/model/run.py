@@ -191,9 +191,11 @@ def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000
     return store, out
 
 
-def _fit_members(model, guide, data, seeds, what, tag, dump_extra, common, report_every, verbose, member_masks=None):
-    """The batched fit behind ``run_inference_ensemble`` and ``run_inference_jackknife``: ``len(seeds)`` members of one
-    engine (member k with ``seeds[k]`` and, if given, its slice of ``member_masks``), stepped in report windows.
+def _fit_members(model, guide, data, seeds, what, tag, dump_extra, common, report_every, verbose, member_masks=None,
+                 member_counts=None):
+    """The batched fit behind ``run_inference_ensemble`` and the jackknives: ``len(seeds)`` members of one engine
+    (member k with ``seeds[k]`` and, if given, its slices of ``member_masks`` and ``member_counts``), stepped in report
+    windows.
     Returns the list of ``(param_store, {"loss", "params"})`` pairs, or ``None`` where the batched kernels do not take
     the shape (the caller then fits one after the other).  A non-finite loss of any member halts the fit at the end
     of its report window with the ``ValueError`` of ``run_inference``: the message names ``what[k]``, the parameters
@@ -208,6 +210,8 @@ def _fit_members(model, guide, data, seeds, what, tag, dump_extra, common, repor
         return None
     device = torch.device("cuda", torch.cuda.current_device())
     extra = {} if member_masks is None else {"member_masks": member_masks}
+    if member_counts is not None:
+        extra["member_counts"] = member_counts
     try:
         eng = build_engine(model, guide, data.to(device), device=device, n_guides_total=data.n_guides,
                            n_members=n, **extra, **common)
@@ -369,6 +373,74 @@ def run_inference_guide_jackknife(model, guide, data, seed: int = SEED, initial_
                     raise
                 raise ValueError(f"{exc} ({label})") from exc
     return results[0], results[1:], positions, included
+
+
+def run_inference_sample_jackknife(model, guide, data, by: str = "sample", seed: int = SEED, initial_lr=0.01, gamma=0.1,
+                                   num_steps=2000, report_every: int = 100, verbose: bool = True,
+                                   max_groups_per_run: int = 63):
+    """Sample jackknife: the fit of the screen and one fit per sample (``by="sample"``: one condition of one replicate)
+    or per condition (``by="condition"``: that condition of every replicate) with it masked as the reference masks a
+    sample - ``sample_mask`` and the counts zeroed (``model/jackknife.py::leave_out_samples``) - all with the same
+    ``seed``: common random numbers.
+
+    Returns ``(full, loo, groups, names)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns,
+    ``loo[j]`` exactly what it returns for ``leave_out_samples(data, groups[j])`` - bit for bit - and ``groups`` /
+    ``names`` are those of ``sample_groups(data, by)`` (fewer than two groups: ``ValueError``).  Where the batched
+    kernels take the shape (``bean_hip_ensemble_supported``) the fits are members of one engine that differ in
+    ``sample_mask`` AND in their counts (``HipSVI(member_masks=..., member_counts=...)``, member 0 = the screen itself),
+    stepped by the same launches, in report windows; more than ``max_groups_per_run`` groups (at most 63: the full
+    screen is member 0 of every run) are fitted in several such runs, ``full`` coming from the first.  Every other
+    family (tiling, survival, ControlNormal, sample covariates, screens large enough for the one-launch stepper) is
+    fitted screen after screen through ``run_inference``.  A non-finite loss of any member halts the fit at the end of
+    its report window with the ``ValueError`` of ``run_inference``; message and dump file (``tmp_result.full.pkl`` /
+    ``tmp_result.without_<name>.pkl``, with ``"left_out": [[r, b], ...]``) name the group.  Not combined with guide
+    sharding over several ranks."""
+    from .jackknife import MAX_GUIDE_POSITIONS, leave_out_samples, sample_groups, sample_member_counts, sample_member_masks
+
+    _single_rank_only("run_inference_sample_jackknife")
+    per_run = int(max_groups_per_run)
+    if not 1 <= per_run <= MAX_GUIDE_POSITIONS:
+        raise ValueError(f"max_groups_per_run must be in [1, {MAX_GUIDE_POSITIONS}] (the full screen is member 0 of "
+                         f"every run), got {per_run}")
+    groups, names = sample_groups(data, by)
+    seed = int(seed)
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+    label = lambda j: f"{by} {names[j]} left out"  # noqa: E731
+
+    def counts(part):
+        x, x_bc = sample_member_counts(data, part)
+        # (the barcode-matched counts travel only where the fit uses them: build_engine's reading of the model)
+        return x, (x_bc if bool(_resolve(model).get("use_bcmatch", True)) else None)
+
+    full, loo = None, []
+    for at in range(0, len(groups), per_run):
+        part = list(range(at, min(at + per_run, len(groups))))
+        results = _fit_members(model, guide, data, [seed] * (1 + len(part)),
+                               what=["the full screen"] + [label(j) for j in part],
+                               tag=["full"] + [f"without_{names[j]}" for j in part],
+                               dump_extra=[{"left_out": None, "seed": seed}]
+                               + [{"left_out": [list(p) for p in groups[j]], "seed": seed} for j in part],
+                               common=common, report_every=report_every, verbose=verbose,
+                               member_masks=sample_member_masks(data, [groups[j] for j in part]),
+                               member_counts=counts([groups[j] for j in part]))
+        if results is None:
+            break
+        if full is None:
+            full = results[0]
+        loo.extend(results[1:])
+    else:
+        return full, loo, groups, names
+    # one after the other
+    results = []
+    for what, d in zip(["the full screen"] + [label(j) for j in range(len(groups))],
+                       [data] + [leave_out_samples(data, g) for g in groups]):
+        try:
+            results.append(run_inference(model, guide, d, seed=seed, report_every=report_every, verbose=verbose, **common))
+        except ValueError as exc:
+            if "Fitting halted" not in str(exc):
+                raise
+            raise ValueError(f"{exc} ({what})") from exc
+    return results[0], results[1:], groups, names
 
 
 def identify_model_guide(args):

@@ -290,15 +290,46 @@ int bean_hip_svi_run(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_step,
  *                                 factors and every other buffer as bound here).  Null for both returns the handle
  *                                 to shared masks (prepare again).  The byte counts are checked against K.
  *
+ *   bean_hip_bind_member_counts   per-member counts: the members may also differ in their data (a sample jackknife:
+ *                                 member j is the screen with one sorted sample masked, whose counts the reference
+ *                                 zeroes - the guide kernel reads every bin's count whatever the sample mask says, so a
+ *                                 masked sample is not a mask change alone; a parametric bootstrap or a downsampling
+ *                                 run would bind their draws the same way).  `x` is (K, R, B, G) float32, member-major
+ *                                 like the parameters, device memory the caller keeps alive; `x_bcmatch` has the same
+ *                                 shape, is required exactly when the handle was created with BEAN_FLAG_USE_BCMATCH and
+ *                                 must be null otherwise.  Member k reads its slice where a single fit reads BEAN_BUF_X /
+ *                                 BEAN_BUF_X_BC; member 0 reads its slice too.  Those two slots stay bound and the
+ *                                 single-fit entry points (which address member 0) keep reading THEM, while the
+ *                                 data-only words in member 0's workspace are then those of member 0's slice: as with
+ *                                 member masks, on a handle with member counts the single-fit entry points are only
+ *                                 meaningful if member 0's slice equals the shared buffer (the sample jackknife binds it
+ *                                 so; the library does not compare the arrays).  Allowed after bean_hip_set_members and
+ *                                 before bean_hip_prepare, with or without bean_hip_bind_member_masks (either may be
+ *                                 bound, or both): a call marks the handle unprepared and drops the ensemble graphs,
+ *                                 and the following bean_hip_prepare computes the data-only words (the loss constant
+ *                                 holds the log-factorials of the counts; the observed totals per (replicate, guide))
+ *                                 once per member - it does so whenever member masks OR member counts are bound.
+ *                                 Member k is then, bit for bit, bean_hip_svi_run on a handle of its own whose
+ *                                 BEAN_BUF_X, BEAN_BUF_X_BC, BEAN_BUF_REPGUIDE and BEAN_BUF_SAMPLE_MASK are member k's
+ *                                 slices (size factors, a0 and every other buffer as bound here).  Null for both
+ *                                 returns the handle to shared counts (prepare again).  The byte counts are checked
+ *                                 against K.  The members' counts cost 4 K R B G bytes each; every other input stays
+ *                                 shared.
+ *
  * Errors (status < 0, message in bean_hip_last_error(), nothing launched): a null handle; set_members on a shape that
  * is not supported, after a bind, with n_members outside [1, BEAN_HIP_MAX_MEMBERS]; run_ensemble with n_seeds !=
  * n_members or null seeds; bind_member_masks on a shape that is not supported, before set_members, with one mask null
- * and the other not, or with byte counts other than K R G and 8 K R B (the message states K). */
+ * and the other not, or with byte counts other than K R G and 8 K R B (the message states K); bind_member_counts on a
+ * shape that is not supported, before set_members, with byte counts other than 4 K R B G (the message states K), with
+ * x_bcmatch on a handle without BEAN_FLAG_USE_BCMATCH or without it on a handle with the flag, or with x null and
+ * x_bcmatch not.  The handle stays usable after every one of them. */
 #define BEAN_HIP_MAX_MEMBERS 64
 int bean_hip_ensemble_supported(const bean_hip_ctx* ctx);
 int bean_hip_set_members(bean_hip_ctx* ctx, int32_t n_members);
 int bean_hip_bind_member_masks(bean_hip_ctx* ctx, const void* repguide, uint64_t repguide_bytes,
                                const void* sample_mask, uint64_t sample_mask_bytes);
+int bean_hip_bind_member_counts(bean_hip_ctx* ctx, const void* x, uint64_t x_bytes,
+                                const void* x_bcmatch, uint64_t x_bcmatch_bytes);
 int bean_hip_svi_run_ensemble(bean_hip_ctx* ctx, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
                               uint64_t n_steps, int32_t graph_chunk, void* stream);
 
