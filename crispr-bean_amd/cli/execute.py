@@ -64,36 +64,10 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    if getattr(args, "jackknife_replicates", False) and int(getattr(args, "n_seeds", 1) or 1) > 1:
-        parser.error("--jackknife-replicates fits every member with the same seed and does not combine with --n-seeds > 1.")
-    if getattr(args, "jackknife_replicates", False) and getattr(args, "load_existing", False):
-        parser.error("--jackknife-replicates needs the leave-one-replicate-out fits and does not combine with --load-existing.")
-    if getattr(args, "jackknife_guides", False):
-        if int(getattr(args, "n_seeds", 1) or 1) > 1:
-            parser.error("--jackknife-guides fits every member with the same seed and does not combine with --n-seeds > 1.")
-        if getattr(args, "jackknife_replicates", False):
-            parser.error("--jackknife-guides and --jackknife-replicates are two runs: they do not combine in one.")
-        if getattr(args, "load_existing", False):
-            parser.error("--jackknife-guides needs the leave-one-guide-out fits and does not combine with --load-existing.")
-        if getattr(args, "library_design", None) == "tiling":
-            parser.error("--jackknife-guides needs targets that own their guides and does not combine with tiling.")
-        if int(getattr(args, "jackknife_guides_max", 63)) > 63:
-            parser.error("--jackknife-guides-max is at most 63.")
+    from .run import member_mode
 
-
-    for flag, attr in (("--jackknife-samples", "jackknife_samples"), ("--jackknife-conditions", "jackknife_conditions")):
-        if not getattr(args, attr, False):
-            continue
-        if getattr(args, "jackknife_samples", False) and getattr(args, "jackknife_conditions", False):
-            parser.error("--jackknife-samples and --jackknife-conditions are two runs: they do not combine in one.")
-        if getattr(args, "jackknife_replicates", False):
-            parser.error(f"{flag} and --jackknife-replicates are two runs: they do not combine in one.")
-        if getattr(args, "jackknife_guides", False):
-            parser.error(f"{flag} and --jackknife-guides are two runs: they do not combine in one.")
-        if int(getattr(args, "n_seeds", 1) or 1) > 1:
-            parser.error(f"{flag} fits every member with the same seed and does not combine with --n-seeds > 1.")
-        if getattr(args, "load_existing", False):
-            parser.error(f"{flag} needs the leave-one-out fits and does not combine with --load-existing.")
+    member_mode(args, parser.error,
+                parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
 
 
 def main(argv=None):

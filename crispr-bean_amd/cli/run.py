@@ -15,6 +15,8 @@ from functools import partial
 import numpy as np
 
 from ..framework import read_h5ad
+from ..model import jackknife as jk
+from ..model import run as model_run
 from ..model.readwrite import write_result_table
 from ..model.run import (_check_prior_params, _get_guide_info, _get_guide_target_info, check_args,
                          identify_model_guide, identify_negctrl_model_guide, run_inference)
@@ -58,40 +60,58 @@ def _replicate_names(ndata):
     return names if len(names) == int(ndata.n_reps) else [str(r) for r in range(int(ndata.n_reps))]
 
 
+_SAME_SEED = "{flag} fits every member with the same seed and does not combine with --n-seeds > 1."
+_TWO_RUNS = "{flag} and {other} are two runs: they do not combine in one."
+_NEEDS_FITS = "{{flag}} needs the leave-one-{}out fits and does not combine with --load-existing."
+_SAMPLE_RULES = (("jackknife_replicates", _TWO_RUNS), ("jackknife_guides", _TWO_RUNS), ("n_seeds", _SAME_SEED),
+                 ("load_existing", _NEEDS_FITS.format("")))
+# the flags that ask for a member set, in the order their refusals are reported:
+# (attribute, mode, ((what it does not combine with, sentence), ...))
+MEMBER_FLAGS = (
+    ("jackknife_replicates", "replicates", (("n_seeds", _SAME_SEED),
+                                            ("load_existing", _NEEDS_FITS.format("replicate-")))),
+    ("jackknife_guides", "guides", (("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS),
+                                    ("load_existing", _NEEDS_FITS.format("guide-")),
+                                    ("tiling", "{flag} needs targets that own their guides and does not combine with tiling."))),
+    ("jackknife_samples", "sample", (("jackknife_conditions", _TWO_RUNS),) + _SAMPLE_RULES),
+    ("jackknife_conditions", "condition", (("jackknife_samples", _TWO_RUNS),) + _SAMPLE_RULES),
+)
+_IS_SET = {"n_seeds": lambda args: int(getattr(args, "n_seeds", 1) or 1) > 1,
+           "tiling": lambda args: getattr(args, "library_design", None) == "tiling",
+           "guides_max": lambda args: int(getattr(args, "jackknife_guides_max", 63)) > 63}
+
+
+def _refuse(message):
+    raise ValueError(message)
+
+
+def member_mode(args, fail=_refuse, only=None, parser_rules=None):
+    """The member set this run fits next to the screen: None, "seeds", "replicates", "guides", "sample" or "condition".
+    A combination that is refused goes to ``fail(sentence)`` (the parser's ``error``; here, raising ``ValueError``).
+    ``only``: the flags whose rules are looked at (default: all); ``parser_rules``: further rules per flag, after its own."""
+    is_set = lambda attr: _IS_SET.get(attr, lambda a: bool(getattr(a, attr, False)))(args)  # noqa: E731
+    flag = lambda attr: "--" + attr.replace("_", "-")  # noqa: E731
+    mode = "seeds" if is_set("n_seeds") else None
+    for attr, flag_mode, rules in MEMBER_FLAGS:
+        if not is_set(attr) or (only is not None and attr not in only):
+            continue
+        for other, sentence in rules + (parser_rules or {}).get(attr, ()):
+            if is_set(other):
+                fail(sentence.format(flag=flag(attr), other=flag(other)))
+        mode = flag_mode
+    return mode
+
+
 def check_guide_jackknife_switches(args) -> bool:
     """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
-    if not bool(getattr(args, "jackknife_guides", False)):
-        return False
-    if int(getattr(args, "n_seeds", 1) or 1) > 1:
-        raise ValueError("--jackknife-guides fits every member with the same seed and does not combine with --n-seeds > 1.")
-    if bool(getattr(args, "jackknife_replicates", False)):
-        raise ValueError("--jackknife-guides and --jackknife-replicates are two runs: they do not combine in one.")
-    if args.load_existing:
-        raise ValueError("--jackknife-guides needs the leave-one-guide-out fits and does not combine with --load-existing.")
-    if args.library_design == "tiling":
-        raise ValueError("--jackknife-guides needs targets that own their guides and does not combine with tiling.")
-    return True
+    return member_mode(args, only=("jackknife_guides",)) == "guides"
 
 
 def check_sample_jackknife_switches(args):
     """``"sample"`` / ``"condition"`` if --jackknife-samples / --jackknife-conditions is set, else None; the
     combinations they are refused with raise (the parser refuses them first)."""
-    by_sample = bool(getattr(args, "jackknife_samples", False))
-    by_condition = bool(getattr(args, "jackknife_conditions", False))
-    if not (by_sample or by_condition):
-        return None
-    if by_sample and by_condition:
-        raise ValueError("--jackknife-samples and --jackknife-conditions are two runs: they do not combine in one.")
-    flag = "--jackknife-samples" if by_sample else "--jackknife-conditions"
-    if bool(getattr(args, "jackknife_replicates", False)):
-        raise ValueError(f"{flag} and --jackknife-replicates are two runs: they do not combine in one.")
-    if bool(getattr(args, "jackknife_guides", False)):
-        raise ValueError(f"{flag} and --jackknife-guides are two runs: they do not combine in one.")
-    if int(getattr(args, "n_seeds", 1) or 1) > 1:
-        raise ValueError(f"{flag} fits every member with the same seed and does not combine with --n-seeds > 1.")
-    if args.load_existing:
-        raise ValueError(f"{flag} needs the leave-one-out fits and does not combine with --load-existing.")
-    return "sample" if by_sample else "condition"
+    mode = member_mode(args, only=("jackknife_samples", "jackknife_conditions"))
+    return mode if mode in ("sample", "condition") else None
 
 
 def _sample_group_names(ndata, groups, fallback, by, condition_column):
@@ -109,6 +129,48 @@ def _sample_group_names(ndata, groups, fallback, by, condition_column):
     else:
         return list(fallback)
     return names if len(set(names)) == len(names) else list(fallback)
+
+
+def _entries(heads, fits):
+    return [{**head, "params": out["params"], "loss": out["loss"]} for head, (_, out) in zip(heads, fits)]
+
+
+def _seed_members(fit, ndata, args, guide_names):
+    from ..model.ensemble import combine_ensemble
+
+    members = fit(model_run.run_inference_ensemble, seeds=[model_run.SEED + k for k in range(int(args.n_seeds))])
+    store, spread = combine_ensemble(members)  # the tables come from the combination
+    combined = (store, {"params": {k: v.detach().cpu() for k, v in store.items()}, "loss": members[0][1]["loss"]})
+    return combined, _entries([{}] * len(members), members), {"seed_sd": spread["mu_seed_sd"], "n_seeds": len(members)}
+
+
+def _replicate_members(fit, ndata, args, guide_names):
+    full, loo, left_out = fit(model_run.run_inference_jackknife)
+    names = _replicate_names(ndata)
+    return (full, _entries([{"left_out": names[r]} for r in left_out], loo),
+            {"jackknife": jk.jackknife_summary(full, loo, left_out, names)})
+
+
+def _guide_members(fit, ndata, args, guide_names):
+    full, loo, positions, included = fit(model_run.run_inference_guide_jackknife,
+                                         max_positions=int(getattr(args, "jackknife_guides_max", 63)))
+    return (full, {"included": included, "positions": _entries([{"position": j} for j in positions], loo)},
+            {"guide_jackknife": jk.guide_jackknife_summary(full, loo, positions, included, ndata, guide_names)})
+
+
+def _sample_members(fit, ndata, args, guide_names):
+    by = member_mode(args)
+    full, loo, groups, fallback = fit(model_run.run_inference_sample_jackknife, by=by)
+    names = _sample_group_names(ndata, groups, fallback, by, args.condition_col)
+    return (full, _entries([{"left_out": name, "pairs": [list(p) for p in g]} for name, g in zip(names, groups)], loo),
+            {"sample_jackknife": jk.sample_jackknife_summary(full, loo, groups, names)})
+
+
+# mode -> (what fits its members and returns (the fit the tables come from, the members' entry of the --save-raw
+#          pickle, write_result_table's keywords for their summary), the key of that entry)
+MEMBER_RUNS = {"seeds": (_seed_members, "ensemble"), "replicates": (_replicate_members, "jackknife"),
+               "guides": (_guide_members, "guide_jackknife"), "sample": (_sample_members, "sample_jackknife"),
+               "condition": (_sample_members, "sample_jackknife")}
 
 
 def main(args, return_data=False):
@@ -193,18 +255,8 @@ def main(args, return_data=False):
         model = partial(model, prior_params=_check_prior_params(args.prior_params, ndata))
 
     info(f"Running inference for {model_label}...")
-    n_seeds = int(getattr(args, "n_seeds", 1) or 1)
-    jackknife = bool(getattr(args, "jackknife_replicates", False))
-    if jackknife and n_seeds > 1:
-        raise ValueError("--jackknife-replicates fits every member with the same seed and does not combine with --n-seeds > 1.")
-    if jackknife and args.load_existing:
-        raise ValueError("--jackknife-replicates needs the leave-one-replicate-out fits and does not combine with --load-existing.")
-    guide_jackknife = check_guide_jackknife_switches(args)
-    sample_jackknife = check_sample_jackknife_switches(args)
-    sjk = None
-    seed_sd = None
-    jk = None
-    gjk = None
+    mode = member_mode(args)
+    table_columns = {}
     save_dict = dict()
     param_history_dict_negctrl = None
     if args.load_existing:
@@ -231,57 +283,14 @@ def main(args, return_data=False):
                                                param_history_dict_negctrl["mu_scale"].detach().mean()))
     if not args.load_existing:
         save_dict["data"] = ndata
-        if n_seeds > 1:
-            # a seed ensemble: member 0 is the fit a run without --n-seeds does; the tables come from the combination
-            from ..model.ensemble import combine_ensemble
-            from ..model.run import SEED, run_inference_ensemble
-
-            members = run_inference_ensemble(model, guide, ndata, [SEED + k for k in range(n_seeds)], num_steps=args.n_iter)
-            param_history_dict, spread = combine_ensemble(members)
-            seed_sd = spread["mu_seed_sd"]
-            save_dict["params"] = {k: v.detach().cpu() for k, v in param_history_dict.items()}
-            save_dict["loss"] = members[0][1]["loss"]
-            save_dict["ensemble"] = [{"params": out["params"], "loss": out["loss"]} for _, out in members]
-        elif jackknife:
-            # a replicate jackknife: member 0 is the fit a run without the flag does, and the tables come from it
-            from ..model.jackknife import jackknife_summary
-            from ..model.run import run_inference_jackknife
-
-            full, loo, left_out = run_inference_jackknife(model, guide, ndata, num_steps=args.n_iter)
-            names = _replicate_names(ndata)
-            jk = jackknife_summary(full, loo, left_out, names)
-            param_history_dict, save_dict_model = deepcopy(full)
+        if mode is not None:
+            # a member set: member 0 is the fit a run without the flag does, the set's summary adds columns to its tables
+            fit_members, key = MEMBER_RUNS[mode]
+            fit = lambda fit_of, **own: fit_of(model, guide, ndata, num_steps=args.n_iter, **own)  # noqa: E731
+            shown, saved, table_columns = fit_members(fit, ndata, args, list(guide_info_df.index))
+            param_history_dict, save_dict_model = deepcopy(shown)
             save_dict.update(save_dict_model)
-            save_dict["jackknife"] = [{"left_out": names[r], "params": out["params"], "loss": out["loss"]}
-                                      for r, (_, out) in zip(left_out, loo)]
-        elif guide_jackknife:
-            # a guide jackknife: member 0 is the fit a run without the flag does, and the tables' columns come from it
-            from ..model.jackknife import guide_jackknife_summary
-            from ..model.run import run_inference_guide_jackknife
-
-            full, loo, positions, included = run_inference_guide_jackknife(
-                model, guide, ndata, num_steps=args.n_iter, max_positions=int(getattr(args, "jackknife_guides_max", 63)))
-            gjk = guide_jackknife_summary(full, loo, positions, included, ndata, list(guide_info_df.index))
-            param_history_dict, save_dict_model = deepcopy(full)
-            save_dict.update(save_dict_model)
-            save_dict["guide_jackknife"] = {
-                "included": included,
-                "positions": [{"position": j, "params": out["params"], "loss": out["loss"]}
-                              for j, (_, out) in zip(positions, loo)]}
-        elif sample_jackknife:
-            # a sample jackknife: member 0 is the fit a run without the flag does, and the tables' columns come from it
-            from ..model.jackknife import sample_jackknife_summary
-            from ..model.run import run_inference_sample_jackknife
-
-            full, loo, groups, fallback = run_inference_sample_jackknife(model, guide, ndata, by=sample_jackknife,
-                                                                         num_steps=args.n_iter)
-            names = _sample_group_names(ndata, groups, fallback, sample_jackknife, args.condition_col)
-            sjk = sample_jackknife_summary(full, loo, groups, names)
-            param_history_dict, save_dict_model = deepcopy(full)
-            save_dict.update(save_dict_model)
-            save_dict["sample_jackknife"] = [
-                {"left_out": name, "pairs": [list(p) for p in g], "params": out["params"], "loss": out["loss"]}
-                for name, g, (_, out) in zip(names, groups, loo)]
+            save_dict[key] = saved
         else:
             param_history_dict, save_dict_model = deepcopy(run_inference(model, guide, ndata, num_steps=args.n_iter))
             save_dict.update(save_dict_model)
@@ -306,10 +315,7 @@ def main(args, return_data=False):
         sd_is_fitted=(args.selection == "sorting"),
         sample_covariates=getattr(ndata, "sample_covariates", None),
         is_survival_screen=(args.selection == "survival"),
-        **({"seed_sd": seed_sd, "n_seeds": n_seeds} if seed_sd is not None else {}),
-        **({"jackknife": jk} if jk is not None else {}),
-        **({"guide_jackknife": gjk} if gjk is not None else {}),
-        **({"sample_jackknife": sjk} if sjk is not None else {}),
+        **table_columns,
     )
     info("Done!")
     return prefix

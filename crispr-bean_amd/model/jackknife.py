@@ -27,14 +27,67 @@ The counts matter: the (replicate, guide) site of a masked sample stays on, and 
 bin whatever the sample mask says, so the members of such a jackknife differ in their data, not in their masks alone
 (``sample_member_masks``, ``sample_member_counts``, ``sample_jackknife_summary``).
 
+Each of these, and the seed ensemble, is K fits of one screen: a ``MemberPlan``, fitted by ``model/run.py::_fit_plan``.
+
 Pure torch: no GPU involved in this file.
 """
 from __future__ import annotations
 
 import copy
-from typing import Dict, List, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
+
+
+@dataclass(frozen=True)
+class MemberPlan:
+    """K fits of one screen, in member order: everything ``model/run.py::_fit_plan`` needs to fit them as members of
+    one engine or, where the batched kernels do not take the shape, one after the other."""
+    seeds: Sequence[int]
+    labels: Sequence[str]  # what a halt's message calls member k
+    tags: Sequence[str]  # a halt dumps member k to tmp_result.<tags[k]>.pkl ...
+    dump_extra: Sequence[dict]  # ... with these fields next to "param"
+    screen: Callable[[int], object]  # member k's screen: ``data`` itself, or a ``leave_out*`` copy
+    differ_in: Tuple[str, ...] = ()  # what the members' screens differ in: (), ("masks",) or ("masks", "counts")
+    per_run: Optional[int] = None  # members next to member 0 that one engine run may hold; None: all in one
+    label_halts: bool = False  # one after the other: append "(label)" to a halt's message
+    chosen: tuple = ()  # what the constructor chose (left-out replicates, positions, groups ...), for the caller
+
+
+def stack_masks(screens):
+    """``(repguide (K, R, G) bool, sample_mask (K, R, B))`` of K screens, in their order."""
+    return torch.stack([s.repguide_mask != 0 for s in screens]), torch.stack([s.sample_mask for s in screens])
+
+
+def stack_counts(screens):
+    """``(X (K, R, B, G), X_bcmatch (K, R, B, G) or None)`` of K screens, float32: their ``X_masked`` and, where the
+    first has them, ``X_bcmatch_masked``."""
+    x = torch.stack([s.X_masked.to(torch.float32) for s in screens])
+    if getattr(screens[0], "X_bcmatch_masked", None) is None:
+        return x, None
+    return x, torch.stack([s.X_bcmatch_masked.to(torch.float32) for s in screens])
+
+
+def seed_plan(data, seeds) -> MemberPlan:
+    """A seed ensemble: member k is the screen itself with ``seeds[k]``.  No seed is a ``ValueError``."""
+    seeds = [int(s) for s in seeds]
+    if not seeds:
+        raise ValueError("run_inference_ensemble needs at least one seed")
+    ks = range(len(seeds))
+    return MemberPlan(seeds, [f"member {k}" for k in ks], [f"member{k}" for k in ks],
+                      [{"member": k, "seed": seeds[k]} for k in ks], screen=lambda k: data)
+
+
+def _leave_one_out_plan(data, seed, items, label, tag, key, value, leave, **more) -> MemberPlan:
+    """One seed for all: member 0 is the screen itself, member 1 + j is ``leave(data, items[j])``."""
+    seed = int(seed)
+    return MemberPlan(
+        seeds=[seed] * (1 + len(items)),
+        labels=["the full screen"] + [label(x) for x in items],
+        tags=["full"] + [tag(x) for x in items],
+        dump_extra=[{key: None, "seed": seed}] + [{key: value(x), "seed": seed} for x in items],
+        screen=lambda k: data if k == 0 else leave(data, items[k - 1]), **more)
 
 
 def leave_out(data, r: int):
@@ -65,15 +118,25 @@ def candidate_replicates(data) -> List[int]:
 
 
 def member_masks(data, left_out: Sequence[int]):
-    """``(repguide (K, R, G) bool, sample_mask (K, R, B))`` of the K = 1 + len(left_out) fits: member 0 has the
-    screen's own masks, member 1 + j those of ``leave_out(data, left_out[j])``."""
-    screens = [data] + [leave_out(data, r) for r in left_out]
-    return (torch.stack([s.repguide_mask != 0 for s in screens]), torch.stack([s.sample_mask for s in screens]))
+    """``stack_masks`` of the screen and of ``leave_out(data, r)`` for every r of ``left_out``."""
+    return stack_masks([data] + [leave_out(data, r) for r in left_out])
+
+
+def replicate_plan(data, seed) -> MemberPlan:
+    """A replicate jackknife: the screen and, per replicate of ``candidate_replicates``, the screen without it."""
+    left_out = candidate_replicates(data)
+    return _leave_one_out_plan(data, seed, left_out, label=lambda r: f"replicate {r} left out",
+                               tag=lambda r: f"without_replicate{r}", key="left_out", value=lambda r: r,
+                               leave=leave_out, differ_in=("masks",), chosen=(left_out,))
+
+
+def _param(result, name) -> torch.Tensor:
+    store = result[0] if isinstance(result, (tuple, list)) else result
+    return store[name].detach().cpu().to(torch.float64)
 
 
 def _mu_loc(result) -> torch.Tensor:
-    store = result[0] if isinstance(result, (tuple, list)) else result
-    return store["mu_loc"].detach().cpu().to(torch.float64)
+    return _param(result, "mu_loc")
 
 
 def jackknife_summary(full, loo, left_out: Sequence[int], replicate_names: Sequence) -> Dict[str, object]:
@@ -154,11 +217,19 @@ def guides_at_position(data, j: int) -> torch.Tensor:
 
 
 def guide_member_masks(data, positions: Sequence[int]):
-    """``(repguide (K, R, G) bool, sample_mask (K, R, B))`` of the K = 1 + len(positions) fits: member 0 has the
-    screen's own masks, member 1 + j masks the guide at position ``positions[j]`` of every target that has one;
-    ``sample_mask`` is the screen's, K times."""
-    screens = [data] + [leave_out_guides(data, guides_at_position(data, j)) for j in positions]
-    return (torch.stack([s.repguide_mask != 0 for s in screens]), torch.stack([data.sample_mask] * len(screens)))
+    """``stack_masks`` of the screen and, for every j of ``positions``, of the screen with the guide at position j of
+    every target that has one masked."""
+    return stack_masks([data] + [leave_out_guides(data, guides_at_position(data, j)) for j in positions])
+
+
+def guide_plan(data, seed, max_positions: int = MAX_GUIDE_POSITIONS) -> MemberPlan:
+    """A guide jackknife: the screen and, per position of ``guide_positions``, the screen without the guide at that
+    position of every target.  One after the other, a halt's message gets the member's label."""
+    positions, included = guide_positions(data, max_positions)
+    return _leave_one_out_plan(data, seed, positions, label=lambda j: f"guides at position {j} of their targets left out",
+                               tag=lambda j: f"without_guide_position{j}", key="left_out_position", value=lambda j: j,
+                               leave=lambda d, j: leave_out_guides(d, guides_at_position(d, j)),
+                               differ_in=("masks",), label_halts=True, chosen=(positions, included))
 
 
 def guide_jackknife_summary(full, loo, positions: Sequence[int], included, data, guide_names: Sequence) -> Dict[str, object]:
@@ -270,25 +341,28 @@ def sample_groups(data, by: str = "sample") -> Tuple[List[List[Tuple[int, int]]]
 
 
 def sample_member_masks(data, groups):
-    """``(repguide (K, R, G) bool, sample_mask (K, R, B))`` of the K = 1 + len(groups) fits: member 0 has the screen's
-    own masks, member 1 + j those of ``leave_out_samples(data, groups[j])`` (``repguide`` is the screen's, K times)."""
-    screens = [data] + [leave_out_samples(data, g) for g in groups]
-    return (torch.stack([data.repguide_mask != 0] * len(screens)), torch.stack([s.sample_mask for s in screens]))
+    """``stack_masks`` of the screen and of ``leave_out_samples(data, g)`` for every g of ``groups``."""
+    return stack_masks([data] + [leave_out_samples(data, g) for g in groups])
 
 
 def sample_member_counts(data, groups):
-    """``(X (K, R, B, G), X_bcmatch (K, R, B, G) or None)`` of the K = 1 + len(groups) fits, float32: member 0 has the
-    screen's own ``X_masked`` / ``X_bcmatch_masked``, member 1 + j those of ``leave_out_samples(data, groups[j])``."""
-    screens = [data] + [leave_out_samples(data, g) for g in groups]
-    x = torch.stack([s.X_masked.to(torch.float32) for s in screens])
-    if getattr(data, "X_bcmatch_masked", None) is None:
-        return x, None
-    return x, torch.stack([s.X_bcmatch_masked.to(torch.float32) for s in screens])
+    """``stack_counts`` of the screen and of ``leave_out_samples(data, g)`` for every g of ``groups``."""
+    return stack_counts([data] + [leave_out_samples(data, g) for g in groups])
 
 
-def _param(result, name) -> torch.Tensor:
-    store = result[0] if isinstance(result, (tuple, list)) else result
-    return store[name].detach().cpu().to(torch.float64)
+def sample_plan(data, by: str, seed: int, max_groups_per_run: int = MAX_GUIDE_POSITIONS) -> MemberPlan:
+    """A sample jackknife: the screen and, per group of ``sample_groups(data, by)``, the screen without it - other masks
+    AND other counts - in engine runs of at most ``max_groups_per_run`` groups next to the full screen (outside
+    ``[1, 63]``: ``ValueError``).  One after the other, a halt's message gets the member's label."""
+    per_run = int(max_groups_per_run)
+    if not 1 <= per_run <= MAX_GUIDE_POSITIONS:
+        raise ValueError(f"max_groups_per_run must be in [1, {MAX_GUIDE_POSITIONS}] (the full screen is member 0 of "
+                         f"every run), got {per_run}")
+    groups, names = sample_groups(data, by)
+    return _leave_one_out_plan(data, seed, list(zip(names, groups)), label=lambda x: f"{by} {x[0]} left out",
+                               tag=lambda x: f"without_{x[0]}", key="left_out", value=lambda x: [list(p) for p in x[1]],
+                               leave=lambda d, x: leave_out_samples(d, x[1]), differ_in=("masks", "counts"),
+                               per_run=per_run, label_halts=True, chosen=(groups, names))
 
 
 def sample_jackknife_summary(full, loo, groups, names: Sequence) -> Dict[str, object]:

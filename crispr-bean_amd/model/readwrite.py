@@ -150,6 +150,23 @@ def _guide_editing_columns(guide_info_df: pd.DataFrame, P, guide_acc) -> None:
     guide_info_df.insert(2, "scaled_edit_eff", _scale_pi(edited_share, guide_acc, fitted_noise_logit=logit_noise))
 
 
+def _flat(v) -> np.ndarray:
+    return np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)
+
+
+def _add_summary_columns(element: pd.DataFrame, summary: dict, what: str, numeric: Sequence[str], names: str, count: str,
+                         count_per_target: bool = False) -> None:
+    """A member set's summary into the element table, in place and in this order: its ``numeric`` columns, its column
+    of ``names`` and its ``count`` (one number or, ``count_per_target``, an int64 per target).  Every per-target entry
+    must have the table's length."""
+    n = [int(summary[count])] * len(element) if not count_per_target else _flat(summary[count]).astype(np.int64)
+    columns = {**{k: _flat(summary[k]) for k in numeric}, names: list(summary[names]), count: n}
+    if any(len(v) != len(element) for v in columns.values()):
+        raise ValueError(f"{what} has {len(columns[numeric[0]])} entries for {len(element)} targets")
+    for k, v in columns.items():
+        element[k] = v
+
+
 def write_result_table(
     target_info_df: pd.DataFrame,
     guide_info_df: pd.DataFrame,
@@ -203,41 +220,23 @@ def write_result_table(
     if seed_sd is not None or n_seeds is not None:
         if seed_sd is None or n_seeds is None:
             raise ValueError("seed_sd and n_seeds go together")
-        spread = np.asarray(seed_sd.detach().cpu() if hasattr(seed_sd, "detach") else seed_sd, dtype=np.float64).reshape(-1)
+        spread = _flat(seed_sd)
         if len(spread) != len(element):
             raise ValueError(f"seed_sd has {len(spread)} entries for {len(element)} targets")
         element["mu_seed_sd"] = spread
         element["n_seeds"] = int(n_seeds)
     if jackknife is not None:
-        flat = lambda v: np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)  # noqa: E731
-        se, shift, reps = flat(jackknife["mu_jk_se"]), flat(jackknife["mu_jk_max_shift"]), list(jackknife["mu_jk_max_shift_rep"])
-        if not len(se) == len(shift) == len(reps) == len(element):
-            raise ValueError(f"the jackknife summary has {len(se)} entries for {len(element)} targets")
-        element["mu_jk_se"] = se
-        element["mu_jk_max_shift"] = shift
-        element["mu_jk_max_shift_rep"] = reps
-        element["n_jk"] = int(jackknife["n_jk"])
+        _add_summary_columns(element, jackknife, "the jackknife summary", ("mu_jk_se", "mu_jk_max_shift"),
+                             "mu_jk_max_shift_rep", "n_jk")
     if guide_jackknife is not None:
-        flat = lambda v: np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)  # noqa: E731
-        gj = guide_jackknife
-        se, shift, names = flat(gj["mu_gjk_se"]), flat(gj["mu_gjk_max_shift"]), list(gj["mu_gjk_max_shift_guide"])
-        count, per_guide = flat(gj["n_gjk"]).astype(np.int64), flat(gj["mu_shift_left_out"])
-        if not len(se) == len(shift) == len(names) == len(count) == len(element):
-            raise ValueError(f"the guide jackknife summary has {len(se)} entries for {len(element)} targets")
+        per_guide = _flat(guide_jackknife["mu_shift_left_out"])
         if len(per_guide) != len(guide_info_df):
             raise ValueError(f"the guide jackknife summary has {len(per_guide)} entries for {len(guide_info_df)} guides")
-        element["mu_gjk_se"] = se
-        element["mu_gjk_max_shift"] = shift
-        element["mu_gjk_max_shift_guide"] = names
-        element["n_gjk"] = count
+        _add_summary_columns(element, guide_jackknife, "the guide jackknife summary", ("mu_gjk_se", "mu_gjk_max_shift"),
+                             "mu_gjk_max_shift_guide", "n_gjk", count_per_target=True)
     if sample_jackknife is not None:
-        flat = lambda v: np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)  # noqa: E731
-        shift, names = flat(sample_jackknife["mu_sjk_max_shift"]), list(sample_jackknife["mu_sjk_max_shift_sample"])
-        if not len(shift) == len(names) == len(element):
-            raise ValueError(f"the sample jackknife summary has {len(shift)} entries for {len(element)} targets")
-        element["mu_sjk_max_shift"] = shift
-        element["mu_sjk_max_shift_sample"] = names
-        element["n_sjk"] = int(sample_jackknife["n_sjk"])
+        _add_summary_columns(element, sample_jackknife, "the sample jackknife summary", ("mu_sjk_max_shift",),
+                             "mu_sjk_max_shift_sample", "n_sjk")
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

@@ -18,6 +18,7 @@ import torch
 
 from ..engine import HipSVI
 from . import model as sorting_model
+from .jackknife import guide_plan, replicate_plan, sample_plan, seed_plan, stack_counts, stack_masks
 from .model import ModelSpec
 
 logger = logging.getLogger(__name__)
@@ -175,43 +176,39 @@ def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000
                 eng = engines[-1]
                 dump = {k: v.cpu() for k, v in eng.constrained(getattr(eng, "window_start", None)).items()}
             pkl.dump({"param": dump}, handle)
-        for e in engines:
-            e.close()
         raise ValueError(
             f"Fitting halted for command: {' '.join(sys.argv)} with following error: \n {exc}"
         )
-    except Exception:
+    finally:
         for e in engines:
             e.close()
-        raise
-    for e in engines:
-        e.close()
     store = ParamStore(constrained)
     out = {"loss": losses, "params": {k: v.detach().cpu() for k, v in constrained.items()}}
     return store, out
 
 
-def _fit_members(model, guide, data, seeds, what, tag, dump_extra, common, report_every, verbose, member_masks=None,
-                 member_counts=None):
-    """The batched fit behind ``run_inference_ensemble`` and the jackknives: ``len(seeds)`` members of one engine
-    (member k with ``seeds[k]`` and, if given, its slices of ``member_masks`` and ``member_counts``), stepped in report
-    windows.
-    Returns the list of ``(param_store, {"loss", "params"})`` pairs, or ``None`` where the batched kernels do not take
-    the shape (the caller then fits one after the other).  A non-finite loss of any member halts the fit at the end
-    of its report window with the ``ValueError`` of ``run_inference``: the message names ``what[k]``, the parameters
-    as they were at the start of the window go to ``tmp_result.<tag[k]>.pkl`` together with ``dump_extra[k]``."""
+def _fit_members(model, guide, data, plan, run, common, report_every, verbose):
+    """One engine run of ``_fit_plan``: the members ``run`` of ``plan`` (member i of the engine is member ``run[i]`` of
+    the plan).  Returns their ``(param_store, {"loss", "params"})`` pairs, or ``None`` where the batched kernels do not
+    take the shape; halts as ``_fit_plan`` says."""
     from .. import parallel
     from .._lib import MAX_MEMBERS
     from ..engine import EnsembleUnsupported
 
-    n = len(seeds)
+    n = len(run)
+    seeds = [plan.seeds[k] for k in run]
     spec = _resolve(model)
+    extra = {}
+    if plan.differ_in:
+        screens = [plan.screen(k) for k in run]
+        extra["member_masks"] = stack_masks(screens)
+        if "counts" in plan.differ_in:
+            x, x_bc = stack_counts(screens)
+            # (the barcode-matched counts travel only where the fit uses them: build_engine's reading of the model)
+            extra["member_counts"] = (x, x_bc if bool(spec.get("use_bcmatch", True)) else None)
     if spec.family in ("MultiMixtureNormal", "ControlNormal") or spec.selection == "survival" or n > MAX_MEMBERS:
         return None
     device = torch.device("cuda", torch.cuda.current_device())
-    extra = {} if member_masks is None else {"member_masks": member_masks}
-    if member_counts is not None:
-        extra["member_counts"] = member_counts
     try:
         eng = build_engine(model, guide, data.to(device), device=device, n_guides_total=data.n_guides,
                            n_members=n, **extra, **common)
@@ -229,16 +226,15 @@ def _fit_members(model, guide, data, seeds, what, tag, dump_extra, common, repor
                 try:
                     parallel.check_window_finite(windows[member], done)
                 except FloatingPointError as exc:
-                    name = f"tmp_result.{tag[member]}.pkl"
-                    error(f"Error occurred during fitting ({what[member]}, seed {seeds[member]}). "
+                    what = plan.labels[run[member]]
+                    name = f"tmp_result.{plan.tags[run[member]]}.pkl"
+                    error(f"Error occurred during fitting ({what}, seed {seeds[member]}). "
                           f"Saving temporary output at {name}.")
                     with open(name, "wb") as handle:
                         dump = {p: v.cpu() for p, v in eng.constrained(window_start, member=member).items()}
-                        pkl.dump({"param": dump, **dump_extra[member]}, handle)
-                    raise ValueError(
-                        f"Fitting halted for command: {' '.join(sys.argv)} with following error: \n "
-                        f"{what[member]} (seed {seeds[member]}): {exc}"
-                    )
+                        pkl.dump({"param": dump, **plan.dump_extra[run[member]]}, handle)
+                    raise ValueError(f"Fitting halted for command: {' '.join(sys.argv)} with following error: \n "
+                                     f"{what} (seed {seeds[member]}): {exc}")
             if verbose:
                 print(f"loss {' '.join(str(float(v)) for v in windows[:, 0])} @ iter {done}")
             done += k
@@ -250,6 +246,43 @@ def _fit_members(model, guide, data, seeds, what, tag, dump_extra, common, repor
                             {"loss": losses[member].tolist(), "params": {p: v.detach().cpu() for p, v in constrained.items()}}))
     finally:
         eng.close()
+    return results
+
+
+def _fit_plan(model, guide, data, plan, common, report_every, verbose):
+    """The K fits of a ``MemberPlan`` (``model/jackknife.py``): the list of what ``run_inference`` returns for
+    ``plan.screen(k)`` with ``plan.seeds[k]`` - bit for bit.  This is the fit behind ``run_inference_ensemble`` and the
+    three jackknives.
+
+    Where the batched kernels take the shape (the sorting variant families: ``bean_hip_ensemble_supported``) the fits
+    are members of one engine - with their own masks and counts where the plan's screens differ in them
+    (``HipSVI(member_masks=..., member_counts=...)``, member 0 = the screen itself) - stepped by the same launches, in
+    report windows.  With ``plan.per_run`` an engine run holds member 0 and at most that many further members; member
+    0's result is the first run's.  Every other family (tiling, survival, ControlNormal, sample covariates, screens large
+    enough for the one-launch stepper) and more than ``MAX_MEMBERS`` members in one run are fitted one after the other
+    through ``run_inference``.  A non-finite loss of ANY member halts the fit at the end of its report window with the
+    ``ValueError`` of ``run_inference``: the message names ``plan.labels[k]`` and the seed, and the parameters as they
+    were at the start of the window go to ``tmp_result.<plan.tags[k]>.pkl`` together with ``plan.dump_extra[k]``."""
+    K = len(plan.seeds)
+    results = {}
+    for at in range(1, max(K, 2), plan.per_run or K):
+        run = [0] + list(range(at, min(at + (plan.per_run or K), K)))
+        fitted = _fit_members(model, guide, data, plan, run, common, report_every, verbose)
+        if fitted is None:
+            break
+        for k, fit in zip(run, fitted):
+            results.setdefault(k, fit)  # (member 0: the first run's)
+    else:
+        return [results[k] for k in range(K)]
+    results = []  # one after the other
+    for k, seed in enumerate(plan.seeds):
+        try:
+            results.append(run_inference(model, guide, plan.screen(k), seed=seed, report_every=report_every,
+                                         verbose=verbose, **common))
+        except ValueError as exc:
+            if not plan.label_halts or "Fitting halted" not in str(exc):
+                raise
+            raise ValueError(f"{exc} ({plan.labels[k]})") from exc
     return results
 
 
@@ -265,26 +298,14 @@ def run_inference_ensemble(model, guide, data, seeds, initial_lr=0.01, gamma=0.1
     """``len(seeds)`` independent SVI fits of one screen, member k with the random streams of ``seeds[k]``.
 
     Returns a list of ``(param_store, {"loss", "params"})`` pairs, each exactly what
-    ``run_inference(..., seed=seeds[k])`` returns - bit for bit.  Where the batched kernels take the shape (the
-    sorting variant families: ``bean_hip_ensemble_supported``) all members are stepped by the same launches; every
-    other family (tiling, survival, ControlNormal, sample covariates, screens large enough to fill the GPU with one
-    fit) is fitted seed after seed through ``run_inference``.  A non-finite loss of ANY member halts the fit at the
-    end of its report window with the ``ValueError`` of ``run_inference``; message and dump file
-    (``tmp_result.member<k>.pkl``) name the member.  Not combined with guide sharding over several ranks."""
-    seeds = [int(s) for s in seeds]
-    if not seeds:
-        raise ValueError("run_inference_ensemble needs at least one seed")
+    ``run_inference(..., seed=seeds[k])`` returns - bit for bit: all members stepped by the same launches where the
+    batched kernels take the shape, else seed after seed (``_fit_plan``).  A non-finite loss of ANY member halts the fit;
+    message and dump file (``tmp_result.member<k>.pkl``) name the member.  Not combined with guide sharding over
+    several ranks."""
+    plan = seed_plan(data, seeds)
     _single_rank_only("run_inference_ensemble")
-    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
-    members = range(len(seeds))
-    results = _fit_members(model, guide, data, seeds, what=[f"member {k}" for k in members],
-                           tag=[f"member{k}" for k in members],
-                           dump_extra=[{"member": k, "seed": seeds[k]} for k in members],
-                           common=common, report_every=report_every, verbose=verbose)
-    if results is None:  # one after the other
-        results = [run_inference(model, guide, data, seed=s, report_every=report_every, verbose=verbose, **common)
-                   for s in seeds]
-    return results
+    return _fit_plan(model, guide, data, plan, dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps),
+                     report_every, verbose)
 
 
 def run_inference_jackknife(model, guide, data, seed: int = SEED, initial_lr=0.01, gamma=0.1, num_steps=2000,
@@ -295,30 +316,16 @@ def run_inference_jackknife(model, guide, data, seed: int = SEED, initial_lr=0.0
 
     Returns ``(full, loo, left_out)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns, ``loo[j]``
     exactly what it returns for ``leave_out(data, left_out[j])`` - bit for bit - and ``left_out`` lists the replicates
-    that are not already fully masked (fewer than two: ``ValueError``).  Where the batched kernels take the shape
-    (``bean_hip_ensemble_supported``) the 1 + len(left_out) fits are members of one engine that differ in their masks
-    only (``HipSVI(member_masks=...)``, member 0 = the screen's own masks) and are stepped by the same launches, in
-    report windows; every other family (tiling, survival, ControlNormal, sample covariates, screens large enough for
-    the one-launch stepper) is fitted mask after mask through ``run_inference``.  A non-finite loss of any member halts
-    the fit at the end of its report window with the ``ValueError`` of ``run_inference``; message and dump file
-    (``tmp_result.full.pkl`` / ``tmp_result.without_replicate<r>.pkl``, with ``"left_out": r``) name the left-out
-    replicate.  Not combined with guide sharding over several ranks."""
-    from .jackknife import candidate_replicates, leave_out, member_masks
-
+    that are not already fully masked (fewer than two: ``ValueError``).  The 1 + len(left_out) fits differ in their
+    masks only: members of one engine where the batched kernels take the shape, else mask after mask (``_fit_plan``).
+    A non-finite loss of any member halts the fit; message and dump file (``tmp_result.full.pkl`` /
+    ``tmp_result.without_replicate<r>.pkl``, with ``"left_out": r``) name the left-out replicate.  Not combined with
+    guide sharding over several ranks."""
     _single_rank_only("run_inference_jackknife")
-    left_out = candidate_replicates(data)
-    seed = int(seed)
-    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
-    results = _fit_members(model, guide, data, [seed] * (1 + len(left_out)),
-                           what=["the full screen"] + [f"replicate {r} left out" for r in left_out],
-                           tag=["full"] + [f"without_replicate{r}" for r in left_out],
-                           dump_extra=[{"left_out": r, "seed": seed} for r in [None] + list(left_out)],
-                           common=common, report_every=report_every, verbose=verbose,
-                           member_masks=member_masks(data, left_out))
-    if results is None:  # one after the other
-        results = [run_inference(model, guide, d, seed=seed, report_every=report_every, verbose=verbose, **common)
-                   for d in [data] + [leave_out(data, r) for r in left_out]]
-    return results[0], results[1:], left_out
+    plan = replicate_plan(data, seed)
+    results = _fit_plan(model, guide, data, plan, dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps),
+                        report_every, verbose)
+    return (results[0], results[1:], *plan.chosen)
 
 
 def run_inference_guide_jackknife(model, guide, data, seed: int = SEED, initial_lr=0.01, gamma=0.1, num_steps=2000,
@@ -336,43 +343,24 @@ def run_inference_guide_jackknife(model, guide, data, seed: int = SEED, initial_
     in all its options) the targets share no parameter and the streams are keyed by global index: target t's slice of
     ``loo[i]`` is, bit for bit, its slice of the fit with only guide (t, positions[i]) masked, and a target without a
     guide at that position keeps the full fit's bits.  There the 1 + len(positions) fits are members of one engine
-    that differ in ``repguide_mask`` only and are stepped by the same launches, in report windows
-    (``bean_hip_ensemble_supported``).  Everywhere else the masks are fitted one after the other through
-    ``run_inference``, with the same return value - but survival variant screens couple their targets through ``q0``
-    and sorting ``Normal`` with sample covariates through ``mu_cov``: a member is then "position j left out
-    everywhere", NOT a set of single-guide fits.  Tiling families are refused (an edit's guides are not a target's
-    guides), as are several ranks.  A non-finite loss of any member halts the fit at the end of its report window with
-    the ``ValueError`` of ``run_inference``; message and dump file (``tmp_result.full.pkl`` /
+    that differ in ``repguide_mask`` only (``_fit_plan``).  Everywhere else the masks are fitted one after the other,
+    with the same return value - but survival variant screens couple their targets through ``q0`` and sorting
+    ``Normal`` with sample covariates through ``mu_cov``: a member is then "position j left out everywhere", NOT a set
+    of single-guide fits.  Tiling families are refused (an edit's guides are not a target's guides), as are several
+    ranks.  A non-finite loss of any member halts the fit; message and dump file (``tmp_result.full.pkl`` /
     ``tmp_result.without_guide_position<j>.pkl``, with ``"left_out_position": j``) name the position."""
-    from .jackknife import guides_at_position, guide_member_masks, guide_positions, leave_out_guides
-
     spec = _resolve(model)
     if spec.family == "MultiMixtureNormal" or getattr(data, "library_design", "variant") == "tiling":
         raise ValueError("a guide jackknife needs targets that own their guides: not defined for tiling screens "
                          "(an edit's guides are not a target's guides)")
     _single_rank_only("run_inference_guide_jackknife")
-    positions, included = guide_positions(data, max_positions)
+    plan = guide_plan(data, seed, max_positions)
     n_long = int((data.target_lengths.detach().cpu() > int(max_positions)).sum())
     if n_long:
         info(f"Guide jackknife: {n_long} target(s) with more than {int(max_positions)} guides take no part.")
-    seed = int(seed)
-    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
-    what = ["the full screen"] + [f"guides at position {j} of their targets left out" for j in positions]
-    results = _fit_members(model, guide, data, [seed] * (1 + len(positions)), what=what,
-                           tag=["full"] + [f"without_guide_position{j}" for j in positions],
-                           dump_extra=[{"left_out_position": j, "seed": seed} for j in [None] + list(positions)],
-                           common=common, report_every=report_every, verbose=verbose,
-                           member_masks=guide_member_masks(data, positions))
-    if results is None:  # one after the other
-        results = []
-        for label, d in zip(what, [data] + [leave_out_guides(data, guides_at_position(data, j)) for j in positions]):
-            try:
-                results.append(run_inference(model, guide, d, seed=seed, report_every=report_every, verbose=verbose, **common))
-            except ValueError as exc:
-                if "Fitting halted" not in str(exc):
-                    raise
-                raise ValueError(f"{exc} ({label})") from exc
-    return results[0], results[1:], positions, included
+    results = _fit_plan(model, guide, data, plan, dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps),
+                        report_every, verbose)
+    return (results[0], results[1:], *plan.chosen)
 
 
 def run_inference_sample_jackknife(model, guide, data, by: str = "sample", seed: int = SEED, initial_lr=0.01, gamma=0.1,
@@ -385,62 +373,17 @@ def run_inference_sample_jackknife(model, guide, data, by: str = "sample", seed:
 
     Returns ``(full, loo, groups, names)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns,
     ``loo[j]`` exactly what it returns for ``leave_out_samples(data, groups[j])`` - bit for bit - and ``groups`` /
-    ``names`` are those of ``sample_groups(data, by)`` (fewer than two groups: ``ValueError``).  Where the batched
-    kernels take the shape (``bean_hip_ensemble_supported``) the fits are members of one engine that differ in
-    ``sample_mask`` AND in their counts (``HipSVI(member_masks=..., member_counts=...)``, member 0 = the screen itself),
-    stepped by the same launches, in report windows; more than ``max_groups_per_run`` groups (at most 63: the full
-    screen is member 0 of every run) are fitted in several such runs, ``full`` coming from the first.  Every other
-    family (tiling, survival, ControlNormal, sample covariates, screens large enough for the one-launch stepper) is
-    fitted screen after screen through ``run_inference``.  A non-finite loss of any member halts the fit at the end of
-    its report window with the ``ValueError`` of ``run_inference``; message and dump file (``tmp_result.full.pkl`` /
-    ``tmp_result.without_<name>.pkl``, with ``"left_out": [[r, b], ...]``) name the group.  Not combined with guide
-    sharding over several ranks."""
-    from .jackknife import MAX_GUIDE_POSITIONS, leave_out_samples, sample_groups, sample_member_counts, sample_member_masks
-
+    ``names`` are those of ``sample_groups(data, by)`` (fewer than two groups: ``ValueError``).  The fits differ in
+    ``sample_mask`` AND in their counts: members of one engine where the batched kernels take the shape - more than
+    ``max_groups_per_run`` groups (at most 63: the full screen is member 0 of every run) in several such runs, ``full``
+    coming from the first - else screen after screen (``_fit_plan``).  A non-finite loss of any member halts the fit;
+    message and dump file (``tmp_result.full.pkl`` / ``tmp_result.without_<name>.pkl``, with ``"left_out": [[r, b],
+    ...]``) name the group.  Not combined with guide sharding over several ranks."""
     _single_rank_only("run_inference_sample_jackknife")
-    per_run = int(max_groups_per_run)
-    if not 1 <= per_run <= MAX_GUIDE_POSITIONS:
-        raise ValueError(f"max_groups_per_run must be in [1, {MAX_GUIDE_POSITIONS}] (the full screen is member 0 of "
-                         f"every run), got {per_run}")
-    groups, names = sample_groups(data, by)
-    seed = int(seed)
-    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
-    label = lambda j: f"{by} {names[j]} left out"  # noqa: E731
-
-    def counts(part):
-        x, x_bc = sample_member_counts(data, part)
-        # (the barcode-matched counts travel only where the fit uses them: build_engine's reading of the model)
-        return x, (x_bc if bool(_resolve(model).get("use_bcmatch", True)) else None)
-
-    full, loo = None, []
-    for at in range(0, len(groups), per_run):
-        part = list(range(at, min(at + per_run, len(groups))))
-        results = _fit_members(model, guide, data, [seed] * (1 + len(part)),
-                               what=["the full screen"] + [label(j) for j in part],
-                               tag=["full"] + [f"without_{names[j]}" for j in part],
-                               dump_extra=[{"left_out": None, "seed": seed}]
-                               + [{"left_out": [list(p) for p in groups[j]], "seed": seed} for j in part],
-                               common=common, report_every=report_every, verbose=verbose,
-                               member_masks=sample_member_masks(data, [groups[j] for j in part]),
-                               member_counts=counts([groups[j] for j in part]))
-        if results is None:
-            break
-        if full is None:
-            full = results[0]
-        loo.extend(results[1:])
-    else:
-        return full, loo, groups, names
-    # one after the other
-    results = []
-    for what, d in zip(["the full screen"] + [label(j) for j in range(len(groups))],
-                       [data] + [leave_out_samples(data, g) for g in groups]):
-        try:
-            results.append(run_inference(model, guide, d, seed=seed, report_every=report_every, verbose=verbose, **common))
-        except ValueError as exc:
-            if "Fitting halted" not in str(exc):
-                raise
-            raise ValueError(f"{exc} ({what})") from exc
-    return results[0], results[1:], groups, names
+    plan = sample_plan(data, by, seed, max_groups_per_run)
+    results = _fit_plan(model, guide, data, plan, dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps),
+                        report_every, verbose)
+    return (results[0], results[1:], *plan.chosen)
 
 
 def identify_model_guide(args):

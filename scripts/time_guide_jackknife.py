@@ -14,184 +14,39 @@ synchronisations; engines are built outside the timed region on both sides (the 
 copy: the masks are bound data).  Written: median / min / max wall time per fit-set and the waves per SIMD of the two
 launches of a step.
 """
-import argparse
-import json
-import os
-import statistics
-import subprocess
-import sys
-import time
+import member_timing as mt
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WINDOW = 100
 SHAPES = [  # (label, guides, replicates, family, engine keywords): 5 guides per target, members = 5 + 1
     ("readme 3455x6 MixtureNormal", 3455, 6, "MixtureNormal", {}),
     ("readme 3455x6 MixtureNormal+Acc", 3455, 6, "MixtureNormal", {"scale_by_accessibility": True}),
     ("5000x3 MixtureNormal", 5000, 3, "MixtureNormal", {}),
     ("5000x3 MixtureNormal+Acc", 5000, 3, "MixtureNormal", {"scale_by_accessibility": True}),
 ]
-SEED = 101
 LMAX = 5  # guides per target of make_sorting_variant_screen
+WHAT = ("guide jackknife, 1 + Lmax masked fits as members of one engine (this build) vs the same fits in a row "
+        "(parent build), wall time per fit-set")
 
 
-def worker():
-    sys.path.insert(0, ROOT)
-    import torch
-
-    import bean_amd  # noqa: F401
-    from bean_amd import engine
+def build(engine, data, fam, kw, steps, mode, k):
     from bean_amd.model.jackknife import guides_at_position, guide_member_masks, guide_positions, leave_out_guides
-    from bean_amd.preprocessing.synthetic import make_sorting_variant_screen
 
-    dev = torch.device("cuda:0")
-    screens, engines = {}, {}
-
-    def screen(i):
-        if i not in screens:
-            _, g, r, _, kw = SHAPES[i]
-            screens[i] = make_sorting_variant_screen(g, r, seed=7, with_accessibility=bool(kw.get("scale_by_accessibility"))).to(dev)
-        return screens[i]
-
-    def engines_of(i, mode, steps):
-        if (i, mode) not in engines:
-            for key in [key for key in engines if key[0] != i]:  # one shape's engines at a time
-                for e in engines.pop(key):
-                    e.close()
-            _, _, _, fam, kw = SHAPES[i]
-            data = screen(i)
-            positions, _ = guide_positions(data)
-            assert len(positions) == LMAX
-            if mode == "batched":
-                engines[(i, mode)] = [engine.HipSVI(fam, data, num_steps=steps, n_members=1 + len(positions),
-                                                    member_masks=guide_member_masks(data, positions), **kw)]
-            else:
-                engines[(i, mode)] = [engine.HipSVI(fam, d, num_steps=steps, **kw)
-                                      for d in [data] + [leave_out_guides(data, guides_at_position(data, j)) for j in positions]]
-        return engines[(i, mode)]
-
-    for line in sys.stdin:
-        req = json.loads(line)
-        if req["op"] == "quit":
-            break
-        i, steps, mode = req["shape"], req["steps"], req["mode"]
-        es = engines_of(i, mode, req["capacity"])
-        k = LMAX + 1
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        if mode == "batched":
-            for first in range(0, steps, WINDOW):
-                es[0].run_ensemble(min(WINDOW, steps - first), [SEED] * k, first_step=first)
-        else:
-            for e in es:  # the masked fits in a row: every fit begins like a fresh one (its first window prepares)
-                for first in range(0, steps, WINDOW):
-                    e.run(min(WINDOW, steps - first), seed=SEED, first_step=first, resume=True)
-        torch.cuda.synchronize(dev)
-        dt = time.perf_counter() - t0
-        e = es[0]
-        info = {"wall_s": dt, "kernel": e.dominant_kernel, "cus": torch.cuda.get_device_properties(dev).multi_processor_count,
-                "targets": int(e.T), "members": k, "finite": all(bool(torch.isfinite(x.loss_hist).all()) for x in es)}
-        sys.stdout.write(json.dumps(info) + "\n")
-        sys.stdout.flush()
-    for es in engines.values():
-        for e in es:
-            e.close()
+    positions, _ = guide_positions(data)
+    assert len(positions) == LMAX
+    if mode == "batched":
+        return [engine.HipSVI(fam, data, num_steps=steps, n_members=1 + LMAX,
+                              member_masks=guide_member_masks(data, positions), **kw)]
+    return [engine.HipSVI(fam, d, num_steps=steps, **kw)
+            for d in [data] + [leave_out_guides(data, guides_at_position(data, j)) for j in positions]]
 
 
-class Worker:
-    def __init__(self, lib=None):
-        env = dict(os.environ)
-        if lib:
-            env["BEAN_HIP_LIB"] = os.path.abspath(lib)
-        else:
-            env.pop("BEAN_HIP_LIB", None)
-        self.p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--worker"], stdin=subprocess.PIPE,
-                                  stdout=subprocess.PIPE, text=True, env=env)
-
-    def ask(self, **req):
-        self.p.stdin.write(json.dumps(req) + "\n")
-        self.p.stdin.flush()
-        line = self.p.stdout.readline()
-        if not line:
-            raise RuntimeError(f"worker died (exit status {self.p.poll()})")
-        return json.loads(line)
-
-    def close(self):
-        try:
-            self.p.stdin.write(json.dumps({"op": "quit"}) + "\n")
-            self.p.stdin.flush()
-            self.p.wait(timeout=60)
-        except Exception:
-            self.p.kill()
+def seeds_of(data, k):
+    return [mt.SEED] * (1 + LMAX)
 
 
-def waves_per_simd(guides, reps, targets, k, cus):
-    simds = 4 * cus
-    tiles = (guides + 63) // 64
-    guide_waves = (tiles + 7) // 8 * 8 * reps * k
-    param_blocks = (targets * 16 + 255) // 256 + (guides + 255) // 256
-    return {"k_guide_wave2": guide_waves / simds, "k_param": 4 * param_blocks * k / simds}
-
-
-def stats(xs):
-    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "n": len(xs)}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--worker", action="store_true")
-    ap.add_argument("--parent-lib")
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "guide_jackknife_small_screens.json"))
-    a = ap.parse_args()
-    if a.worker:
-        return worker()
-    if not a.parent_lib or not os.path.exists(a.parent_lib):
-        sys.exit("--parent-lib: a libbean_hip.so built from the parent commit (the sequential baseline)")
-    if a.reps < 5:
-        sys.exit("--reps: at least five repetitions")
-    new, old = Worker(), Worker(a.parent_lib)
-    rows = []
-    try:
-        for i, (label, guides, reps, fam, kw) in enumerate(SHAPES):
-            k = LMAX + 1
-            times = {"batched": [], "sequential": []}
-            # untimed: builds engines, captures graphs
-            meta = new.ask(op="time", shape=i, steps=200, capacity=a.steps, mode="batched")
-            old.ask(op="time", shape=i, steps=200, capacity=a.steps, mode="sequential")
-            for rep in range(a.reps):
-                r1 = new.ask(op="time", shape=i, steps=a.steps, capacity=a.steps, mode="batched")
-                r2 = old.ask(op="time", shape=i, steps=a.steps, capacity=a.steps, mode="sequential")
-                assert r1["finite"] and r2["finite"], label
-                times["batched"].append(r1["wall_s"])
-                times["sequential"].append(r2["wall_s"])
-            e, q = stats(times["batched"]), stats(times["sequential"])
-            spread = max(e["max"] - e["min"], q["max"] - q["min"])
-            row = {
-                "shape": label, "guides": guides, "replicates": reps, "family": fam, "engine_kw": kw, "members": k,
-                "steps": a.steps, "batched_wall_s": e, "sequential_parent_wall_s": q,
-                "speedup_median": q["median"] / e["median"],
-                "gain_s": q["median"] - e["median"], "larger_min_max_spread_s": spread,
-                "faster_by_more_than_the_spread": (q["median"] - e["median"]) > spread,
-                "waves_per_simd": waves_per_simd(guides, reps, meta["targets"], k, meta["cus"]),
-            }
-            rows.append(row)
-            print(f"{label:34s} K={k:2d}  batched {e['median']*1e3:8.1f} ms [{e['min']*1e3:.1f}, {e['max']*1e3:.1f}]  "
-                  f"{k} parent fits {q['median']*1e3:8.1f} ms [{q['min']*1e3:.1f}, {q['max']*1e3:.1f}]  "
-                  f"x{row['speedup_median']:.2f}", flush=True)
-    finally:
-        new.close()
-        old.close()
-    met = all(r["faster_by_more_than_the_spread"] for r in rows)
-    out = {"what": "guide jackknife, 1 + Lmax masked fits as members of one engine (this build) vs the same fits in a row "
-                   "(parent build), wall time per fit-set",
-           "steps_per_fit": a.steps, "window": WINDOW, "repetitions": a.reps, "seed": SEED, "rows": rows,
-           "condition_met_at_every_shape": bool(met)}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        json.dump(out, fh, indent=1)
-    print(f"faster than the parent's fits in a row by more than the spread at every shape: {'yes' if met else 'NO'}; wrote {a.out}")
+def rows_of_shape(a, new, old, i, shape):
+    return [mt.jackknife_row(a, i, shape, [("batched", new, {"mode": "batched"}), ("sequential", old, {"mode": "sequential"})])]
 
 
 if __name__ == "__main__":
-    main()
+    mt.main(__file__, "guide_jackknife_small_screens.json", lambda: mt.serve(SHAPES, build, seeds_of), rows_of_shape, SHAPES,
+            lambda a, rows: mt.jackknife_summary(a, rows, WHAT))

@@ -13,61 +13,20 @@ import torch
 
 import bean_amd  # noqa: F401
 from bean_amd import _lib
-from bean_amd.cli.execute import get_parser
-from bean_amd.cli.execute import main as bean_main
-from bean_amd.framework import h5ad_io
 from bean_amd.preprocessing.synthetic import (make_sorting_tiling_screen, make_sorting_variant_screen,
                                                make_survival_variant_screen)
 
+import members_common
+from members_common import (CONFIGS, DEV, GOLD, STEPS, VAR, _assert_same, _h5ad_reader_present, _kw_of, _mini,  # noqa: F401
+                            _run, _state)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-VAR = os.path.join(GOLD, "var_mini_screen.h5ad")
 BW = os.path.join(GOLD, "accessibility_signal_chr6.bw")
 SEEDS = (101, 7, 2_000_000_011)
-STEPS = 300
-
-
-@pytest.fixture(autouse=True)
-def _h5ad_reader_present():
-    try:
-        import h5py  # noqa: F401
-    except ImportError:
-        assert os.path.exists(h5ad_io.HELPER_PYTHON), "no h5py helper interpreter: .h5ad screens cannot be read here"
-
-
-def _mini(tmp_path, *extra):
-    from bean_amd.cli import run as cli_run
-
-    args = get_parser().parse_args(["run", "sorting", "variant", VAR, *extra, "-o", str(tmp_path), "--sample-mask-col", ""])
-    return cli_run.main(args, return_data=True)
-
-
-def _state(eng, member=None):
-    pick = (lambda t: t) if member is None else (lambda t: t[member])
-    out = {f"p.{k}": pick(v).clone() for k, v in eng.unconstrained.items()}
-    out.update({f"m.{k}": pick(v).clone() for k, v in eng._m.items()})
-    out.update({f"v.{k}": pick(v).clone() for k, v in eng._v.items()})
-    out["loss"] = pick(eng.loss_hist)[: eng.steps_done].clone()
-    return out
 
 
 def _single(family, data, seed, kw, steps=STEPS, **run_kw):
-    from bean_amd import engine
-
-    eng = engine.HipSVI(family, data, num_steps=STEPS, **kw)
-    eng.run(steps, seed=seed, **run_kw)
-    torch.cuda.synchronize()
-    st = _state(eng)
-    eng.close()
-    return st
-
-
-def _assert_same(got, want, what):
-    assert set(got) == set(want), what
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, (got[k].double() - want[k].double()).abs().max().item())
+    return members_common._single(family, data, kw, seed=seed, steps=steps, **run_kw)
 
 
 def _check_members(family, data, kw, seeds=SEEDS):
@@ -87,32 +46,6 @@ def _check_members(family, data, kw, seeds=SEEDS):
     for k, seed in enumerate(seeds):
         _assert_same(members[k], _single(family, data, seed, kw), f"{family} {kw} member {k} (seed {seed})")
     assert not torch.equal(members[0]["p.mu_loc"], members[1]["p.mu_loc"])
-
-
-def _priors(data):
-    t = data.n_targets
-    g = torch.Generator().manual_seed(5)
-    return {"mu_loc": 0.2 * torch.randn(t, 1, generator=g), "mu_scale": 0.5 + torch.rand(t, 1, generator=g),
-            "sd_loc": 0.1 * torch.randn(t, 1, generator=g), "sd_scale": 0.05 + 0.1 * torch.rand(t, 1, generator=g)}
-
-
-CONFIGS = [
-    ("Normal", dict()),
-    ("Normal", dict(use_bcmatch=False)),
-    ("MixtureNormal", dict()),
-    ("MixtureNormal", dict(use_bcmatch=False)),
-    ("MixtureNormal", dict(scale_by_accessibility=True, fit_noise=True)),
-    ("MixtureNormal", dict(scale_by_accessibility=True, fit_noise=False)),
-    ("MixtureNormal", dict(prior="yes")),
-    ("Normal", dict(prior="yes")),
-]
-
-
-def _kw_of(kw, data):
-    kw = dict(kw)
-    if kw.pop("prior", None):
-        kw["prior_params"] = _priors(data)
-    return kw
 
 
 @pytest.mark.parametrize("family,kw", CONFIGS)
@@ -338,13 +271,6 @@ def test_run_inference_ensemble_halts_naming_the_member(tmp_path, monkeypatch):
     assert dump["member"] == 0 and dump["seed"] == 101 and "mu_loc" in dump["param"]
     for k, v in dump["param"].items():
         assert torch.isfinite(v).all(), k
-
-
-def _run(out, *argv):
-    os.makedirs(out)
-    assert bean_main(["run", *argv, "-o", out, "--sample-mask-col", ""]) == 0
-    (d,) = [os.path.join(out, p) for p in os.listdir(out) if p.startswith("bean_run_result.")]
-    return d
 
 
 def test_cli_n_seeds(tmp_path):

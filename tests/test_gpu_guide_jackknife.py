@@ -13,64 +13,17 @@ import pytest
 import torch
 
 import bean_amd  # noqa: F401
-from bean_amd.cli.execute import get_parser
-from bean_amd.cli.execute import main as bean_main
-from bean_amd.framework import h5ad_io
 from bean_amd.model.jackknife import guides_at_position, guide_member_masks, guide_positions, leave_out_guides
 from bean_amd.preprocessing.synthetic import (make_sorting_tiling_screen, make_sorting_variant_screen,
                                                make_survival_variant_screen)
 
+from members_common import (DEV, SEED, STEPS, VAR, _assert_same, _h5ad_reader_present, _kw_of, _mini, _run,  # noqa: F401
+                            _same_results, _single, _state)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-VAR = os.path.join(GOLD, "var_mini_screen.h5ad")
-SEED = 101
-STEPS = 300
 ELEMENT_COLUMNS = ["mu_gjk_se", "mu_gjk_max_shift", "mu_gjk_max_shift_guide", "n_gjk"]
 PER_TARGET = ("mu_loc", "mu_scale", "sd_loc", "sd_scale")
 PER_GUIDE = ("alpha_pi", "noise_loc", "noise_scale")
-
-
-@pytest.fixture(autouse=True)
-def _h5ad_reader_present():
-    try:
-        import h5py  # noqa: F401
-    except ImportError:
-        assert os.path.exists(h5ad_io.HELPER_PYTHON), "no h5py helper interpreter: .h5ad screens cannot be read here"
-
-
-def _state(eng, member=None):
-    pick = (lambda t: t) if member is None else (lambda t: t[member])
-    out = {f"p.{k}": pick(v).clone() for k, v in eng.unconstrained.items()}
-    out.update({f"m.{k}": pick(v).clone() for k, v in eng._m.items()})
-    out.update({f"v.{k}": pick(v).clone() for k, v in eng._v.items()})
-    out["loss"] = pick(eng.loss_hist)[: eng.steps_done].clone()
-    return out
-
-
-def _single(family, data, kw):
-    from bean_amd import engine
-
-    eng = engine.HipSVI(family, data, num_steps=STEPS, **kw)
-    eng.run(STEPS, seed=SEED)
-    torch.cuda.synchronize()
-    st = _state(eng)
-    eng.close()
-    return st
-
-
-def _assert_same(got, want, what):
-    assert set(got) == set(want), what
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, (got[k].double() - want[k].double()).abs().max().item())
-
-
-def _priors(data):
-    t = data.n_targets
-    g = torch.Generator().manual_seed(5)
-    return {"mu_loc": 0.2 * torch.randn(t, 1, generator=g), "mu_scale": 0.5 + torch.rand(t, 1, generator=g),
-            "sd_loc": 0.1 * torch.randn(t, 1, generator=g), "sd_scale": 0.05 + 0.1 * torch.rand(t, 1, generator=g)}
 
 
 CONFIGS = {
@@ -80,13 +33,6 @@ CONFIGS = {
     "MixtureNormal+Acc": ("MixtureNormal", dict(scale_by_accessibility=True, fit_noise=False)),
     "MixtureNormal+prior": ("MixtureNormal", dict(prior="yes")),
 }
-
-
-def _kw_of(kw, data):
-    kw = dict(kw)
-    if kw.pop("prior", None):
-        kw["prior_params"] = _priors(data)
-    return kw
 
 
 @functools.lru_cache(maxsize=None)
@@ -152,13 +98,6 @@ def test_member_is_the_single_fit_with_its_masks(config):
     # same seed, other data: the members differ from the full fit and from each other
     assert not torch.equal(states[0]["p.mu_loc"], states[1]["p.mu_loc"])
     assert not torch.equal(states[1]["p.mu_loc"], states[2]["p.mu_loc"])
-
-
-def _mini(tmp_path, *extra):
-    from bean_amd.cli import run as cli_run
-
-    args = get_parser().parse_args(["run", "sorting", "variant", VAR, *extra, "-o", str(tmp_path), "--sample-mask-col", ""])
-    return cli_run.main(args, return_data=True)
 
 
 @pytest.mark.parametrize("extra,family", [([], "MixtureNormal"), (["--uniform-edit"], "Normal")])
@@ -230,14 +169,6 @@ def test_untouched_targets_keep_the_full_fits_bits(config):
 
 
 # ---------------------------------------------------------------- run_inference_guide_jackknife
-def _same_results(got, want):
-    store, out = got
-    ref_store, ref = want
-    assert set(out) == {"loss", "params"} and out["loss"] == ref["loss"]
-    assert set(out["params"]) == set(ref["params"]) == set(store.keys())
-    for k, v in ref["params"].items():
-        assert out["params"][k].device.type == "cpu" and torch.equal(out["params"][k], v), k
-        assert torch.equal(store[k].cpu(), ref_store[k].cpu()), k
 
 
 def test_run_inference_guide_jackknife_batched_fallback_and_tiling(tmp_path, monkeypatch):
@@ -334,11 +265,6 @@ def test_halt_names_the_position(tmp_path, monkeypatch):
 
 
 # ---------------------------------------------------------------- CLI
-def _run(out, *argv):
-    os.makedirs(out)
-    assert bean_main(["run", *argv, "-o", out, "--sample-mask-col", ""]) == 0
-    (d,) = [os.path.join(out, p) for p in os.listdir(out) if p.startswith("bean_run_result.")]
-    return d
 
 
 def test_cli_jackknife_guides(tmp_path):

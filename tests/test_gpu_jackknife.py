@@ -2,9 +2,7 @@
 masks - parameters, both moments and the loss history - for every sorting variant family the batched kernels take, in
 windows, eagerly and across a second prepare; the per-member loss constants; the C entry point's rejections; the
 fallback for the other families; the CLI.  -m gpu."""
-import csv
 import ctypes
-import io
 import os
 import pickle
 from functools import partial
@@ -16,54 +14,15 @@ import torch
 
 import bean_amd  # noqa: F401
 from bean_amd import _lib
-from bean_amd.cli.execute import main as bean_main
-from bean_amd.framework import h5ad_io
 from bean_amd.model.jackknife import candidate_replicates, leave_out, member_masks
 from bean_amd.preprocessing.synthetic import (make_sorting_tiling_screen, make_sorting_variant_screen,
                                                make_survival_variant_screen)
 
+from members_common import (CONFIGS, DEV, SEED, STEPS, VAR, _assert_same, _h5ad_reader_present, _kw_of, _run,  # noqa: F401
+                            _same_results, _single, _state, _without_columns)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-VAR = os.path.join(GOLD, "var_mini_screen.h5ad")
-SEED = 101
-STEPS = 300
 COLUMNS = ["mu_jk_se", "mu_jk_max_shift", "mu_jk_max_shift_rep", "n_jk"]
-
-
-@pytest.fixture(autouse=True)
-def _h5ad_reader_present():
-    try:
-        import h5py  # noqa: F401
-    except ImportError:
-        assert os.path.exists(h5ad_io.HELPER_PYTHON), "no h5py helper interpreter: .h5ad screens cannot be read here"
-
-
-def _state(eng, member=None):
-    pick = (lambda t: t) if member is None else (lambda t: t[member])
-    out = {f"p.{k}": pick(v).clone() for k, v in eng.unconstrained.items()}
-    out.update({f"m.{k}": pick(v).clone() for k, v in eng._m.items()})
-    out.update({f"v.{k}": pick(v).clone() for k, v in eng._v.items()})
-    out["loss"] = pick(eng.loss_hist)[: eng.steps_done].clone()
-    return out
-
-
-def _single(family, data, kw, seed=SEED, steps=STEPS):
-    from bean_amd import engine
-
-    eng = engine.HipSVI(family, data, num_steps=STEPS, **kw)
-    eng.run(steps, seed=seed)
-    torch.cuda.synchronize()
-    st = _state(eng)
-    eng.close()
-    return st
-
-
-def _assert_same(got, want, what):
-    assert set(got) == set(want), what
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, (got[k].double() - want[k].double()).abs().max().item())
 
 
 def _screens(data):
@@ -99,32 +58,6 @@ def _check_members(family, data, kw):
     # same seed, other data: the members differ from the full fit and from each other
     assert not torch.equal(members[0]["p.mu_loc"], members[1]["p.mu_loc"])
     assert not torch.equal(members[1]["p.mu_loc"], members[2]["p.mu_loc"])
-
-
-def _priors(data):
-    t = data.n_targets
-    g = torch.Generator().manual_seed(5)
-    return {"mu_loc": 0.2 * torch.randn(t, 1, generator=g), "mu_scale": 0.5 + torch.rand(t, 1, generator=g),
-            "sd_loc": 0.1 * torch.randn(t, 1, generator=g), "sd_scale": 0.05 + 0.1 * torch.rand(t, 1, generator=g)}
-
-
-CONFIGS = [
-    ("Normal", dict()),
-    ("Normal", dict(use_bcmatch=False)),
-    ("MixtureNormal", dict()),
-    ("MixtureNormal", dict(use_bcmatch=False)),
-    ("MixtureNormal", dict(scale_by_accessibility=True, fit_noise=True)),
-    ("MixtureNormal", dict(scale_by_accessibility=True, fit_noise=False)),
-    ("MixtureNormal", dict(prior="yes")),
-    ("Normal", dict(prior="yes")),
-]
-
-
-def _kw_of(kw, data):
-    kw = dict(kw)
-    if kw.pop("prior", None):
-        kw["prior_params"] = _priors(data)
-    return kw
 
 
 def _ragged(**kw):
@@ -316,16 +249,6 @@ def test_rejections_leave_the_handle_usable():
     til.close()
 
 
-def _same_results(got, want):
-    store, out = got
-    ref_store, ref = want
-    assert set(out) == {"loss", "params"} and out["loss"] == ref["loss"]
-    assert set(out["params"]) == set(ref["params"]) == set(store.keys())
-    for k, v in ref["params"].items():
-        assert out["params"][k].device.type == "cpu" and torch.equal(out["params"][k], v), k
-        assert torch.equal(store[k].cpu(), ref_store[k].cpu()), k
-
-
 def test_run_inference_jackknife_batched_and_fallback(tmp_path, monkeypatch):
     from bean_amd import engine
     from bean_amd.model import model as m
@@ -409,24 +332,6 @@ def test_run_inference_jackknife_halts_naming_the_left_out_replicate(tmp_path, m
     assert dump["left_out"] == 2 and dump["seed"] == 101 and "mu_loc" in dump["param"]
     for k, v in dump["param"].items():
         assert torch.isfinite(v).all(), k
-
-
-def _run(out, *argv):
-    os.makedirs(out)
-    assert bean_main(["run", *argv, "-o", out, "--sample-mask-col", ""]) == 0
-    (d,) = [os.path.join(out, p) for p in os.listdir(out) if p.startswith("bean_run_result.")]
-    return d
-
-
-def _without_columns(path, names):
-    """The CSV file's bytes with the named columns cut out, field text untouched."""
-    with open(path, newline="") as fh:
-        rows = list(csv.reader(fh))
-    keep = [i for i, c in enumerate(rows[0]) if c not in names]
-    assert len(keep) == len(rows[0]) - len(names)
-    buf = io.StringIO()
-    csv.writer(buf, lineterminator="\n").writerows([[row[i] for i in keep] for row in rows])
-    return buf.getvalue().encode()
 
 
 def test_cli_jackknife_replicates(tmp_path):

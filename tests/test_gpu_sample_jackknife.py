@@ -4,10 +4,7 @@ batched kernels take; the masks alone do not give that fit; windows, eager launc
 shared counts; the C entry point's rejections; run_inference_sample_jackknife batched, in several runs and in its
 fallback; the CLI; and a planted bad sample that the influence table puts first.  -m gpu."""
 import copy
-import csv
 import ctypes
-import importlib.util
-import io
 import os
 import pickle
 from functools import partial
@@ -19,66 +16,20 @@ import torch
 
 import bean_amd  # noqa: F401
 from bean_amd import _lib
-from bean_amd.cli.execute import get_parser
-from bean_amd.cli.execute import main as bean_main
-from bean_amd.framework import h5ad_io
 from bean_amd.model.jackknife import (leave_out_samples, sample_groups, sample_jackknife_summary, sample_member_counts,
                                       sample_member_masks)
 from bean_amd.preprocessing.synthetic import (make_sorting_tiling_screen, make_sorting_variant_screen,
                                                make_survival_variant_screen)
 
+from members_common import (CONFIGS, DEV, SEED, STEPS, VAR, _assert_same, _h5ad_reader_present, _kw_of, _mini,  # noqa: F401
+                            _run, _same_results, _single, _state, _without_columns)
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-HERE = os.path.dirname(os.path.abspath(__file__))
-VAR = os.path.join(HERE, "golden", "var_mini_screen.h5ad")
-SEED = 101
-STEPS = 300
 COLUMNS = ["mu_sjk_max_shift", "mu_sjk_max_shift_sample", "n_sjk"]
-
-# the configurations of the replicate jackknife's tests, as that file lists them
-_spec = importlib.util.spec_from_file_location("_replicate_jackknife_tests", os.path.join(HERE, "test_gpu_jackknife.py"))
-_rjk = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(_rjk)
-CONFIGS, _kw_of = _rjk.CONFIGS, _rjk._kw_of
-
-
-@pytest.fixture(autouse=True)
-def _h5ad_reader_present():
-    try:
-        import h5py  # noqa: F401
-    except ImportError:
-        assert os.path.exists(h5ad_io.HELPER_PYTHON), "no h5py helper interpreter: .h5ad screens cannot be read here"
-
-
-def _state(eng, member=None):
-    pick = (lambda t: t) if member is None else (lambda t: t[member])
-    out = {f"p.{k}": pick(v).clone() for k, v in eng.unconstrained.items()}
-    out.update({f"m.{k}": pick(v).clone() for k, v in eng._m.items()})
-    out.update({f"v.{k}": pick(v).clone() for k, v in eng._v.items()})
-    out["loss"] = pick(eng.loss_hist)[: eng.steps_done].clone()
-    return out
-
-
-def _single(family, data, kw, seed=SEED, steps=STEPS):
-    from bean_amd import engine
-
-    eng = engine.HipSVI(family, data, num_steps=STEPS, **kw)
-    eng.run(steps, seed=seed)
-    torch.cuda.synchronize()
-    st = _state(eng)
-    eng.close()
-    return st
 
 
 def _same(got, want):
     return set(got) == set(want) and all(got[k].shape == want[k].shape and torch.equal(got[k], want[k]) for k in want)
-
-
-def _assert_same(got, want, what):
-    assert set(got) == set(want), what
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert torch.equal(got[k], want[k]), (what, k, (got[k].double() - want[k].double()).abs().max().item())
 
 
 def _counts(data, groups, kw):
@@ -136,13 +87,6 @@ def test_member_is_the_single_fit_by_condition_ragged_tiles(family, kw):
     data = make_sorting_variant_screen(1003, 3, seed=9, guides_per_target=7,
                                        with_accessibility=bool(kw.get("scale_by_accessibility")))
     assert _check_members(family, data, _kw_of(kw, data), "condition") == 1 + data.n_condits
-
-
-def _mini(tmp_path, *extra):
-    from bean_amd.cli import run as cli_run
-
-    args = get_parser().parse_args(["run", "sorting", "variant", VAR, *extra, "-o", str(tmp_path), "--sample-mask-col", ""])
-    return cli_run.main(args, return_data=True)
 
 
 @pytest.mark.parametrize("extra,family", [([], "MixtureNormal"), (["--uniform-edit"], "Normal")])
@@ -304,14 +248,6 @@ def test_rejections_leave_the_handle_usable():
 
 
 # ---------------------------------------------------------------- run_inference_sample_jackknife
-def _same_results(got, want):
-    store, out = got
-    ref_store, ref = want
-    assert set(out) == {"loss", "params"} and out["loss"] == ref["loss"]
-    assert set(out["params"]) == set(ref["params"]) == set(store.keys())
-    for k, v in ref["params"].items():
-        assert out["params"][k].device.type == "cpu" and torch.equal(out["params"][k], v), k
-        assert torch.equal(store[k].cpu(), ref_store[k].cpu()), k
 
 
 def _as_run_inference(res, model, guide, data, n, by):
@@ -423,22 +359,6 @@ def test_run_inference_sample_jackknife_halts_naming_the_left_out_sample(tmp_pat
 
 
 # ---------------------------------------------------------------- CLI
-def _run(out, *argv):
-    os.makedirs(out)
-    assert bean_main(["run", *argv, "-o", out, "--sample-mask-col", ""]) == 0
-    (d,) = [os.path.join(out, p) for p in os.listdir(out) if p.startswith("bean_run_result.")]
-    return d
-
-
-def _without_columns(path, names):
-    """The CSV file's bytes with the named columns cut out, field text untouched."""
-    with open(path, newline="") as fh:
-        rows = list(csv.reader(fh))
-    keep = [i for i, c in enumerate(rows[0]) if c not in names]
-    assert len(keep) == len(rows[0]) - len(names)
-    buf = io.StringIO()
-    csv.writer(buf, lineterminator="\n").writerows([[row[i] for i in keep] for row in rows])
-    return buf.getvalue().encode()
 
 
 def test_cli_jackknife_samples(tmp_path):
