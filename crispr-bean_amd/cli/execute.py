@@ -53,6 +53,12 @@ def get_parser():
                           "--jackknife-replicates, --jackknife-guides, --n-seeds > 1 or --load-existing.")
     own.add_argument("--jackknife-conditions", dest="jackknife_conditions", action="store_true",
                      help="As --jackknife-samples, leaving out one condition (that bin of every replicate) per fit.")
+    own.add_argument("--num-particles", dest="num_particles", type=_positive_int, default=1,
+                     help="Draw every latent site this many times in each step of the main model's fit and update with the "
+                          "mean of the gradients (Pyro's Trace_ELBO(num_particles=P); default 1, the reference's single "
+                          "draw): one fit and the usual tables, with less gradient noise.  The --fit-negctrl fit of the "
+                          "negative controls stays at one particle.  At most 64; not combined with --n-seeds > 1, any "
+                          "--jackknife-* flag or --load-existing.")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))
@@ -64,10 +70,11 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    from .run import member_mode
+    from .run import member_mode, particle_count
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
+    particle_count(args, parser.error)
 
 
 def main(argv=None):

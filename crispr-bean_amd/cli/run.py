@@ -102,6 +102,34 @@ def member_mode(args, fail=_refuse, only=None, parser_rules=None):
     return mode
 
 
+_PARTICLES_ONE_FIT = ("--num-particles averages draws inside one fit and does not combine with {other}: particles inside "
+                      "member sets are not batched.")
+_PARTICLES_NEED_FIT = "--num-particles needs the fit itself and does not combine with --load-existing."
+_PARTICLES_MAX = "--num-particles is at most {most}."
+
+
+def particle_count(args, fail=_refuse) -> int:
+    """``--num-particles``: the draws per step of the main model's fit.  More than one is refused - ``fail(sentence)``,
+    as ``member_mode`` - next to a member set (``--n-seeds`` > 1, any ``--jackknife-*``), with ``--load-existing`` and
+    above ``MAX_MEMBERS``."""
+    from .._lib import MAX_MEMBERS
+
+    n = int(getattr(args, "num_particles", 1) or 1)
+    if n < 1:
+        fail(f"--num-particles must be >= 1, got {n}.")
+    if n == 1:
+        return 1
+    is_set = lambda attr: _IS_SET.get(attr, lambda a: bool(getattr(a, attr, False)))(args)  # noqa: E731
+    for attr in ("n_seeds",) + tuple(attr for attr, _, _ in MEMBER_FLAGS):
+        if is_set(attr):
+            fail(_PARTICLES_ONE_FIT.format(other="--" + attr.replace("_", "-")))
+    if is_set("load_existing"):
+        fail(_PARTICLES_NEED_FIT)
+    if n > MAX_MEMBERS:
+        fail(_PARTICLES_MAX.format(most=MAX_MEMBERS))
+    return n
+
+
 def check_guide_jackknife_switches(args) -> bool:
     """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
     return member_mode(args, only=("jackknife_guides",)) == "guides"
@@ -256,6 +284,7 @@ def main(args, return_data=False):
 
     info(f"Running inference for {model_label}...")
     mode = member_mode(args)
+    n_particles = particle_count(args)
     table_columns = {}
     save_dict = dict()
     param_history_dict_negctrl = None
@@ -292,7 +321,9 @@ def main(args, return_data=False):
             save_dict.update(save_dict_model)
             save_dict[key] = saved
         else:
-            param_history_dict, save_dict_model = deepcopy(run_inference(model, guide, ndata, num_steps=args.n_iter))
+            particles = dict(num_particles=n_particles) if n_particles > 1 else {}
+            param_history_dict, save_dict_model = deepcopy(
+                run_inference(model, guide, ndata, num_steps=args.n_iter, **particles))
             save_dict.update(save_dict_model)
     if rank != 0:
         return prefix

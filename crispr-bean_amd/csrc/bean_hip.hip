@@ -6,7 +6,8 @@
 //   launches             launch_timed, launch_param, launch_guide and its forms, set_step / finalize, elbo_grad / adam
 //   stepping             what the entry points share (begin_steps / first_draw / mark_resumable, the noise predicates,
 //                        capture_graph / build_ladder / replay_pairs), the whole-call launches (k_svi_tile,
-//                        k_svi_async), then bean_hip_svi_run, the seed ensemble (_run_ensemble), bean_hip_svi_resume
+//                        k_svi_async), then bean_hip_svi_run, the seed ensemble (_run_ensemble), the particle steps
+//                        (_run_particles), bean_hip_svi_resume
 //   sharded / comm       bean_hip_sharded_*, bean_hip_comm_*, bean_hip_svi_run_exchanged
 //   introspection        step_bytes, dominant_kernel*, profile, diagnostics
 // Which entry point replays which graph ladder: the table in DESIGN.md, section 1.
@@ -132,6 +133,18 @@ struct bean_hip_ctx {
     // member reads the shared BEAN_BUF_X / BEAN_BUF_X_BC
     const float* member_x;
     const float* member_xbc;
+    // multi-particle SVI (bean_particles.hpp): P draws per step, one update with their mean gradient.  The particles are
+    // members that share the caller's single-fit parameters and moments; particle p >= 1 has the p-th private copy of the
+    // workspace (member_ws), of tsum_buf and of loss_acc, and every particle row p of particle_grad and particle_loss
+    int n_particles;
+    bool particles_set;        // bean_hip_set_particles has been called
+    float* particle_grad;      // per parameter array a (P, n) float32 block, the arrays end to end (particle_arrays)
+    double* particle_loss;     // (P, loss_capacity) losses of the particles; the caller's loss_hist holds their mean
+    DevArgs* particles_dev;    // device: DevArgs of the P particles
+    std::vector<DevArgs> particles_host;
+    std::vector<uint64_t> particle_seeds;
+    bool particles_dirty;      // particles_dev is older than the bound buffers / the seeds
+    std::vector<hipGraphExec_t> graphs_part;  // [k]: 2^k particle steps (four launches each)
 };
 
 extern "C" const char* bean_hip_version(void) {
@@ -317,7 +330,9 @@ static void drop_graph(bean_hip_ctx* c) {
     destroy_graphs(c->graphs_xchg);
     destroy_graphs(c->graphs_resume);
     destroy_graphs(c->graphs_ens);
+    destroy_graphs(c->graphs_part);
     c->members_dirty = true;
+    c->particles_dirty = true;
     c->resume_ok = false;  // (called whenever a buffer, the shape-dependent state or the seed changes)
 }
 
@@ -437,6 +452,12 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
     c->member_smask = nullptr;
     c->member_x = nullptr;
     c->member_xbc = nullptr;
+    c->n_particles = 1;
+    c->particles_set = false;
+    c->particle_grad = nullptr;
+    c->particle_loss = nullptr;
+    c->particles_dev = nullptr;
+    c->particles_dirty = true;
     c->loss_acc = nullptr;
     c->profile = false;
     c->profile_param = false;
@@ -732,6 +753,9 @@ extern "C" int bean_hip_destroy(bean_hip_ctx* c) {
     if (c->loss_acc) (void)hipFree(c->loss_acc);
     if (c->member_ws) (void)hipFree(c->member_ws);
     if (c->members_dev) (void)hipFree(c->members_dev);
+    if (c->particle_grad) (void)hipFree(c->particle_grad);
+    if (c->particle_loss) (void)hipFree(c->particle_loss);
+    if (c->particles_dev) (void)hipFree(c->particles_dev);
     delete c;
     return 0;
 }
@@ -748,11 +772,19 @@ extern "C" int bean_hip_bind(bean_hip_ctx* c, int slot, void* ptr, uint64_t nbyt
             if (nbytes < 8 || nbytes % 8) return fail("bean_hip_bind: loss_hist must hold >= 1 double");
             if (nbytes % (8 * K)) return fail("bean_hip_bind: loss_hist of " + std::to_string(K) + " members is (members, capacity) doubles");
             // (the accumulators of all members in one allocation, member-major like loss_hist itself)
+            // (particles: the caller's loss_hist keeps its single-fit size, the library owns the particles' rows)
+            const uint64_t Pn = (uint64_t)c->n_particles;
             if (nbytes / 8 / K != c->loss_capacity || !c->loss_acc) {
                 if (c->loss_acc) (void)hipFree(c->loss_acc);
                 c->loss_acc = nullptr;
-                HIP_OK(hipMalloc((void**)&c->loss_acc, (nbytes / 8) * kLossSub * kLossWords * sizeof(long long)));
-                HIP_OK(hipMemset(c->loss_acc, 0, (nbytes / 8) * kLossSub * kLossWords * sizeof(long long)));
+                HIP_OK(hipMalloc((void**)&c->loss_acc, (nbytes / 8) * Pn * kLossSub * kLossWords * sizeof(long long)));
+                HIP_OK(hipMemset(c->loss_acc, 0, (nbytes / 8) * Pn * kLossSub * kLossWords * sizeof(long long)));
+                if (c->particle_loss) (void)hipFree(c->particle_loss);
+                c->particle_loss = nullptr;
+                if (c->particles_set) {
+                    HIP_OK(hipMalloc((void**)&c->particle_loss, (nbytes / 8) * Pn * sizeof(double)));
+                    HIP_OK(hipMemset(c->particle_loss, 0, (nbytes / 8) * Pn * sizeof(double)));
+                }
             }
             c->loss_capacity = nbytes / 8 / K;
         } else if (slot >= BEAN_BUF_P_MU_LOC && slot < BEAN_BUF_V_MU_LOC + 16 && nbytes != want * K) {
@@ -813,6 +845,9 @@ static int check_bound(bean_hip_ctx* c, bool need_grads, bool need_moments) {
 }
 
 static int upload_members(bean_hip_ctx* c, const uint64_t* seeds, hipStream_t stream);
+// private copies of everything a step writes: one per ensemble member or per particle (the two exclude each other)
+static int n_copies(const bean_hip_ctx* c) { return c->n_members > 1 ? c->n_members : c->n_particles; }
+static int alloc_workspace_copies(bean_hip_ctx* c, int n);
 
 extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
     if (!c) return fail("bean_hip_prepare: null handle");
@@ -857,7 +892,7 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
             c->d.tsum_direct = (!c->d.wide_targets && c->shape.max_target_len >= 1 && c->shape.max_target_len <= 64) ? 1 : 0;
             const size_t n_sum1 = c->d.tsum_direct ? (size_t)2 * c->d.R * 2 * c->d.T : (size_t)2 * c->d.R * c->d.n_tiles * nt;
             c->tsum_stride = n_sum1;
-            const size_t n_sum = n_sum1 * (size_t)c->n_members;  // (an ensemble: one part per member)
+            const size_t n_sum = n_sum1 * (size_t)n_copies(c);  // (an ensemble: one part per member; particles alike)
             if (c->tsum_buf) (void)hipFree(c->tsum_buf);
             c->tsum_buf = nullptr;
             HIP_OK(hipMalloc((void**)&c->tsum_buf, n_sum * sizeof(double)));
@@ -978,10 +1013,10 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         }
     }
 #endif
-    if (c->n_members > 1) {
-        // every member's private workspace starts as a copy of the one just prepared: the data-only parts (the
-        // constant, the bin edges, the accessibility factors, the kPNrg row) are then there for all of them
-        for (int k = 1; k < c->n_members; ++k)
+    if (n_copies(c) > 1 || c->particles_set) {
+        // every member's (particle's) private workspace starts as a copy of the one just prepared: the data-only parts
+        // (the constant, the bin edges, the accessibility factors, the kPNrg row) are then there for all of them
+        for (int k = 1; k < n_copies(c); ++k)
             HIP_OK(hipMemcpyAsync(c->member_ws + (size_t)(k - 1) * c->member_ws_stride, c->workspace, c->workspace_bytes,
                                   hipMemcpyDeviceToDevice, stream));
         const size_t lds = guide_wave2_lds(c->d.B, c->d.tile_targets);
@@ -1815,14 +1850,14 @@ extern "C" int bean_hip_set_members(bean_hip_ctx* c, int32_t n_members) {
         return fail("bean_hip_set_members: the batched kernels do not take this shape (bean_hip_ensemble_supported): "
                     "fit its seeds one after the other");
     if (c->bound_any) return fail("bean_hip_set_members: call it after bean_hip_create and before any bean_hip_bind");
+    if (n_members > 1 && c->n_particles > 1)
+        return fail("bean_hip_set_members: this handle steps " + std::to_string(c->n_particles) +
+                    " particles (bean_hip_set_particles): particles inside member sets are not batched");
     static_assert(BEAN_HIP_MAX_MEMBERS == kEnsembleMaxMembers, "the header's cap is the kernels'");
-    if (c->member_ws) (void)hipFree(c->member_ws);
-    c->member_ws = nullptr;
     if (c->members_dev) (void)hipFree(c->members_dev);
     c->members_dev = nullptr;
     c->n_members = 1;
-    c->member_ws_stride = (size_t)((c->workspace_bytes + 255) / 256 * 256);
-    if (n_members > 1) HIP_OK(hipMalloc((void**)&c->member_ws, (size_t)(n_members - 1) * c->member_ws_stride));
+    if (c->n_particles == 1 && alloc_workspace_copies(c, n_members)) return -1;
     HIP_OK(hipMalloc((void**)&c->members_dev, (size_t)n_members * sizeof(DevArgs)));
     c->n_members = n_members;
     c->members_set = true;
@@ -1833,6 +1868,36 @@ extern "C" int bean_hip_set_members(bean_hip_ctx* c, int32_t n_members) {
     c->member_seeds.clear();
     c->prepared = false;
     drop_graph(c);
+    return 0;
+}
+
+// What members and particles share.  m is a copy of c->d: every pointer into the workspace moves to the k-th private
+// copy of it (k >= 1), tsum and the loss accumulators to their k-th part (the one list of those fields)
+static void relocate_private(const bean_hip_ctx* c, DevArgs& m, int k) {
+    const char* w0 = (const char*)c->workspace;
+    const char* w1 = w0 + c->workspace_bytes;
+    const ptrdiff_t off = (c->member_ws + (size_t)(k - 1) * c->member_ws_stride) - (char*)c->workspace;
+#define BEAN_WS(f)                                                                  \
+    do {                                                                            \
+        const char* q_ = (const char*)m.f;                                          \
+        if (q_ && q_ >= w0 && q_ < w1) m.f = (decltype(m.f))(const_cast<char*>(q_) + off); \
+    } while (0)
+    BEAN_WS(tabP); BEAN_WS(tabPmu); BEAN_WS(tabPy); BEAN_WS(P0); BEAN_WS(mu_t); BEAN_WS(y_t); BEAN_WS(eps_mu); BEAN_WS(eps_sd);
+    BEAN_WS(part); BEAN_WS(mu_a); BEAN_WS(sig_a); BEAN_WS(lpn); BEAN_WS(eps_noise); BEAN_WS(kacc); BEAN_WS(loss_const);
+    BEAN_WS(const_acc); BEAN_WS(tile_ctr); BEAN_WS(bnd_ctr); BEAN_WS(ue_z); BEAN_WS(ue_idx); BEAN_WS(dbg); BEAN_WS(wrow);
+    BEAN_WS(nobs); BEAN_WS(rrow); BEAN_WS(pi_ws); BEAN_WS(gpi_ws); BEAN_WS(trow); BEAN_WS(dgq); BEAN_WS(dgq_t); BEAN_WS(lpart);
+    BEAN_WS(q0_ctr); BEAN_WS(ctrA); BEAN_WS(ctrB);
+#undef BEAN_WS
+    m.loss_acc += (size_t)k * c->loss_capacity * kLossSub * kLossWords;
+    if (m.tsum) m.tsum += (size_t)k * c->tsum_stride;
+}
+
+// (n - 1) private copies of the workspace for n members or particles (filled by bean_hip_prepare)
+static int alloc_workspace_copies(bean_hip_ctx* c, int n) {
+    if (c->member_ws) (void)hipFree(c->member_ws);
+    c->member_ws = nullptr;
+    c->member_ws_stride = (size_t)((c->workspace_bytes + 255) / 256 * 256);
+    if (n > 1) HIP_OK(hipMalloc((void**)&c->member_ws, (size_t)(n - 1) * c->member_ws_stride));
     return 0;
 }
 
@@ -1852,20 +1917,7 @@ static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
         if (c->member_xbc) m.Xbc = c->member_xbc + n;
     }
     if (k == 0) return m;
-    const char* w0 = (const char*)c->workspace;
-    const char* w1 = w0 + c->workspace_bytes;
-    const ptrdiff_t off = (c->member_ws + (size_t)(k - 1) * c->member_ws_stride) - (char*)c->workspace;
-#define BEAN_WS(f)                                                                  \
-    do {                                                                            \
-        const char* q_ = (const char*)m.f;                                          \
-        if (q_ && q_ >= w0 && q_ < w1) m.f = (decltype(m.f))(const_cast<char*>(q_) + off); \
-    } while (0)
-    BEAN_WS(tabP); BEAN_WS(tabPmu); BEAN_WS(tabPy); BEAN_WS(P0); BEAN_WS(mu_t); BEAN_WS(y_t); BEAN_WS(eps_mu); BEAN_WS(eps_sd);
-    BEAN_WS(part); BEAN_WS(mu_a); BEAN_WS(sig_a); BEAN_WS(lpn); BEAN_WS(eps_noise); BEAN_WS(kacc); BEAN_WS(loss_const);
-    BEAN_WS(const_acc); BEAN_WS(tile_ctr); BEAN_WS(bnd_ctr); BEAN_WS(ue_z); BEAN_WS(ue_idx); BEAN_WS(dbg); BEAN_WS(wrow);
-    BEAN_WS(nobs); BEAN_WS(rrow); BEAN_WS(pi_ws); BEAN_WS(gpi_ws); BEAN_WS(trow); BEAN_WS(dgq); BEAN_WS(dgq_t); BEAN_WS(lpart);
-    BEAN_WS(q0_ctr); BEAN_WS(ctrA); BEAN_WS(ctrB);
-#undef BEAN_WS
+    relocate_private(c, m, k);
     for (int i = 0; i < 8; ++i) {
         const size_t n = (size_t)(expected_bytes(c->shape, BEAN_BUF_P_MU_LOC + i) / 4) * (size_t)k;
         if (m.p[i]) m.p[i] += n;
@@ -1874,8 +1926,6 @@ static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
         if (m.v[i]) m.v[i] += n;
     }
     m.loss_hist += (size_t)k * c->loss_capacity;
-    m.loss_acc += (size_t)k * c->loss_capacity * kLossSub * kLossWords;
-    if (m.tsum) m.tsum += (size_t)k * c->tsum_stride;
     return m;
 }
 
@@ -1954,21 +2004,20 @@ static int ens_kind(const bean_hip_ctx* c) {
     return (kind1 && !param_generic_only()) ? 1 : 0;
 }
 
+// (mem, K: the members of an ensemble, or the particles of a fit)
 template <bool FINISH, bool ADAM, bool PREP>
-static void launch_param_ens(bean_hip_ctx* c, hipStream_t stream) {
+static void launch_param_ens(bean_hip_ctx* c, hipStream_t stream, const DevArgs* mem, int K) {
     int ntb, nb;
     grid_param(c, ntb, nb);
-    const dim3 grid((unsigned)nb, (unsigned)c->n_members), block(kParamBlock);
-    const DevArgs* mem = c->members_dev;
+    const dim3 grid((unsigned)nb, (unsigned)K), block(kParamBlock);
     if (ens_kind(c) == 1) hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 1>), grid, block, 0, stream, mem, ntb);
     else hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 0>), grid, block, 0, stream, mem, ntb);
 }
 
-static void launch_guide_ens(bean_hip_ctx* c, hipStream_t stream) {
+static void launch_guide_ens(bean_hip_ctx* c, hipStream_t stream, const DevArgs* mem, int K) {
     const DevArgs& d = c->d;
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)c->n_members), block(64);
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)K), block(64);
     const size_t lds = guide_wave2_lds(d.B, d.tile_targets);
-    const DevArgs* mem = c->members_dev;
     with_family_acc(d, [&](auto fam, auto acc) {
         hipLaunchKernelGGL((k_guide_wave2_ens<fam(), acc()>), grid, block, lds, stream, mem);
     });
@@ -1976,9 +2025,23 @@ static void launch_guide_ens(bean_hip_ctx* c, hipStream_t stream) {
 
 static void enqueue_pairs_ens(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
     for (uint64_t i = 0; i < n; ++i) {
-        launch_param_ens<true, true, true>(c, stream);
-        launch_guide_ens(c, stream);
+        launch_param_ens<true, true, true>(c, stream, c->members_dev, c->n_members);
+        launch_guide_ens(c, stream, c->members_dev, c->n_members);
     }
+}
+
+// the loss window of the call's n_steps steps of K members (particles) to zero, their step counters to first_step
+static void launch_set_step_ens(hipStream_t stream, const DevArgs* mem, int K, uint64_t first_step, uint64_t n_steps) {
+    const uint64_t words = n_steps * kLossSub * kLossWords;
+    unsigned blocks = (unsigned)((words + 255) / 256);
+    if (blocks < 1) blocks = 1;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(k_set_step_ens, dim3(blocks, (unsigned)K), dim3(256), 0, stream, mem, (unsigned long long)first_step,
+                       (unsigned long long)first_step, (unsigned long long)n_steps);
+}
+static void launch_finalize_ens(hipStream_t stream, const DevArgs* mem, int K, uint64_t first_step, uint64_t n_steps) {
+    hipLaunchKernelGGL(k_loss_finalize_ens, dim3((unsigned)((n_steps + 3) / 4), (unsigned)K), dim3(n_steps == 1 ? 64 : 256), 0,
+                       stream, mem, (unsigned long long)first_step, (unsigned long long)n_steps, 0);
 }
 
 extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
@@ -2023,24 +2086,159 @@ extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds,
             }
         }
     }
-    {
-        const uint64_t words = n_steps * kLossSub * kLossWords;
-        unsigned blocks = (unsigned)((words + 255) / 256);
-        if (blocks < 1) blocks = 1;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(k_set_step_ens, dim3(blocks, (unsigned)K), dim3(256), 0, stream, (const DevArgs*)c->members_dev,
-                           (unsigned long long)first_step, (unsigned long long)first_step, (unsigned long long)n_steps);
-    }
-    launch_param_ens<false, false, true>(c, stream);
-    launch_guide_ens(c, stream);
+    launch_set_step_ens(stream, c->members_dev, K, first_step, n_steps);
+    launch_param_ens<false, false, true>(c, stream, c->members_dev, K);
+    launch_guide_ens(c, stream, c->members_dev, K);
     if (use_graph) {
         if (replay_pairs(c, c->graphs_ens, stream, n_steps - 1, pairs_n)) return -1;
     } else {
         enqueue_pairs_ens(c, stream, n_steps - 1);
     }
-    launch_param_ens<true, true, false>(c, stream);
-    hipLaunchKernelGGL(k_loss_finalize_ens, dim3((unsigned)((n_steps + 3) / 4), (unsigned)K), dim3(n_steps == 1 ? 64 : 256), 0,
-                       stream, (const DevArgs*)c->members_dev, (unsigned long long)first_step, (unsigned long long)n_steps, 0);
+    launch_param_ens<true, true, false>(c, stream, c->members_dev, K);
+    launch_finalize_ens(stream, c->members_dev, K, first_step, n_steps);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- multi-particle SVI (bean_particles.hpp): P draws per step in the `_ens` launches, one update with their mean
+extern "C" int bean_hip_set_particles(bean_hip_ctx* c, int32_t n_particles) {
+    if (!c) return fail("bean_hip_set_particles: null handle");
+    if (n_particles < 1 || n_particles > BEAN_HIP_MAX_MEMBERS)
+        return fail("bean_hip_set_particles: n_particles must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) + "]");
+    if (!ensemble_shape_ok(c))
+        return fail("bean_hip_set_particles: the batched kernels do not take this shape (bean_hip_ensemble_supported): "
+                    "step its particles one after the other");
+    if (c->bound_any) return fail("bean_hip_set_particles: call it after bean_hip_create and before any bean_hip_bind");
+    if (c->n_members > 1)
+        return fail("bean_hip_set_particles: this handle steps " + std::to_string(c->n_members) +
+                    " members (bean_hip_set_members): particles inside member sets are not batched");
+    if (c->particle_grad) (void)hipFree(c->particle_grad);
+    c->particle_grad = nullptr;
+    if (c->particles_dev) (void)hipFree(c->particles_dev);
+    c->particles_dev = nullptr;
+    c->n_particles = 1;
+    c->particles_set = false;
+    if (alloc_workspace_copies(c, n_particles)) return -1;
+    uint64_t n_all = 0;
+    for (int i = 0; i < 8; ++i) n_all += expected_bytes(c->shape, BEAN_BUF_P_MU_LOC + i) / 4;
+    HIP_OK(hipMalloc((void**)&c->particle_grad, (size_t)n_all * (size_t)n_particles * sizeof(float)));
+    HIP_OK(hipMemset(c->particle_grad, 0, (size_t)n_all * (size_t)n_particles * sizeof(float)));
+    HIP_OK(hipMalloc((void**)&c->particles_dev, (size_t)n_particles * sizeof(DevArgs)));
+    c->n_particles = n_particles;
+    c->particles_set = true;
+    c->particle_seeds.clear();
+    c->prepared = false;
+    drop_graph(c);
+    return 0;
+}
+
+// the bound parameter arrays end to end, and where each one's (P, n) scratch block lies in particle_grad
+static ParticleArrays particle_arrays(const bean_hip_ctx* c) {
+    ParticleArrays a;
+    long at = 0;
+    for (int i = 0; i < 8; ++i) {
+        const long n = (long)(expected_bytes(c->shape, BEAN_BUF_P_MU_LOC + i) / 4);
+        a.p[i] = c->d.p[i];
+        a.g[i] = c->d.g[i];
+        a.m[i] = c->d.m[i];
+        a.v[i] = c->d.v[i];
+        a.scratch[i] = c->particle_grad + (size_t)at * (size_t)c->n_particles;
+        a.start[i] = at;
+        at += n;
+    }
+    a.start[8] = at;
+    return a;
+}
+
+// DevArgs of particle q: c->d - the shared parameters and moments - with everything a step writes moved to the
+// particle's own part: the workspace copy, tsum, the loss accumulators, its scratch rows, its row of losses
+static DevArgs particle_args(const bean_hip_ctx* c, int q, uint64_t seed) {
+    DevArgs m = c->d;
+    m.seed = seed;
+    m.tgrad = nullptr;
+    if (q > 0) relocate_private(c, m, q);
+    const ParticleArrays a = particle_arrays(c);
+    for (int i = 0; i < 8; ++i)
+        if (m.g[i]) m.g[i] = const_cast<float*>(a.scratch[i]) + (size_t)q * (size_t)(a.start[i + 1] - a.start[i]);
+    m.loss_hist = c->particle_loss + (size_t)q * c->loss_capacity;
+    return m;
+}
+
+static int upload_particles(bean_hip_ctx* c, const uint64_t* seeds, hipStream_t stream) {
+    const int P = c->n_particles;
+    HIP_OK(hipStreamSynchronize(stream));  // no launch in flight reads the array while it changes
+    c->particles_host.resize((size_t)P);
+    for (int q = 0; q < P; ++q) c->particles_host[(size_t)q] = particle_args(c, q, seeds[q]);
+    HIP_OK(hipMemcpyAsync(c->particles_dev, c->particles_host.data(), (size_t)P * sizeof(DevArgs), hipMemcpyHostToDevice, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+// n particle steps, four launches each; every one begins at the step counters the one before has left
+static void enqueue_particle_steps(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
+    const DevArgs* mem = c->particles_dev;
+    const int P = c->n_particles;
+    const ParticleArrays a = particle_arrays(c);
+    const unsigned blocks = (unsigned)((a.start[8] + 255) / 256);
+    for (uint64_t i = 0; i < n; ++i) {
+        launch_param_ens<false, false, true>(c, stream, mem, P);
+        launch_guide_ens(c, stream, mem, P);
+        launch_param_ens<true, false, false>(c, stream, mem, P);
+        hipLaunchKernelGGL(k_particle_adam, dim3(blocks), dim3(256), 0, stream, mem, P, a);
+    }
+}
+
+extern "C" int bean_hip_svi_run_particles(bean_hip_ctx* c, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
+                                          uint64_t n_steps, int32_t graph_chunk, void* stream_) {
+    if (!c) return fail("bean_hip_svi_run_particles: null handle");
+    if (!seeds) return fail("bean_hip_svi_run_particles: null seeds");
+    if (!c->particles_set) return fail("bean_hip_svi_run_particles: call bean_hip_set_particles first");
+    if (n_seeds != c->n_particles)
+        return fail("bean_hip_svi_run_particles: " + std::to_string(n_seeds) + " seeds for " + std::to_string(c->n_particles) +
+                    " particle(s) (bean_hip_set_particles)");
+    if (!ensemble_shape_ok(c))
+        return fail("bean_hip_svi_run_particles: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
+    if (per_step_noise(c->d) || c->d.pi_out)
+        return fail("bean_hip_svi_run_particles: injected or dumped noise belongs to single evaluations");
+    if (check_bound(c, true, true)) return -1;  // (the mean gradient goes to the bound gradient buffers)
+    const int go = begin_steps(c, "bean_hip_svi_run_particles", first_step, n_steps);
+    if (go <= 0) return go;
+    hipStream_t stream = (hipStream_t)stream_;
+    c->resume_ok = false;
+    const int P = c->n_particles;
+    bool same = !c->particles_dirty && (int)c->particle_seeds.size() == P;
+    for (int q = 0; same && q < P; ++q) same = c->particle_seeds[(size_t)q] == seeds[q];
+    if (!same) {
+        // (the launches - captured ones too - hold the ADDRESS of this array: new seeds need no new graphs)
+        if (upload_particles(c, seeds, stream)) return -1;
+        c->particle_seeds.assign(seeds, seeds + P);
+        c->particles_dirty = false;
+    }
+    const bool use_graph = graph_chunk > 0 && stream != nullptr;
+    auto steps_n = [&](uint64_t n) {
+        enqueue_particle_steps(c, stream, n);
+        return 0;
+    };
+    if (use_graph) {  // a ladder of its own, cut like the pair paths': graphs of 1, 2, 4, ... <= graph_chunk steps
+        const int n_rungs = top_rung(graph_chunk, 1, 10) + 1;
+        if ((int)c->graphs_part.size() != n_rungs) {
+            destroy_graphs(c->graphs_part);
+            if (build_ladder(c, c->graphs_part, stream, n_rungs, 1, c->alleles_fresh, steps_n)) {
+                destroy_graphs(c->graphs_part);
+                return -1;
+            }
+        }
+    }
+    launch_set_step_ens(stream, c->particles_dev, P, first_step, n_steps);
+    if (use_graph) {
+        if (replay_pairs(c, c->graphs_part, stream, n_steps, steps_n)) return -1;
+    } else {
+        enqueue_particle_steps(c, stream, n_steps);
+    }
+    launch_finalize_ens(stream, c->particles_dev, P, first_step, n_steps);
+    hipLaunchKernelGGL(k_particle_loss, dim3((unsigned)((n_steps + 255) / 256)), dim3(256), 0, stream,
+                       (const DevArgs*)c->particles_dev, P, c->d.loss_hist, (unsigned long long)first_step,
+                       (unsigned long long)n_steps);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -3370,6 +3370,7 @@ __global__ __launch_bounds__(256) void k_test_special(int op, long n, const doub
 #include "bean_guide_v2.hpp"
 #include "bean_async_v2.hpp"  // all the steps of a call in one launch, tile-asynchronous
 #include "bean_ensemble.hpp"  // K seeds of one screen per launch: a member axis on the pair path
+#include "bean_particles.hpp"  // P draws per step on that member axis, one update with their mean gradient
 #ifdef BEAN_AB_KERNELS  // opt-in steppers, both bit-identical to the default path and measured slower
 #include "bean_step_v2.hpp"
 #endif

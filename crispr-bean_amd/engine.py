@@ -40,6 +40,16 @@ class EnsembleUnsupported(ValueError):
     """``HipSVI(..., n_members=K)`` on a shape the batched kernels do not take (``bean_hip_ensemble_supported``)."""
 
 
+def particle_mean(values):
+    """Mean of P tensors as a particle step forms it (``include/bean_hip.h``): a float64 accumulator that starts from the
+    first and adds the others in order, ONE multiply by ``1.0 / P``, then one rounding to the inputs' dtype."""
+    acc = values[0].to(torch.float64, copy=True)
+    for v in values[1:]:
+        acc += v.to(torch.float64)
+    acc *= 1.0 / len(values)
+    return acc.to(values[0].dtype)
+
+
 class HipSVI:
     """One model family bound to one screen on one GPU."""
 
@@ -72,9 +82,14 @@ class HipSVI:
         n_members: int = 1,
         member_masks=None,
         member_counts=None,
+        n_particles: int = 1,
     ):
         if family not in _lib.FAMILY:
             raise ValueError(f"unknown model family {family!r}")
+        if not 1 <= int(n_particles) <= _lib.MAX_MEMBERS:
+            raise ValueError(f"n_particles must be in [1, {_lib.MAX_MEMBERS}]")
+        if int(n_particles) != 1 and int(n_members) != 1:
+            raise ValueError("particles inside member sets are not batched: n_particles > 1 needs n_members == 1")
         if member_masks is not None:
             # per-member masks (bean_hip_bind_member_masks): checked before the library is touched
             if int(n_members) == 1:
@@ -259,6 +274,17 @@ class HipSVI:
                                           "after the other (run_inference_ensemble does)")
             with torch.cuda.device(dev):
                 self._check(self.lib.bean_hip_set_members(self._h, self.n_members), "set_members")
+        # multi-particle SVI (run_particles): P draws per step, one update with their mean gradient.  Where the batched
+        # kernels take the shape the library steps the particles in the same launches (bean_hip_svi_run_particles);
+        # everywhere else run_particles drives the defining loop itself.  Every tensor keeps its single-fit shape.
+        # (One particle goes the same way: run_particles is then run() in the particle step's four launches.)
+        self.n_particles = int(n_particles)
+        self._particles_native = False
+        # (a library named by BEAN_HIP_LIB may be an older build without the entry points: _lib.ENSEMBLE_SYMBOLS)
+        if self.n_members == 1 and hasattr(self.lib, "bean_hip_set_particles") and self.ensemble_supported:
+            with torch.cuda.device(dev):
+                self._check(self.lib.bean_hip_set_particles(self._h, self.n_particles), "set_particles")
+            self._particles_native = True
         self._keep: Dict[str, torch.Tensor] = {}
         self.stream = torch.cuda.Stream(device=dev)
 
@@ -411,7 +437,12 @@ class HipSVI:
         cap = int(loss_capacity) if loss_capacity is not None else self.num_steps + 8
         self.loss_hist = torch.zeros(max(cap, 1) if self.n_members == 1 else (self.n_members, max(cap, 1)),
                                      dtype=torch.float64, device=dev)
-        self._bind("LOSS_HIST", self.loss_hist)
+        self._loss_all = self.loss_hist
+        if self.n_particles != 1 and not self._particles_native:
+            # the defining loop evaluates every particle into a spare slot BEHIND the history, which only ever holds means
+            self._loss_all = torch.zeros(max(cap, 1) + 1, dtype=torch.float64, device=dev)
+            self.loss_hist = self._loss_all[:-1]
+        self._bind("LOSS_HIST", self._loss_all)
         self._noise_out: Dict[str, torch.Tensor] = {}
         if dump_noise:
             self._noise_out["eps_mu"] = torch.zeros(T, dtype=torch.float64, device=dev)
@@ -785,6 +816,56 @@ class HipSVI:
                                                            self._sptr()), "svi_run_ensemble")
         self._resume_broken = True  # (a following run(resume=True) does not continue this call)
         self.steps_done = first + n_steps
+
+    def run_particles(self, n_steps: int, seed: int = 101, graph_chunk: int = 50, first_step: Optional[int] = None):
+        """Enqueue ``n_steps`` SVI steps that each draw every latent site ``n_particles`` times - particle p with
+        ``particle_seeds(seed, n_particles)[p]`` - and apply ONE ClippedAdam update with the mean of the gradients (no
+        host synchronisation).  The step is defined in ``include/bean_hip.h``; one particle is ``run(n_steps, seed)``
+        bit for bit, stepping in windows gives the bits of one call, and ``loss_hist`` holds the particles' mean loss.
+
+        Where the batched kernels take the shape (``ensemble_supported``) the particles share the launches
+        (``bean_hip_svi_run_particles``); everywhere else - tiling, survival, ControlNormal, sample covariates, screens
+        large enough for the one-launch stepper - the same step is driven from here: ``bean_hip_elbo_grad`` per
+        particle, the float64 mean on the gradient tensors, ``bean_hip_adam``."""
+        from .model.jackknife import particle_seeds
+
+        if self.n_members != 1:
+            raise ValueError("particles inside member sets are not batched: run_particles needs n_members == 1")
+        seeds = particle_seeds(seed, self.n_particles)
+        first = self.steps_done if first_step is None else int(first_step)
+        if first + n_steps > self.loss_hist.numel():
+            raise ValueError("loss history too small: raise num_steps / loss_capacity")
+        if self._particles_native:
+            arr = (ctypes.c_uint64 * len(seeds))(*seeds)
+            with self._on_stream():
+                self._check(self.lib.bean_hip_svi_run_particles(self._h, arr, len(seeds), first, int(n_steps),
+                                                                int(graph_chunk), self._sptr()), "svi_run_particles")
+        elif self.n_particles == 1:  # the single fit itself
+            self.run(n_steps, seed=seed, graph_chunk=graph_chunk, first_step=first)
+        else:
+            self._run_particles_loop(seeds, first, int(n_steps))
+        self._resume_broken = True  # (a following run(resume=True) does not continue this call)
+        self.steps_done = first + n_steps
+
+    def _run_particles_loop(self, seeds, first: int, n_steps: int):
+        """The defining loop of a particle step on the engine's stream, nothing read back."""
+        lib, h, sp = self.lib, self._h, self._sptr()
+        spare = self._loss_all.numel() - 1
+        names = list(self.grads)
+        P = len(seeds)
+        with self._on_stream(), torch.cuda.stream(self.stream):
+            per_particle = [[torch.empty_like(self.grads[k]) for k in names] for _ in seeds]
+            losses = torch.empty(P, dtype=torch.float64, device=self.device)
+            for s in range(first, first + n_steps):
+                for p, sd in enumerate(seeds):
+                    self._check(lib.bean_hip_elbo_grad(h, int(sd), s, spare, sp), "elbo_grad")
+                    for dst, k in zip(per_particle[p], names):
+                        dst.copy_(self.grads[k])
+                    losses[p] = self._loss_all[spare]
+                for i, k in enumerate(names):
+                    self.grads[k].copy_(particle_mean([per_particle[p][i] for p in range(P)]))
+                self._check(lib.bean_hip_adam(h, s + 1, sp), "adam")
+                self._loss_all[s] = particle_mean(list(losses.unbind(0)))
 
     def _tensor_versions(self):
         return tuple(t._version for d in (self.unconstrained, self._m, self._v) for t in d.values())

@@ -79,6 +79,17 @@ def seed_plan(data, seeds) -> MemberPlan:
                       [{"member": k, "seed": seeds[k]} for k in ks], screen=lambda k: data)
 
 
+PARTICLE_SEED_STRIDE = 1_000_003
+
+
+def particle_seeds(seed: int, n_particles: int) -> List[int]:
+    """The seeds of a multi-particle fit's draws (``HipSVI.run_particles``, ``run_inference(num_particles=P)``): particle
+    p draws with ``seed + 1_000_003 * p``, so particle 0 is the fit's own seed.  ``n_particles < 1`` is a ``ValueError``."""
+    if int(n_particles) < 1:
+        raise ValueError(f"n_particles must be >= 1, got {int(n_particles)}")
+    return [int(seed) + PARTICLE_SEED_STRIDE * p for p in range(int(n_particles))]
+
+
 def _leave_one_out_plan(data, seed, items, label, tag, key, value, leave, **more) -> MemberPlan:
     """One seed for all: member 0 is the screen itself, member 1 + j is ``leave(data, items[j])``."""
     seed = int(seed)

@@ -18,7 +18,8 @@ import torch
 
 from ..engine import HipSVI
 from . import model as sorting_model
-from .jackknife import guide_plan, replicate_plan, sample_plan, seed_plan, stack_counts, stack_masks
+from .jackknife import (guide_plan, particle_seeds, replicate_plan, sample_plan, seed_plan, stack_counts,  # noqa: F401
+                        stack_masks)
 from .model import ModelSpec
 
 logger = logging.getLogger(__name__)
@@ -92,7 +93,7 @@ def build_engine(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000,
 
 
 def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000, autoguide=False,
-                  seed: int = SEED, report_every: int = 100, verbose: bool = True):
+                  seed: int = SEED, report_every: int = 100, verbose: bool = True, num_particles: int = 1):
     """Run SVI for the given model and guide (``bean/model/run.py:347-396``).
 
     Returns ``(param_store, {"loss": [float] * num_steps, "params": {name: cpu
@@ -106,11 +107,22 @@ def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000
     When ``torch.distributed`` is initialised with more than one rank the guides
     are sharded on target boundaries (``parallel.run_sharded``): every rank fits
     its shard on its own GPU and all ranks return the whole-screen result.
+
+    ``num_particles=P`` > 1 (Pyro's ``Trace_ELBO(num_particles=P)``, which the reference never passes): every step
+    draws every latent site P times, particle p with ``particle_seeds(seed, P)[p]``, and applies one update with the
+    mean of the P gradients (``HipSVI.run_particles``); ``loss`` holds the particles' mean loss.  One fit, the same
+    return structure, the same halt.  Not combined with guide sharding over several ranks.
     """
     import torch.distributed as dist
 
     from .. import parallel
+    from .._lib import MAX_MEMBERS
 
+    num_particles = int(num_particles)
+    if not 1 <= num_particles <= MAX_MEMBERS:
+        raise ValueError(f"num_particles must be in [1, {MAX_MEMBERS}], got {num_particles}")
+    if num_particles > 1:
+        _single_rank_only("run_inference(num_particles > 1)")
     world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
     device = torch.device("cuda", torch.cuda.current_device())
     spec = _resolve(model)
@@ -146,12 +158,16 @@ def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000
                 factory, data, num_steps, seed=seed, report_every=report_every, on_report=report)
         else:
             whole = (0, data.n_guides, 0, getattr(data, "n_targets", 0))
-            eng = factory(data, whole, data.n_guides)  # configuration errors surface as they are
+            particles = dict(n_particles=num_particles) if num_particles > 1 else {}
+            eng = factory(data, whole, data.n_guides, **particles)  # configuration errors surface as they are
             done = 0
             while done < num_steps:
                 k = min(report_every, num_steps - done)
                 eng.window_start = eng.snapshot()  # what a halt inside this window dumps
-                eng.run(k, seed=seed, resume=True)
+                if num_particles > 1:
+                    eng.run_particles(k, seed)
+                else:
+                    eng.run(k, seed=seed, resume=True)
                 # the reference halts at the failing step (run.py:375-390); here at the end of its report window
                 window = eng.loss_hist[done:done + k]
                 parallel.check_window_finite(window, done)

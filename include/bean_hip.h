@@ -333,6 +333,39 @@ int bean_hip_bind_member_counts(bean_hip_ctx* ctx, const void* x, uint64_t x_byt
 int bean_hip_svi_run_ensemble(bean_hip_ctx* ctx, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
                               uint64_t n_steps, int32_t graph_chunk, void* stream);
 
+/* Multi-particle SVI: every step draws every latent site P times and applies ONE ClippedAdam update with the mean of
+ * the P gradients (Pyro's Trace_ELBO(num_particles = P)).  With particle seeds s_0 ... s_{P-1}, step s is:
+ *   1. for every particle p, bean_hip_elbo_grad(seed = s_p, step = s) at the current, shared parameters: the loss L_p
+ *      and the float32 gradients g_p, bit for bit;
+ *   2. per element, acc = (double)g_0, then + (double)g_1, + (double)g_2, ... in particle order, and the mean gradient
+ *      is (float)(acc * (1.0 / P)): one float64 multiply, one rounding, no contraction;
+ *   3. bean_hip_adam(t = s + 1) with that mean (it is clamped as a single gradient is; a NaN in any g_p stays);
+ *   4. loss_hist[s] = (L_0 + L_1 + ... in particle order, float64) * (1.0 / P).
+ * The P evaluations run in the same launches (the member axis of the ensemble kernels); P = 1 is bean_hip_svi_run.
+ *
+ *   bean_hip_set_particles        after bean_hip_create, before ANY bean_hip_bind; 1 <= n_particles <=
+ *                                 BEAN_HIP_MAX_MEMBERS; only where bean_hip_ensemble_supported is 1.  Every buffer of
+ *                                 the caller keeps its single-fit size: parameters, moments, gradients, loss_hist.  The
+ *                                 handle owns what is per particle: a workspace copy, the loss accumulators, a (P, n)
+ *                                 float32 gradient scratch per parameter array and (P, capacity) loss values.  It does
+ *                                 not combine with bean_hip_set_members(K > 1): whichever of the two comes second is
+ *                                 refused.  The single-fit entry points keep working.
+ *   bean_hip_svi_run_particles    n_steps such steps from first_step: `seeds` is a HOST array of n_seeds == n_particles
+ *                                 values.  The gradient buffers must be bound: behind the call they hold the mean
+ *                                 gradient of its last step, and loss_hist[first_step .. first_step + n_steps) the mean
+ *                                 losses; no other slot of loss_hist is written.  Windows give the bits of one call.
+ *                                 Graphs of up to graph_chunk steps when graph_chunk > 0 (eager launches when 0).
+ *                                 Injected / dumped noise is refused.  A following bean_hip_svi_resume does not
+ *                                 continue it.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched): a null handle; set_particles on a shape that
+ * is not supported, after a bind, with n_particles outside [1, BEAN_HIP_MAX_MEMBERS], or on a handle of more than one
+ * member (and set_members(K > 1) on a handle of more than one particle); run_particles before set_particles, with
+ * n_seeds != n_particles, null seeds, or noise buffers bound.  The handle stays usable after every one of them. */
+int bean_hip_set_particles(bean_hip_ctx* ctx, int32_t n_particles);
+int bean_hip_svi_run_particles(bean_hip_ctx* ctx, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
+                               uint64_t n_steps, int32_t graph_chunk, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
