@@ -52,6 +52,17 @@
 // the residency.  Every poll is bounded (kAsyncSpinMax) and watches an abort word; a wave that gives up sets it, every
 // wave then leaves at its next poll or pull, the grid drains, and the call's loss slots report NaN (the host halts a
 // fit on a non-finite loss window).
+// With finisher roles a group's finishes are a sequence of POSITIONS known in advance: position p stands for a fixed
+// (step, tile of the group, part) in the items' order (async_fin_pos), the ring word of a position is filled by the wave
+// that completes that tile, and positions are taken in order (one counter per group).  Take the oldest step s of the
+// launch that has an unfinished finish.  Every finish of the steps before is done, so no item of step s waits, and a
+// group hands all of them out before any later item: every tile of step s completes and every position of step s is
+// filled.  A position that is taken is held by a wave that polls its word and then finishes it.  Below an untaken one
+// there are only positions of step s (older ones are finished, hence taken), so the group's oldest untaken position gets
+// filled too, and is then taken by a finisher, by an item wave that waits for step s + 1 (it looks at that position every
+// kAsyncStealEvery polls and takes it only when it is filled, so an item wave never waits inside a finish), or by a wave
+// that has run out of items.  No cycle, whoever is resident.  With no finisher resident a filled position behind an
+// unfilled older one waits until the older tile is complete: that costs time, not progress.
 //
 // Visibility (MI355X_MICROARCH.md, "inter-workgroup visibility"; the forms measured valid there).  Per-XCD L2s are not
 // coherent with each other and a CU's L1 is never refreshed by another CU's stores.  Everything one wave writes and
@@ -114,10 +125,12 @@ __host__ __device__ inline bool async_size_in_range(long items, long simds = 102
     const double per_simd = (double)items / (double)(simds > 0 ? simds : 1);
     return per_simd >= (double)kAsyncMinItems / 1024.0 && per_simd <= (double)kAsyncMaxItems / 1024.0;
 }
-// Finisher roles (round 5, second form).  One more wave per SIMD that does nothing but finish tiles: the wave that
-// completes a tile appends two entries to its group's finish ring - the tile's TARGETS (sums, priors, ClippedAdam, draw,
+// Finisher roles (round 5, second form).  One more wave per SIMD that does nothing but finish tiles: a tile's finish
+// is two positions of its group's finish ring - the tile's TARGETS (sums, priors, ClippedAdam, draw,
 // Phi tables, the R waves' loss parts) and its GUIDES (alpha_pi, noise site, digamma tables): two chains that do not
-// depend on each other - and pulls its next item at once; a finisher takes the ring's next position and polls it, so
+// depend on each other; the wave that completes a tile fills both words and pulls its next item at once; a finisher takes
+// the group's next position, knows from it which (step, tile, part) it will finish, PREPARES that finish
+// (async_finish_tile) and polls the position's word, so
 // the two parts of a tile run on two waves at the same time (11 and 5 us instead of 19 in a row), and an item waits for
 // its tile's two completed-step words and its neighbours' target words.  The item waves lose the fifth of their time they
 // spent finishing; a finisher is a latency chain that takes few issue slots from its SIMD's item waves.  It pays where an
@@ -127,11 +140,16 @@ __host__ __device__ inline bool async_size_in_range(long items, long simds = 102
 // 512 ... 2 048 finishers make no difference.  (With the finish in ONE piece the roles lost at 50k - 50.3 / 48.8: the hop
 // through the ring made the tile's chain longer than the item waves' step - and won as much at 62.5k, 57.4 / 61.0.)
 // Progress does not depend on the finishers being resident: a wave whose item has waited kAsyncStealEvery polls takes the
-// oldest finish nobody has taken, and a wave that finds no items left joins the finishers
+// oldest position nobody has taken if it is filled, and a wave that finds no items left joins the finishers
 // (tests/test_gpu_async.py runs both).
+// With the finish prepared before the tile's last wave arrives (async_finish_tile) the hop and the lookups that made the
+// roles lose on small screens are mostly gone, and at two item waves per SIMD the roles win at every size measured
+// (profiles/r06_async_grid_table.txt; us per step, roles / no roles): 25k guides 36.6 / 39.7 (0.95 items per wave),
+// 37.5k 39.6 / 42.2, 43.75k 41.7 / 42.7, 50k 45.8 / 47.5, 62.5k 56.4 / 59.6.  At three item waves per SIMD the table
+// moves nothing: 75k 62.7 / 62.5, 100k 75.3 / 77.4, 125k 92.8 / 95.7.
 __host__ __device__ inline bool async_finisher_roles(int waves_per_simd, long items, long simds) {
     const double per_wave = (double)items / (double)(waves_per_simd * simds);
-    return (waves_per_simd == 2 && per_wave >= 1.8) || (waves_per_simd == 3 && per_wave >= 2.4);
+    return (waves_per_simd == 2 && per_wave >= 0.95) || (waves_per_simd == 3 && per_wave >= 2.4);
 }
 constexpr int kAsyncQueueStride = 32;      // ints between two groups' queue counters (separate 128-byte lines)
 constexpr int kAsyncStealEvery = 64;       // polls between two looks of a waiting item's wave into the finish ring
@@ -144,12 +162,11 @@ struct AsyncArgs {
     int* done;                 // [2 n_tiles] steps of THIS call whose finish is complete: [2 k] tile k's targets, [2 k + 1] its guides
     int* abort_flag;           // [1] set by a wave whose poll ran out
     // finisher roles (n_guide_blocks > 0): blocks from n_guide_blocks upwards only finish tiles; the wave that completes a
-    // tile appends (step, tile) to its group's finish ring instead of finishing it itself
+    // tile fills the tile's position(s) of its group's finish ring instead of finishing it itself
     int n_guide_blocks;        // 0: every wave pulls items and the last arriver finishes (no roles)
-    int fin_split;             // 1: a tile's finish is two ring entries (targets, guides); 0: one
+    int fin_split;             // 1: a tile's finish is two ring positions (targets, guides); 0: one
     int* fhead;                // [8 * kAsyncQueueStride] next ring position a finisher takes
-    int* ftail;                // [8 * kAsyncQueueStride] next ring position to be filled
-    int* fring;                // [8 * fring_stride] ((step + 1) << 18) | (part: 0 targets, 1 guides, 2 both) << 16 | (tile >> 3); 0 = not filled yet
+    int* fring;                // [8 * fring_stride] by position (async_fin_pos): local step + 1 once the tile is complete; 0 = not yet
     long fring_stride;
     const float* step_sizes;   // [n_steps] ClippedAdam step size of the update of step0 + i (k_step_sizes)
     unsigned long long* stamps;  // diagnostic builds (-DBEAN_ASYNC_STAMP): kAsyncStampSteps x items x 8 words, or null
@@ -243,12 +260,27 @@ __device__ __forceinline__ void async_give_up(const DevArgs* cp, const AsyncArgs
 // DevArgs come from their copy in global memory into SGPRs (bean_devargs_sgpr.hpp), read again for every item: nothing
 // derived from them is loop-invariant to the compiler (with MachineLICM on and DevArgs as a kernel argument, the
 // inlined loop spilled 249 VGPRs: 576 B of scratch per lane).
+//
+// PREPARE and COMPLETE.  A finisher knows (step, tile, part) from the ring position it took, before the tile's last
+// wave has arrived (`wait_slot`: the position's ring word, still zero).  Whatever the finish needs that does not depend
+// on the step's items and that no wave of the launch writes is fetched BEFORE the wave polls that word: DevArgs into
+// SGPRs, the tile's first target and target count (g2t), the target offsets (toff) - three of the four dependent round
+// trips that used to stand between "tile complete" and the first load of its sums.  Everything that reads what the
+// step's items or a neighbour's finish wrote (boundary counters, sums, state, loss parts) is issued after the poll has
+// matched, as before: the arithmetic and the order of every addition are unchanged, only when three lookups are made
+// moves.  A finish that is taken when it is already filled (wait_slot = nullptr: the last arriver without roles, a
+// waiting item wave that takes the oldest filled position) runs prepare inline.
+// Returns kAsyncFinDone, or why the wave must leave: the abort word was seen, or the poll ran out.
+constexpr int kAsyncFinDone = 0, kAsyncFinLeave = 1, kAsyncFinGaveUp = 2;
 template <int FAM, bool ACC>
-__device__ BEAN_ASYNC_INLINE void async_finish_tile(const DevArgs* cp, unsigned long long step, unsigned long long slot,
-                                               float step_size, int tile, int part BEAN_ASYNC_ST_ARG) {
+__device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned long long step, unsigned long long slot,
+                                              float step_size, int tile, int part, const int* wait_slot,
+                                              const int* abort_flag BEAN_ASYNC_ST_ARG) {
     // part: 1 = the tile's targets (sums, priors, ClippedAdam, draw, Phi tables; the R waves' loss parts), 2 = its guides
     // (alpha_pi, the noise site, digamma tables), 3 = both.  The two do not depend on each other: with finisher roles they
-    // are two entries of the finish ring and run on two waves at the same time.
+    // are two positions of the finish ring and run on two waves at the same time.
+    // (the tile's next step waits for this chain: it goes first on its SIMD - but not while it only polls)
+    if (BEAN_ASYNC_PRIO && !wait_slot) __builtin_amdgcn_s_setprio(3);
     const DevArgs c = dev_args_in_sgprs(cp);
     part = rfl_i(part);
     step = rfl_u64(step);
@@ -282,6 +314,24 @@ __device__ BEAN_ASYNC_INLINE void async_finish_tile(const DevArgs* cp, unsigned 
         tof0 = __builtin_amdgcn_readlane(tv, 0);
         tof1 = __builtin_amdgcn_readlane(tv, 1);
     }
+    // ---- prepared: now wait until the tile's last wave has arrived (lane 0 polls the position's word, lane 1 the abort
+    // word; bounded).  The rows, sums and loss parts of all R waves had completed before the arrival that filled the word,
+    // and nothing below is loaded before the poll has matched.
+    if (wait_slot) {
+        int spins = 0;
+        for (;;) {
+            int v = 0, ab = 0;
+            if (lane == 0) v = __hip_atomic_load(wait_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 1) ab = __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__any(ab != 0)) return kAsyncFinLeave;
+            if (__builtin_amdgcn_readfirstlane(v) != 0) break;
+            if (++spins > kAsyncSpinMax) return kAsyncFinGaveUp;
+            __builtin_amdgcn_s_sleep(BEAN_ASYNC_SLEEP);
+        }
+        if (BEAN_ASYNC_PRIO) __builtin_amdgcn_s_setprio(3);
+    }
+    asm volatile("" ::: "memory");
+    BEAN_ASYNC_TF(part == 2 ? 6 : 4);
     const unsigned long long s_prep = ctr.step + 1;
     AdamCoef ak;
     ak.step_size = ctr.step_size;
@@ -492,6 +542,7 @@ __device__ BEAN_ASYNC_INLINE void async_finish_tile(const DevArgs* cp, unsigned 
         atomicAdd((unsigned long long*)acc + 1, (unsigned long long)b);
         if (d) atomicAdd((unsigned long long*)acc + 2, (unsigned long long)d);
     }
+    return kAsyncFinDone;
 }
 
 // One item: k_guide_wave2's wave work on (tile, r) at the step, this wave's loss part, the arrival.  Returns
@@ -545,6 +596,16 @@ __device__ BEAN_ASYNC_INLINE int2 async_guide_item(const DevArgs* cp, unsigned l
     return res;
 }
 
+// Position p of a group's finish sequence stands for a fixed (local step, tile of the group, part), in queue order:
+// (step, tile, part), one position per tile and step or - fin_split - two, the targets' part first.
+__device__ __forceinline__ void async_fin_pos(int p, int nx, int split, int& s, int& jt, int& part) {
+    const int per = split ? 2 * nx : nx;
+    s = p / per;
+    const int rem = p - s * per;
+    jt = split ? rem >> 1 : rem;
+    part = split ? (rem & 1) + 1 : 3;  // 1 targets, 2 guides, 3 both
+}
+
 template <int FAM, bool ACC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_ASYNC_EU)))
 void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
@@ -553,43 +614,30 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
     const int nx = (n_tiles - x + 7) >> 3;      // tiles k with k & 7 == x
     const int per_step = nx * R;
     const long total = (long)per_step * a.n_steps;
-    const long total_fin = (a.fin_split ? 2l : 1l) * nx * a.n_steps;  // (ring entries per tile and step)
+    const long total_fin = (a.fin_split ? 2l : 1l) * nx * a.n_steps;  // (ring positions per tile and step)
     int* const queue = a.queue + x * kAsyncQueueStride;
     const bool roles = a.n_guide_blocks > 0;
     bool finisher = roles && (int)blockIdx.x >= a.n_guide_blocks;
     int* const fhead = a.fhead + x * kAsyncQueueStride;
-    int* const ftail = a.ftail + x * kAsyncQueueStride;
     int* const fring = a.fring + x * a.fring_stride;
     int item = -1;  // a guide item this wave has pulled and not run yet
     for (;;) {
         int fin_s = -1, fin_tile = 0, fin_part = 3;  // the finish this iteration ends with, if any
+        const int* fin_wait = nullptr;               // ... and the ring word it has to wait for (a position taken in advance)
 #ifdef BEAN_ASYNC_STAMP
         unsigned long long* st_row = nullptr;
 #endif
         if (finisher) {
-            // ---- a finisher takes the group's next finish and waits until it is there
+            // ---- a finisher takes the group's next position: it knows its work at once, prepares it and waits for the
+            // position's word inside async_finish_tile
             int pos = 0;
             if (lane == 0) pos = __hip_atomic_fetch_add(fhead, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             pos = __builtin_amdgcn_readfirstlane(pos);
             if (pos >= total_fin) return;
-            int entry = 0, spins = 0;
-            for (;;) {
-                int v = 0, ab = 0;
-                if (lane == 0) v = __hip_atomic_load(fring + pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (lane == 1) ab = __hip_atomic_load(a.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (__any(ab != 0)) return;
-                entry = __builtin_amdgcn_readfirstlane(v);
-                if (entry != 0) break;
-                if (++spins > kAsyncSpinMax) {
-                    if (lane == 0) async_give_up(cp, a);
-                    return;
-                }
-                __builtin_amdgcn_s_sleep(BEAN_ASYNC_SLEEP);
-            }
-            asm volatile("" ::: "memory");
-            fin_s = (int)((unsigned)entry >> 18) - 1;
-            fin_part = ((entry >> 16) & 3) + 1;  // 1 targets, 2 guides, 3 both
-            fin_tile = (entry & 0xffff) * 8 + x;
+            int jt;
+            async_fin_pos(pos, nx, a.fin_split, fin_s, jt, fin_part);
+            fin_tile = jt * 8 + x;
+            fin_wait = fring + pos;
         } else {
             // ---- pull the group's next item: (step, tile, replicate) in that order
             if (item < 0) {
@@ -647,7 +695,7 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
                         return;
                     }
                     if (roles && (spins & (kAsyncStealEvery - 1)) == 0) {
-                        int e = 0;
+                        int e = 0;  // (position + 1)
                         if (lane == 0) {
                             const int h = __hip_atomic_load(fhead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             if (h < total_fin) {
@@ -655,14 +703,14 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
                                 int expect = h;
                                 if (cand != 0 && __hip_atomic_compare_exchange_strong(fhead, &expect, h + 1, __ATOMIC_RELAXED,
                                                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-                                    e = cand;
+                                    e = h + 1;
                             }
                         }
                         e = __builtin_amdgcn_readfirstlane(e);
                         if (e != 0) {
-                            fin_s = (int)((unsigned)e >> 18) - 1;
-                            fin_part = ((e >> 16) & 3) + 1;
-                            fin_tile = (e & 0xffff) * 8 + x;
+                            int jt;
+                            async_fin_pos(e - 1, nx, a.fin_split, fin_s, jt, fin_part);
+                            fin_tile = jt * 8 + x;
                             break;
                         }
                     }
@@ -678,19 +726,13 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
                 BEAN_ASYNC_T(2);
                 if (fin.x >= 0) {
                     if (roles) {
-                        // the tile is complete: hand its finish to the group's finishers (the rows, sums and loss parts of
-                        // all R waves had completed before the arrival that made this wave the last)
-                        // (two entries: the targets' part and the guides' part run on two finishers at the same time)
+                        // the tile is complete: fill its position(s) of the group's ring (the rows, sums and loss parts of
+                        // all R waves had completed before the arrival that made this wave the last); with two positions
+                        // the targets' part and the guides' part run on two finishers at the same time
                         if (lane == 0) {
-                            const int e = (int)(((unsigned)(s + 1) << 18) | (unsigned)(tile >> 3));
-                            if (a.fin_split) {
-                                const int p = __hip_atomic_fetch_add(ftail, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                __hip_atomic_store(fring + p, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                // targets
-                                __hip_atomic_store(fring + p + 1, e | 0x10000, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // guides
-                            } else {
-                                const int p = __hip_atomic_fetch_add(ftail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                __hip_atomic_store(fring + p, e | 0x20000, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // both
-                            }
+                            int* const w = fring + (long)(s * nx + jt) * (a.fin_split ? 2 : 1);
+                            __hip_atomic_store(w, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (a.fin_split) __hip_atomic_store(w + 1, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         }
                     } else {
                         fin_s = s;
@@ -707,13 +749,15 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
             st_row = nullptr;
             if (a.stamps && fin_s >= kAsyncStampStep0 && fin_s < kAsyncStampStep0 + kAsyncStampSteps)
                 st_row = a.stamps + ((long)(fin_s - kAsyncStampStep0) * ((long)((n_tiles + 7) / 8 * 8) * R) + (long)fin_tile * R) * 8;
-            BEAN_ASYNC_TF(fin_part == 2 ? 6 : 4);
 #endif
             const unsigned long long step = a.step0 + (unsigned long long)fin_s, slot = a.slot0 + (unsigned long long)fin_s;
-            // (the tile's next step waits for this chain: it goes first on its SIMD)
-            if (BEAN_ASYNC_PRIO) __builtin_amdgcn_s_setprio(3);
-            async_finish_tile<FAM, ACC>(cp, step, slot, a.step_sizes[fin_s], fin_tile, fin_part BEAN_ASYNC_ST_PASS);
+            const int left = async_finish_tile<FAM, ACC>(cp, step, slot, a.step_sizes[fin_s], fin_tile, fin_part, fin_wait,
+                                                         a.abort_flag BEAN_ASYNC_ST_PASS);
             if (BEAN_ASYNC_PRIO) __builtin_amdgcn_s_setprio(0);
+            if (left != kAsyncFinDone) {
+                if (left == kAsyncFinGaveUp && lane == 0) async_give_up(cp, a);
+                return;
+            }
             // ---- publish: every store of the finish has completed before the tile's step counts move
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) {

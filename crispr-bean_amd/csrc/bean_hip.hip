@@ -1665,7 +1665,7 @@ static int launch_svi_async_t(bean_hip_ctx* c, hipStream_t stream, const AsyncAr
     if ((long)blocks > items) blocks = (int)((items + 7) / 8 * 8);
     AsyncArgs a = a_in;
     int fin_blocks = 0;
-    // the finish as two ring entries (targets / guides on two finishers at once) while the item waves have few items per
+    // the finish as two ring positions (targets / guides on two finishers at once) while the item waves have few items per
     // step - then a tile's chain is what a step waits for - and as one entry beyond (same box, split / one entry: 50k guides
     // 48.5 / 51.3 us per step, 56k 53.2 / 53.3, 62.5k 59.4 / 58.8, 68.75k 65.5 / 64.4, 125k 97.0 / 95.7)
     a.fin_split = (double)d.n_tiles * d.R / (double)(c->async_blocks > 0 ? c->async_blocks : 1) < 2.15 ? 1 : 0;
@@ -1699,10 +1699,11 @@ static int launch_svi_async(bean_hip_ctx* c, hipStream_t stream, uint64_t step0,
         HIP_OK(hipMalloc((void**)&c->step_sizes, cap * sizeof(float)));
         c->step_sizes_cap = cap;
     }
-    // [8 x stride] queue | abort word (a line of its own) | [8 x stride] finish-ring heads | [8 x stride] tails | done[n_tiles]:
-    // zeroed by every call; behind them the finish rings (n_steps x the group's tiles, zeroed when roles are on)
-    const size_t ws_ints = (size_t)25 * kAsyncQueueStride + (size_t)2 * d.n_tiles;
-    // (finish rings only for calls short enough to have finisher roles: a ring entry holds the step in 14 bits)
+    // [8 x stride] queue | abort word (a line of its own) | [8 x stride] finish-ring heads | done[2 n_tiles]:
+    // zeroed by every call; behind them the finish rings (one or two words per step and tile of the group, by position:
+    // async_fin_pos; zeroed by every call)
+    const size_t ws_ints = (size_t)17 * kAsyncQueueStride + (size_t)2 * d.n_tiles;
+    // (finish rings, and with them finisher roles, only for calls of fewer than 8 000 steps: the rings grow with the call)
     const size_t fring_stride = n_steps < 8000 ? (size_t)2 * ((d.n_tiles + 7) / 8) * n_steps : 0;
     const size_t need_ints = ws_ints + 8 * fring_stride;
     if (need_ints > c->async_ws_ints) {
@@ -1721,8 +1722,7 @@ static int launch_svi_async(bean_hip_ctx* c, hipStream_t stream, uint64_t step0,
     a.queue = c->async_ws;
     a.abort_flag = c->async_ws + 8 * kAsyncQueueStride;
     a.fhead = c->async_ws + 9 * kAsyncQueueStride;
-    a.ftail = c->async_ws + 17 * kAsyncQueueStride;
-    a.done = c->async_ws + 25 * kAsyncQueueStride;
+    a.done = c->async_ws + 17 * kAsyncQueueStride;
     a.fring = c->async_ws + ws_ints;
     a.fring_stride = (long)fring_stride;
     a.n_guide_blocks = 0;  // (set by launch_svi_async_t, where the grid is decided)

@@ -1,5 +1,7 @@
 """Step time of the tile-asynchronous stepper (BEAN_HIP_STEP=async) against the two launches per step (=pair), same box,
-one process per (mode, size): python scripts/time_async.py [guides ...]"""
+one process per (mode, size): python scripts/time_async.py [guides ...]
+ASYNC_BLOCKS=2048,3072:0,3072:1024 adds grids of that many item waves (":fin": that many finisher waves, 0 = no roles;
+without it the default for the size); MODES=async leaves the pair path out; WINDOWS windows of 100 steps are timed."""
 import json
 import os
 import subprocess
@@ -31,10 +33,14 @@ sizes = [int(x) for x in sys.argv[1:]] or [50000, 62500]
 res = {}
 for G in sizes:
     for acc in (os.environ.get("ACC", "0"),):
-        for mode in ["pair", "async"] + [f"async@{b}" for b in os.environ.get("ASYNC_BLOCKS", "").split(",") if b]:
+        base = [m for m in os.environ.get("MODES", "pair,async").split(",") if m]
+        for mode in base + [f"async@{b}" for b in os.environ.get("ASYNC_BLOCKS", "").split(",") if b]:
             env = dict(os.environ, BEAN_HIP_STEP=mode.split("@")[0])
             if "@" in mode:
-                env["BEAN_HIP_ASYNC_BLOCKS"] = mode.split("@")[1]
+                grid = mode.split("@")[1].split(":")
+                env["BEAN_HIP_ASYNC_BLOCKS"] = grid[0]
+                if len(grid) > 1:
+                    env["BEAN_HIP_ASYNC_FIN"] = grid[1]
             p = subprocess.run([sys.executable, "-c", CHILD, str(G), acc], env=env, capture_output=True, text=True, timeout=600)
             line = p.stdout.strip().splitlines()[-1] if p.stdout.strip() else p.stderr[-400:]
             print(G, mode, line, flush=True)
