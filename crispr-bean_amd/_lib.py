@@ -89,7 +89,8 @@ MAX_MEMBERS = 64  # BEAN_HIP_MAX_MEMBERS
 # build beside this one, scripts/time_ensemble.py); such a library serves single fits only
 ENSEMBLE_SYMBOLS = ("bean_hip_ensemble_supported", "bean_hip_set_members", "bean_hip_svi_run_ensemble",
                     "bean_hip_bind_member_masks", "bean_hip_bind_member_counts",
-                    "bean_hip_set_particles", "bean_hip_svi_run_particles")
+                    "bean_hip_set_particles", "bean_hip_svi_run_particles",
+                    "bean_hip_predictive_supported", "bean_hip_simulate")
 PARAM_ORDER = ("mu_loc", "mu_scale", "sd_loc", "sd_scale", "alpha_pi", "noise_loc", "noise_scale", "q0")
 
 # every symbol include/bean_hip.h declares: (name, restype, argtypes)
@@ -111,6 +112,9 @@ SYMBOLS = [
     ("bean_hip_bind_member_counts", c_int32, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64]),
     ("bean_hip_set_particles", c_int32, [c_void_p, c_int32]),
     ("bean_hip_svi_run_particles", c_int32, [c_void_p, POINTER(c_uint64), c_int32, c_uint64, c_uint64, c_int32, c_void_p]),
+    ("bean_hip_predictive_supported", c_int32, [c_void_p]),
+    ("bean_hip_simulate", c_int32,
+     [c_void_p, c_uint64, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
     ("bean_hip_sharded_begin", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
     ("bean_hip_sharded_sums", c_int32, [c_void_p, c_void_p]),
     ("bean_hip_sharded_guide", c_int32, [c_void_p, c_void_p]),

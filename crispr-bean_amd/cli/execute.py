@@ -15,6 +15,13 @@ def _positive_int(text: str) -> int:
     return value
 
 
+def _non_negative_int(text: str) -> int:
+    value = int(text)
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"must be >= 0, got {value}")
+    return value
+
+
 def get_parser():
     parser = argparse.ArgumentParser(prog="bean")
     sub = parser.add_subparsers(dest="subcommand", help="bean subcommands")
@@ -59,6 +66,17 @@ def get_parser():
                           "draw): one fit and the usual tables, with less gradient noise.  The --fit-negctrl fit of the "
                           "negative controls stays at one particle.  At most 64; not combined with --n-seeds > 1, any "
                           "--jackknife-* flag or --load-existing.")
+    own.add_argument("--posterior-predictive", dest="posterior_predictive", type=_non_negative_int, default=0, metavar="S",
+                     help="After the fit, draw S replicate screens from the fitted guide and the likelihood on the GPU "
+                          "and compare them with the observed counts (a posterior predictive check): per guide, "
+                          "ppc_p_score / ppc_z_score (does the model reproduce the guide's sorting score?) and "
+                          "ppc_p_spread (do its replicates disagree more than the model predicts?) in "
+                          "bean_predictive_guides.<model>.csv; per sample, the share of cells with p <= 0.05 and their "
+                          "mean z in bean_predictive_samples.<model>.csv.  The other tables do not change.  With a member "
+                          "set (--n-seeds, --jackknife-*) the check is of the fit the tables come from.  Sorting variant "
+                          "screens only; the --fit-negctrl control fit is not checked.  Default 0: off.")
+    own.add_argument("--predictive-seed", dest="predictive_seed", type=int, default=101,
+                     help="Seed of the draws of --posterior-predictive (default 101).")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))
@@ -70,11 +88,12 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    from .run import member_mode, particle_count
+    from .run import member_mode, particle_count, predictive_draws
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
     particle_count(args, parser.error)
+    predictive_draws(args, parser.error)
 
 
 def main(argv=None):

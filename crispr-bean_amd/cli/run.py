@@ -130,6 +130,25 @@ def particle_count(args, fail=_refuse) -> int:
     return n
 
 
+_PREDICTIVE_FAMILY = ("--posterior-predictive simulates the counts of the sorting variant models (Normal, MixtureNormal) and "
+                      "is not available for {what}.")
+
+
+def predictive_draws(args, fail=_refuse) -> int:
+    """``--posterior-predictive S``: the number of replicate screens to draw after the fit (0: none).  A family the count
+    simulator does not take is refused - ``fail(sentence)``, as ``member_mode`` - with the family named."""
+    n = int(getattr(args, "posterior_predictive", 0) or 0)
+    if n < 0:
+        fail(f"--posterior-predictive must be >= 0, got {n}.")
+    if n == 0:
+        return 0
+    if getattr(args, "library_design", None) == "tiling":
+        fail(_PREDICTIVE_FAMILY.format(what="tiling screens (MultiMixtureNormal)"))
+    if getattr(args, "selection", None) == "survival":
+        fail(_PREDICTIVE_FAMILY.format(what="survival screens"))
+    return n
+
+
 def check_guide_jackknife_switches(args) -> bool:
     """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
     return member_mode(args, only=("jackknife_guides",)) == "guides"
@@ -285,6 +304,14 @@ def main(args, return_data=False):
     info(f"Running inference for {model_label}...")
     mode = member_mode(args)
     n_particles = particle_count(args)
+    n_predictive = predictive_draws(args)
+    if n_predictive:
+        # refused before the fit, not after it: what only the screen shows (sample covariates, several ranks)
+        from ..engine import PredictiveUnsupported
+
+        why = model_run._predictive_refusal(model_run._resolve(model), ndata, world)
+        if why is not None:
+            raise PredictiveUnsupported(_PREDICTIVE_FAMILY.format(what=why))
     table_columns = {}
     save_dict = dict()
     param_history_dict_negctrl = None
@@ -348,5 +375,13 @@ def main(args, return_data=False):
         is_survival_screen=(args.selection == "survival"),
         **table_columns,
     )
+    if n_predictive:
+        from ..model.predictive import write_predictive_tables
+
+        info(f"Posterior predictive check: {n_predictive} replicate screens...")
+        summary = model_run.run_posterior_predictive(model, guide, ndata, param_history_dict, n_draws=n_predictive,
+                                                     seed=int(getattr(args, "predictive_seed", model_run.SEED)))
+        paths = write_predictive_tables(summary, guide_info_df, ndata, f"{prefix}/", model_label, args.result_suffix)
+        info(f"Wrote {paths[0]} and {paths[1]}.")
     info("Done!")
     return prefix

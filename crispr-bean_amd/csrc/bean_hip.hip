@@ -27,6 +27,7 @@
 
 #include "../../include/bean_hip.h"
 #include "bean_kernels.hpp"
+#include "bean_predictive.hpp"  // replicate counts drawn on the device (bean_hip_simulate)
 
 using namespace bean;
 
@@ -2701,6 +2702,63 @@ extern "C" int bean_hip_test_special(int32_t op, uint64_t n, const double* a, co
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_test_special, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
                        (int)op, (long)n, a, x, b, out0, out1);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ posterior predictive replicate counts
+// (bean_predictive.hpp; at the end of the file, so that every other kernel keeps its place in the code object)
+static bool predictive_shape_ok(const bean_hip_ctx* c) {
+    const bean_hip_shape& s = c->shape;
+    return c->wave_guide && c->wave2 && c->fused_guide && !is_survival(s) && s.n_sample_covariates == 0 &&
+           (s.family == BEAN_FAMILY_NORMAL || s.family == BEAN_FAMILY_MIXTURE_NORMAL) && s.guide_offset == 0 &&
+           s.target_offset == 0 && (s.n_guides_total == 0 || s.n_guides_total == s.n_guides) &&
+           !(s.flags & BEAN_FLAG_NOT_LOSS_OWNER) && c->n_members == 1 && c->n_particles == 1;
+}
+
+extern "C" int bean_hip_predictive_supported(const bean_hip_ctx* c) {
+    if (!c) return fail("bean_hip_predictive_supported: null handle");
+    return predictive_shape_ok(c) ? 1 : 0;
+}
+
+extern "C" int bean_hip_simulate(bean_hip_ctx* c, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
+                                 void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes,
+                                 void* stream_) {
+    if (!c) return fail("bean_hip_simulate: null handle");
+    if (!predictive_shape_ok(c))
+        return fail("bean_hip_simulate: the count simulator does not take this handle (bean_hip_predictive_supported): "
+                    "sorting variant Normal / MixtureNormal, unsharded, no sample covariates, one member, one particle");
+    if (!c->prepared) return fail("bean_hip_simulate: call bean_hip_prepare first");
+    if (check_bound(c, false, false)) return -1;
+    const DevArgs& d0 = c->d;
+    const uint64_t n = (uint64_t)d0.R * d0.B * d0.G;
+    const bool use_bc = (d0.flags & kUseBc) != 0;
+    if (!x_out || x_bytes != 4 * n)
+        return fail("bean_hip_simulate: x_out must hold (R, B, G) float32, " + std::to_string(4 * n) + " bytes");
+    if (use_bc && (!xbc_out || xbc_bytes != 4 * n))
+        return fail("bean_hip_simulate: this handle uses the barcode-matched counts: xbc_out must hold (R, B, G) float32, " +
+                    std::to_string(4 * n) + " bytes");
+    if (!use_bc && (xbc_out || xbc_bytes))
+        return fail("bean_hip_simulate: xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
+    if (alpha_out ? alpha_bytes != 16 * n : alpha_bytes != 0)
+        return fail("bean_hip_simulate: alpha_out must be null or hold (2, R, B, G) float64, " + std::to_string(16 * n) +
+                    " bytes");
+    hipStream_t stream = (hipStream_t)stream_;
+    c->d.seed = seed;
+    c->resume_ok = false;  // the workspace now holds this draw and its tables
+    // draw `draw` as bean_hip_elbo_grad(seed, step = draw) prepares it; no loss slot is cleared (n = 0)
+    launch_set_step(c, stream, draw, 0, 0);
+    launch_param<false, false, true>(c, stream);
+    const DevArgs& d = c->d;
+    SimArgs sa;
+    sa.x_out = (float*)x_out;
+    sa.xbc_out = (float*)xbc_out;
+    sa.alpha_out = (double*)alpha_out;
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R), block(64);
+    const size_t lds = simulate_wave2_lds(d.B);
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_simulate_wave2<fam(), acc()>), grid, block, lds, stream, d, sa);
+    });
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -1,0 +1,201 @@
+// k_simulate_wave2: replicate counts of the variant sorting families, drawn on the device (posterior predictive check).
+//
+// For one draw d of the latent sites - the draw bean_hip_elbo_grad(seed, step = d) evaluates, prepared by the same
+// k_set_step + PREP k_param launches - every (replicate, guide) forms the Dirichlet-Multinomial concentrations of its
+// likelihoods (X and, with the flag, X_bcmatch) as guide_pair_math does, then draws
+//     p ~ Dirichlet(alpha),    x_rep ~ Multinomial(n_obs, p),    n_obs = sum_b x_b of the observed counts.
+//
+//   * grid and lanes as k_guide_wave2: a single-wave workgroup is 64 consecutive guides (GLOBAL index) of one
+//     replicate, XCD-aware decode of blockIdx.x, a lane is one (replicate, guide); a lane beyond G writes nothing.
+//   * the pi site: guide_pair_draw<FAM>, same site, subsequence and offset; DevArgs::pi_in and the injected target
+//     noise (lpn, formed by k_param) are honoured as guide_pair_math honours them.
+//   * concentrations: the forward lines of guide_pair_math - accessibility transform, the S = sum_b e_b sf_b pre-pass,
+//     a0 / (S + eps), the sample mask, alpha_raw with the same operands, floor at kEps.
+//   * Dirichlet: B gammas from the Marsaglia-Tsang pair sampler on site kSiteSimGamma (bins two by two), floored at
+//     kDblMin, normalised in float64.  A concentration on the 1e-5 floor takes the sampler's alpha < 1 boost
+//     U^(1 / alpha), which underflows to zero for all but ~0.7 % of the draws: such a bin then holds the kDblMin floor,
+//     i.e. a probability below 1e-300 - what Gamma(1e-5) is.
+//   * Multinomial: n_obs categorical draws by inversion on the float64 cumulative of p; one Philox block of site
+//     kSiteSimCat gives four uniforms u = (w + 0.5) 2^-32; the bin is the number of cumulative values <= u among
+//     the first B - 1, so the last bin takes what the cumulative leaves.  Exact for any n: no approximation branch,
+//     no rejection, and the counts of a pair add up to n_obs by construction.
+//   * COST: the draw loop runs ceil(n_obs / 4) times per lane, so a wave takes as long as its LARGEST total; lanes
+//     that are done idle (a screen's totals inside a tile are of one magnitude; one deep guide costs its wave alone).
+//   * masks do not enter: a pair masked by repguide_mask or n <= mask_thres is simulated like any other (the summary
+//     leaves it out); the sample mask enters the concentrations exactly as in the ELBO.
+//   * LDS: [4][B] per-bin constants of the replicate (as k_guide_wave2 stages them) | [B][64] doubles, a
+//     thread-private column: table value, then concentration, gamma, cumulative | [B][64] floats, the counts drawn.
+//     No scratch, no atomics; results leave through plain vector stores.
+// Counter layout: next to RngSite (bean_special.hpp).
+#pragma once
+
+namespace bean {
+
+struct SimArgs {
+    float* x_out;       // (R, B, G), the layout of BEAN_BUF_X
+    float* xbc_out;     // (R, B, G) or null (no BEAN_FLAG_USE_BCMATCH)
+    double* alpha_out;  // (2, R, B, G) floored concentrations or null
+};
+
+constexpr unsigned long long kSimGammaWords = 512;   // words reserved per pair of bins
+constexpr unsigned long long kSimPairSlots = 32;     // pairs of bins per (likelihood, draw)
+constexpr unsigned long long kSimCatWords = 1ull << 24;  // words per (likelihood, draw): one per categorical draw
+static_assert(kBCap <= 2 * kSimPairSlots, "the gamma windows hold kBCap conditions");
+
+__host__ __device__ inline size_t simulate_wave2_lds(int B) {
+    return ((size_t)4 * B + (size_t)B * 64) * sizeof(double) + (size_t)B * 64 * sizeof(float);
+}
+
+template <int FAM, bool ACC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
+void k_simulate_wave2(DevArgs c, SimArgs s) {
+    constexpr bool MIX = FAM == kMixture;
+    extern __shared__ double sim_lds[];
+    const StepCtr ctr = *c.ctrB;
+    const int wg = blockIdx.x;
+    const int kk = wg >> 3;
+    const int r = kk % c.R;
+    const int tile = (kk / c.R) * 8 + (wg & 7);
+    if (tile >= c.n_tiles) return;
+    const int lane = threadIdx.x;
+    const int G = c.G, B = c.B, R = c.R;
+    const int g = tile * 64 + lane - c.g_sh;
+    const bool valid = g >= 0 && g < G;
+    const bool use_bc = (c.flags & kUseBc) != 0;
+    double* cst = sim_lds;                                    // [4][B]: sf, sf_bc, sample mask, P0
+    double* col = cst + 4 * B + lane;                         // col[b * 64]
+    float* xs = (float*)(cst + 4 * B + (size_t)B * 64) + lane;  // xs[b * 64]
+    {
+        const int kq = lane >> 3, bq = lane & 7;
+        if (kq < 4) {
+            const double* src = kq == 0 ? c.sf + r * B : (kq == 1 ? (use_bc ? c.sf_bc : c.sf) + r * B
+                                                                  : (kq == 2 ? c.smask + r * B : c.P0));
+            for (int b2 = bq; b2 < B; b2 += 8) cst[kq * B + b2] = (MIX || kq != 3) ? src[b2] : 0.0;
+        }
+    }
+    __syncthreads();
+    if (!valid) return;
+    const double* c_sm = cst + 2 * B;
+    const double* c_p0 = cst + 3 * B;
+    const long rgi = (long)r * G + g;
+    const unsigned long long sub = (unsigned long long)r * c.G_tot + (c.g_off + g);
+
+    // ---- the pi draw of this step and its transform: guide_pair_draw + the head of guide_pair_math
+    double pi0 = 0.0, pi1 = 1.0, pe1 = 1.0;
+    if (MIX) {
+        const float api0 = c.p[4][2 * g], api1 = c.p[4][2 * g + 1];
+        const double pa0 = c.pi_a0[g];
+        uint4 philox_first = make_uint4(0u, 0u, 0u, 0u);
+        if (!c.pi_in) philox_first = philox_block(c.seed, ((unsigned long long)kSitePi << 48) + sub, ctr.step * 256ull);
+        double cp0, cp1;
+        guide_pair_draw<FAM>(c, ctr, r, g, api0, api1, pa0, &philox_first, &cp0, &cp1, pi0, pi1);
+        if (c.pi_in) {
+            pi0 = c.pi_in[rgi * 2];
+            pi1 = c.pi_in[rgi * 2 + 1];
+        }
+        if ((c.flags & kDumpPi) && c.pi_out) {
+            c.pi_out[rgi * 2] = pi0;
+            c.pi_out[rgi * 2 + 1] = pi1;
+        }
+        pe1 = pi1;
+        if (ACC) {
+            // scale_pi_by_accessibility + add_noise_to_pi, A = 2 (utils.py:106-178)
+            const double kacc = c.kacc[g];
+            const double s1 = pi1 * kacc;
+            const double p1c = fmin(fmax(s1, 1e-3), 1.0 - 1e-3);
+            const double l = flog(p1c * frcp(1.0 - p1c)) + c.lpn[g];
+            const double el = exp(l);
+            const double pn = el * frcp(1.0 + el);
+            pe1 = fmin(fmax(pn, 1e-3), 1.0 - 1e-3);
+        }
+    }
+    const double w0 = MIX ? (ACC ? 1.0 - pe1 : pi0) : 0.0;  // weight of the wild-type component
+    const double w1 = MIX ? (ACC ? pe1 : pi1) : 1.0;        // weight of the edited component
+    const double epsB = kEps / (double)B;
+    const long tcol = c.g2t[g];
+
+#pragma unroll 1
+    for (int lik = 0; lik < 2; ++lik) {
+        if (lik == 1 && !use_bc) break;
+        const float* X = lik ? c.Xbc : c.X;
+        float* out = lik ? s.xbc_out : s.x_out;
+        const double* sf = cst + lik * B;
+        const double a0 = lik ? c.a0_bc[g] : c.a0[g];
+        // pass 1: n = sum x_b (data) and S = sum_b e_b sf_b; the table value is parked in the column
+        double S = 0.0, n = 0.0;
+#pragma unroll 1
+        for (int b = 0; b < B; ++b) {
+            const double p1 = c.tabP[(long)b * c.T + tcol];
+            const double e = fma(w0, MIX ? c_p0[b] : 0.0, w1 * p1);
+            S += e * sf[b];
+            n += (double)X[((long)r * B + b) * G + g];
+            col[b * 64] = p1;
+        }
+        const double inv = frcp(S + kEps);
+        const double ai = a0 * inv;
+#pragma unroll 1
+        for (int b = 0; b < B; ++b) {
+            const double ar = alpha_raw(w0, MIX ? c_p0[b] : 0.0, w1, col[b * 64], sf[b], epsB, ai * c_sm[b]);
+            const double al = ar < kEps ? kEps : ar;
+            col[b * 64] = al;
+            if (s.alpha_out) s.alpha_out[(((long)lik * R + r) * B + b) * G + g] = al;
+        }
+        // ---- p ~ Dirichlet(alpha): gammas two bins at a time, then the cumulative
+        const unsigned long long dl = ctr.step * 2ull + (unsigned long long)lik;
+        double gsum = 0.0;
+#pragma unroll 1
+        for (int b = 0; b < B; b += 2) {
+            const bool two = b + 1 < B;
+            const double al0 = col[b * 64], al1 = two ? col[(b + 1) * 64] : 1.0;
+            Rng rng(c.seed, kSiteSimGamma, sub, (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords);
+            const GammaPair gp = sample_gamma_pair_inl(al0, al1, rng);
+            const double gm0 = fmax(gp.g0, kDblMin);
+            col[b * 64] = gm0;
+            gsum += gm0;
+            if (two) {
+                const double gm1 = fmax(gp.g1, kDblMin);
+                col[(b + 1) * 64] = gm1;
+                gsum += gm1;
+            }
+        }
+        const double rs = frcp(gsum);
+        double cum = 0.0;
+#pragma unroll 1
+        for (int b = 0; b < B; ++b) {
+            cum += col[b * 64] * rs;
+            col[b * 64] = cum;
+            xs[b * 64] = 0.f;
+        }
+        // ---- x_rep ~ Multinomial(n, p): four categorical draws per Philox block
+        const long n_i = (long)n;
+        const long n_blk = (n_i + 3) >> 2;
+        const unsigned long long cat_sub = ((unsigned long long)kSiteSimCat << 48) + sub;
+        const unsigned long long cat_off = dl * kSimCatWords;
+#pragma unroll 1
+        for (long t = 0; t < n_blk; ++t) {
+            const uint4 w = philox_block(c.seed, cat_sub, cat_off + 4ull * (unsigned long long)t);
+            const double u0 = ((double)w.x + 0.5) * 2.3283064365386963e-10;
+            const double u1 = ((double)w.y + 0.5) * 2.3283064365386963e-10;
+            const double u2 = ((double)w.z + 0.5) * 2.3283064365386963e-10;
+            const double u3 = ((double)w.w + 0.5) * 2.3283064365386963e-10;
+            int k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+#pragma unroll 1
+            for (int b = 0; b < B - 1; ++b) {
+                const double cb = col[b * 64];
+                k0 += u0 >= cb ? 1 : 0;
+                k1 += u1 >= cb ? 1 : 0;
+                k2 += u2 >= cb ? 1 : 0;
+                k3 += u3 >= cb ? 1 : 0;
+            }
+            const long rem = n_i - 4 * t;
+            xs[k0 * 64] += 1.f;
+            if (rem > 1) xs[k1 * 64] += 1.f;
+            if (rem > 2) xs[k2 * 64] += 1.f;
+            if (rem > 3) xs[k3 * 64] += 1.f;
+        }
+#pragma unroll 1
+        for (int b = 0; b < B; ++b) out[((long)r * B + b) * G + g] = xs[b * 64];
+    }
+}
+
+}  // namespace bean

@@ -471,7 +471,16 @@ __device__ BEAN_NOINLINE double dirichlet_grad_one_pre(double x, double alpha, d
 // (seed, site, element) through the subsequence and by the SVI step through the
 // offset, so draws do not depend on grid shape or on the number of GPUs.
 // ---------------------------------------------------------------------------
-enum RngSite : unsigned long long { kSiteTarget = 1, kSitePi = 2, kSiteNoise = 3, kSiteAux = 4, kSiteQ0 = 5, kSiteCov = 6 };
+// Sites 1 - 6 belong to the fit.  Sites 7 and 8 belong to the replicate-count simulator (bean_predictive.hpp), which
+// never draws from a fit's site.  Both use subsequence (site << 48) + r G_tot + g_off + g, one per (replicate, guide);
+// the likelihood (0: X, 1: X_bcmatch) and the draw index d go in the offset, counted in 32-bit words:
+//   kSiteSimGamma  offset ((2 d + lik) 32 + pair) 512: bins (2 pair, 2 pair + 1) share one Marsaglia-Tsang loop, which
+//                  reads at most 1 + 64 Philox blocks = 260 words of its 512; 32 pairs hold the 64 conditions of kBCap
+//   kSiteSimCat    offset (2 d + lik) 2^24: categorical draw i of the pair is word i, so totals below 2^24 (the range in
+//                  which float32 counts are exact integers) stay inside their own window
+// so no two (site, replicate, guide, likelihood, draw) streams overlap.
+enum RngSite : unsigned long long { kSiteTarget = 1, kSitePi = 2, kSiteNoise = 3, kSiteAux = 4, kSiteQ0 = 5, kSiteCov = 6,
+                                    kSiteSimGamma = 7, kSiteSimCat = 8 };
 
 // Stateless view of one Philox subsequence: draw k is counter (offset/4 + k), so
 // the generator lives in 7 registers and never touches memory.

@@ -40,6 +40,10 @@ class EnsembleUnsupported(ValueError):
     """``HipSVI(..., n_members=K)`` on a shape the batched kernels do not take (``bean_hip_ensemble_supported``)."""
 
 
+class PredictiveUnsupported(ValueError):
+    """A posterior predictive check on a shape the count simulator does not take (``bean_hip_predictive_supported``)."""
+
+
 def particle_mean(values):
     """Mean of P tensors as a particle step forms it (``include/bean_hip.h``): a float64 accumulator that starts from the
     first and adds the others in order, ONE multiply by ``1.0 / P``, then one rounding to the inputs' dtype."""
@@ -801,6 +805,42 @@ class HipSVI:
     def ensemble_supported(self) -> bool:
         """Whether the batched kernels take this engine's shape (``bean_hip_ensemble_supported``)."""
         return self.lib.bean_hip_ensemble_supported(self._h) == 1
+
+    @property
+    def predictive_supported(self) -> bool:
+        """Whether the count simulator takes this engine (``bean_hip_predictive_supported``): the sorting variant
+        Normal / MixtureNormal families, unsharded, no sample covariates, one member, one particle."""
+        fn = getattr(self.lib, "bean_hip_predictive_supported", None)
+        return fn is not None and fn(self._h) == 1
+
+    def simulate(self, draw: int, seed: int = 101, alphas: bool = False) -> Dict[str, torch.Tensor]:
+        """Replicate counts of one posterior draw (``bean_hip_simulate``): the latent sites of
+        ``elbo_grad(step=draw, seed=seed)`` at the current parameters, then ``p ~ Dirichlet(alpha)`` and
+        ``x_rep ~ Multinomial(n_obs, p)`` for every (replicate, guide).  Returns device tensors: ``X`` (R, B, G)
+        float32, ``X_bcmatch`` where the fit uses the barcode-matched counts, and with ``alphas`` the floored
+        concentrations ``alpha`` (2, R, B, G) float64.  Parameters, moments, gradients and the loss history are left as
+        they are; the next ``run(resume=True)`` is a plain run."""
+        if not self.predictive_supported:
+            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
+                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
+        dev = self.device
+        x = torch.empty((R, B, G), dtype=torch.float32, device=dev)
+        xbc = torch.empty((R, B, G), dtype=torch.float32, device=dev) if self.use_bcmatch else None
+        al = torch.zeros((2, R, B, G), dtype=torch.float64, device=dev) if alphas else None
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
+        with self._on_stream():
+            self._check(self.lib.bean_hip_simulate(self._h, int(seed), int(draw), ptr(x), nb(x), ptr(xbc), nb(xbc),
+                                                   ptr(al), nb(al), self._sptr()), "simulate")
+        self.invalidate_resume()
+        out = {"X": x}
+        if xbc is not None:
+            out["X_bcmatch"] = xbc
+        if al is not None:
+            out["alpha"] = al
+        return out
 
     def run_ensemble(self, n_steps: int, seeds, graph_chunk: int = 50, first_step: Optional[int] = None):
         """Enqueue ``n_steps`` SVI steps of all ``n_members`` fits, member k with ``seeds[k]`` (no host

@@ -402,6 +402,67 @@ def run_inference_sample_jackknife(model, guide, data, by: str = "sample", seed:
     return (results[0], results[1:], *plan.chosen)
 
 
+def _predictive_refusal(spec, data, world: int = 1):
+    """Why the count simulator does not take this model / screen, or None (``bean_hip_predictive_supported``)."""
+    design = getattr(data, "library_design", "variant")
+    if spec.family == "MultiMixtureNormal" or design == "tiling":
+        return "tiling screens (MultiMixtureNormal)"
+    if spec.selection == "survival" or getattr(data, "selection", "sorting") == "survival":
+        return f"survival screens ({spec.family})"
+    if spec.family == "ControlNormal":
+        return "the negative-control model (ControlNormal)"
+    if getattr(data, "sample_covariates", None) is not None:
+        return f"screens with sample covariates ({spec.family})"
+    if world > 1:
+        return f"guide-sharded fits over {world} ranks ({spec.family})"
+    return None
+
+
+def load_parameters(eng: HipSVI, param_store) -> None:
+    """Write the constrained values of ``param_store`` (what ``run_inference`` returns, or the ``params`` of a
+    ``--save-raw`` pickle that ``--load-existing`` reads) into the engine's unconstrained parameter tensors.  The draw
+    and tables a previous window left on the device belong to other values: the chain of resumed windows is broken."""
+    from ..engine import POSITIVE
+
+    for name, dst in eng.unconstrained.items():
+        if name not in param_store:
+            raise ValueError(f"the parameter store has no {name!r}: it is not a fit of this model")
+        v = torch.as_tensor(param_store[name]).detach().to(dst.device, torch.float32)
+        if v.numel() != dst.numel():
+            raise ValueError(f"parameter {name!r} has {v.numel()} entries, this screen needs {dst.numel()}")
+        dst.copy_((v.log() if name in POSITIVE else v).reshape(dst.shape))
+    eng.invalidate_resume()
+
+
+def run_posterior_predictive(model, guide, data, param_store, n_draws: int = 200, seed: int = SEED):
+    """Posterior predictive check of a fit (``model/predictive.py``): an engine for ``data`` with the fitted parameters
+    of ``param_store`` loaded, ``n_draws`` replicate screens drawn on the device from guide and likelihood, and the
+    summary of their discrepancy statistics against the observed counts (a dict of device tensors).
+
+    Raises ``PredictiveUnsupported`` - the message names the family - for tiling and survival screens,
+    ``ControlNormal``, sample covariates and several ranks."""
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+    from .predictive import posterior_predictive
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _predictive_refusal(spec, data, world)
+    if why is not None:
+        raise PredictiveUnsupported(f"a posterior predictive check is not available for {why}: the count simulator "
+                                    "serves the sorting variant Normal and MixtureNormal models on one GPU")
+    device = torch.device("cuda", torch.cuda.current_device())
+    eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
+    try:
+        load_parameters(eng, param_store)
+        summary = posterior_predictive(eng, n_draws=n_draws, seed=seed)
+        torch.cuda.synchronize(device)
+    finally:
+        eng.close()
+    return summary
+
+
 def identify_model_guide(args):
     """Model label and (model, guide) descriptors for the parsed ``bean run``
     arguments (``bean/model/run.py:399-457``), including the reference's

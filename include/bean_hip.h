@@ -366,6 +366,37 @@ int bean_hip_set_particles(bean_hip_ctx* ctx, int32_t n_particles);
 int bean_hip_svi_run_particles(bean_hip_ctx* ctx, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
                                uint64_t n_steps, int32_t graph_chunk, void* stream);
 
+/* Posterior predictive check: replicate counts drawn on the device from the handle's current parameters.
+ *
+ *   bean_hip_predictive_supported 1 if the count simulator takes this handle, 0 if not: the sorting variant families
+ *                                 k_guide_wave2 serves (Normal, MixtureNormal with or without accessibility scaling /
+ *                                 fit_noise / X_bcmatch / --prior-params), unsharded, no sample covariates, on a
+ *                                 single-fit handle (n_members == 1 and n_particles == 1), whichever stepping path the
+ *                                 handle's size selects.  Not: tiling, survival, ControlNormal.
+ *   bean_hip_simulate             draws the latent sites of "draw `draw`" - bit for bit the draws of
+ *                                 bean_hip_elbo_grad(seed, step = draw), injected noise (*_IN slots) honoured the same
+ *                                 way - forms the Dirichlet-Multinomial concentrations of every (replicate, guide) as
+ *                                 the ELBO does, and draws p ~ Dirichlet(alpha), x_rep ~ Multinomial(n_obs, p) with
+ *                                 n_obs the pair's observed total; masked pairs are simulated like any other.
+ *                                 x_out: (R, B, G) float32, the layout of BEAN_BUF_X (and of one member of
+ *                                 bean_hip_bind_member_counts); xbc_out: the same for X_bcmatch, required exactly when the
+ *                                 handle was created with BEAN_FLAG_USE_BCMATCH and null (0 bytes) otherwise; alpha_out:
+ *                                 null (0 bytes) or (2, R, B, G) float64, the floored concentrations of both
+ *                                 likelihoods (plane 1 is written only with BEAN_FLAG_USE_BCMATCH).  All three are device
+ *                                 memory of the caller.  The same (seed, draw) gives the same bits.  The call writes
+ *                                 no parameter, moment, gradient, loss_hist entry or loss accumulator; it overwrites
+ *                                 the workspace's draws and tables, so a following bean_hip_svi_resume does not
+ *                                 continue an earlier window and bean_hip_svi_run starts from its own first draw, as
+ *                                 after bean_hip_elbo_grad.  No graph is built or replayed.  The time is proportional
+ *                                 to the largest n_obs of each 64-guide tile.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched): a null handle; a handle that is not
+ * supported or not prepared; byte counts other than 4 R B G (x_out, xbc_out) and 16 R B G (alpha_out); xbc_out on a
+ * handle without BEAN_FLAG_USE_BCMATCH or without it on a handle with the flag.  The handle stays usable. */
+int bean_hip_predictive_supported(const bean_hip_ctx* ctx);
+int bean_hip_simulate(bean_hip_ctx* ctx, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes, void* xbc_out,
+                      uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
