@@ -3362,6 +3362,9 @@ __global__ __launch_bounds__(256) void k_test_special(int op, long n, const doub
         const GammaPair gp = op == 8 ? sample_gamma_pair(a[i], b[i], rng) : sample_gamma_pair_floord(a[i], b[i], rng);
         o0[i] = fmax(gp.g0, kDblMin);
         o1[i] = fmax(gp.g1, kDblMin);
+    } else if (op == 10) {
+        // the form the product kernels call, handed the device's own digammas (must equal op 2 bit for bit)
+        o0[i] = dirichlet_grad_one_pre(x[i], a[i], b[i], digamma(a[i]), digamma(b[i]));
     }
 }
 

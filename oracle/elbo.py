@@ -169,6 +169,10 @@ def _finish(model_lp: Dict[str, torch.Tensor], guide_lp: Dict[str, torch.Tensor]
     if record is not None:
         record["model"] = {k: float(v.detach()) for k, v in model_lp.items()}
         record["guide"] = {k: float(v.detach()) for k, v in guide_lp.items()}
+        if record.get("keep_terms"):
+            # on request the site terms themselves, still attached to the graph (tests/grad_bounds.py
+            # differentiates each site on its own)
+            record["terms"] = {"model": dict(model_lp), "guide": dict(guide_lp)}
     return -elbo
 
 

@@ -128,7 +128,7 @@ def mixture_normal_loss(data, params, noise=None, use_bcmatch=True, scale_by_acc
     u = _noise(noise, "mu_negctrl")
     if u is None:
         u = neg.sample((G,))
-    u = u.to(neg.loc.dtype)
+    u = u.to(torch.promote_types(neg.loc.dtype, P["mu_loc"].dtype))  # (float32 as sampled; kept wider by the float64 checking mode)
     model_lp["mu_negctrl"] = neg.log_prob(u).sum()
     mu_edit = torch.repeat_interleave(mu_t, data.target_lengths, dim=0)
     mu = torch.cat([u.unsqueeze(-1), mu_edit + u.unsqueeze(-1)], -1)  # (G, 2)
@@ -221,7 +221,7 @@ def multi_mixture_normal_loss(data, params, noise=None, use_bcmatch=True, scale_
     u = _noise(noise, "mu_negctrl")
     if u is None:
         u = neg.sample((G,))
-    u = u.to(neg.loc.dtype)
+    u = u.to(torch.promote_types(neg.loc.dtype, P["mu_loc"].dtype))  # (float32 as sampled; kept wider by the float64 checking mode)
     model_lp["mu_negctrl"] = neg.log_prob(u).sum()
     mu_a = torch.matmul(a2e, mu_e)  # (G, A - 1)
     mu = torch.cat([u.unsqueeze(-1), u.unsqueeze(-1) + mu_a], -1)  # (G, A)
