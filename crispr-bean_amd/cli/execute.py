@@ -77,6 +77,16 @@ def get_parser():
                           "screens only; the --fit-negctrl control fit is not checked.  Default 0: off.")
     own.add_argument("--predictive-seed", dest="predictive_seed", type=int, default=101,
                      help="Seed of the draws of --posterior-predictive (default 101).")
+    own.add_argument("--bootstrap", dest="bootstrap", type=_non_negative_int, default=0, metavar="K",
+                     help="Parametric bootstrap: after the fit of the screen, draw K screens from the fitted model on the "
+                          "GPU (mu, sd and the guide noise at their fitted locations; fresh pi, Dirichlet and count draws; "
+                          "masks, size factors, a0, pi_a0 and every guide's total as observed), refit each with the same "
+                          "seed and report, per target, the spread and the mean shift of mu over the refits: columns "
+                          "mu_boot_se / mu_boot_bias / n_boot, on the scale of the column mu - a frequentist spread to "
+                          "hold mu_sd against.  K >= 2; sorting variant screens only; not combined with --n-seeds > 1, any "
+                          "--jackknife-* flag, --num-particles > 1 or --load-existing.  Default 0: off.")
+    own.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=101,
+                     help="Seed of the simulated screens of --bootstrap (default 101).")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))

@@ -64,19 +64,34 @@ _SAME_SEED = "{flag} fits every member with the same seed and does not combine w
 _TWO_RUNS = "{flag} and {other} are two runs: they do not combine in one."
 _NEEDS_FITS = "{{flag}} needs the leave-one-{}out fits and does not combine with --load-existing."
 _SAMPLE_RULES = (("jackknife_replicates", _TWO_RUNS), ("jackknife_guides", _TWO_RUNS), ("n_seeds", _SAME_SEED),
-                 ("load_existing", _NEEDS_FITS.format("")))
+                 ("load_existing", _NEEDS_FITS.format("")), ("bootstrap", _TWO_RUNS))
+_BOOTSTRAP_FAMILY = ("{{flag}} simulates the counts of the sorting variant models (Normal, MixtureNormal) and is not "
+                     "available for {}.")
 # the flags that ask for a member set, in the order their refusals are reported:
 # (attribute, mode, ((what it does not combine with, sentence), ...))
 MEMBER_FLAGS = (
     ("jackknife_replicates", "replicates", (("n_seeds", _SAME_SEED),
-                                            ("load_existing", _NEEDS_FITS.format("replicate-")))),
+                                            ("load_existing", _NEEDS_FITS.format("replicate-")),
+                                            ("bootstrap", _TWO_RUNS))),
     ("jackknife_guides", "guides", (("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS),
                                     ("load_existing", _NEEDS_FITS.format("guide-")),
-                                    ("tiling", "{flag} needs targets that own their guides and does not combine with tiling."))),
+                                    ("tiling", "{flag} needs targets that own their guides and does not combine with tiling."),
+                                    ("bootstrap", _TWO_RUNS))),
     ("jackknife_samples", "sample", (("jackknife_conditions", _TWO_RUNS),) + _SAMPLE_RULES),
     ("jackknife_conditions", "condition", (("jackknife_samples", _TWO_RUNS),) + _SAMPLE_RULES),
+    ("bootstrap", "bootstrap", (("bootstrap_one", "{flag} needs at least 2 screens."),
+                                ("tiling", _BOOTSTRAP_FAMILY.format("tiling screens (MultiMixtureNormal)")),
+                                ("survival", _BOOTSTRAP_FAMILY.format("survival screens")),
+                                ("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS),
+                                ("jackknife_guides", _TWO_RUNS), ("jackknife_samples", _TWO_RUNS),
+                                ("jackknife_conditions", _TWO_RUNS),
+                                ("load_existing", "{flag} needs the refits of its simulated screens and does not combine "
+                                                  "with --load-existing."))),
 )
 _IS_SET = {"n_seeds": lambda args: int(getattr(args, "n_seeds", 1) or 1) > 1,
+           "bootstrap": lambda args: int(getattr(args, "bootstrap", 0) or 0) > 0,
+           "bootstrap_one": lambda args: int(getattr(args, "bootstrap", 0) or 0) == 1,
+           "survival": lambda args: getattr(args, "selection", None) == "survival",
            "tiling": lambda args: getattr(args, "library_design", None) == "tiling",
            "guides_max": lambda args: int(getattr(args, "jackknife_guides_max", 63)) > 63}
 
@@ -86,7 +101,8 @@ def _refuse(message):
 
 
 def member_mode(args, fail=_refuse, only=None, parser_rules=None):
-    """The member set this run fits next to the screen: None, "seeds", "replicates", "guides", "sample" or "condition".
+    """The member set this run fits next to the screen: None, "seeds", "replicates", "guides", "sample", "condition" or
+    "bootstrap".
     A combination that is refused goes to ``fail(sentence)`` (the parser's ``error``; here, raising ``ValueError``).
     ``only``: the flags whose rules are looked at (default: all); ``parser_rules``: further rules per flag, after its own."""
     is_set = lambda attr: _IS_SET.get(attr, lambda a: bool(getattr(a, attr, False)))(args)  # noqa: E731
@@ -213,11 +229,18 @@ def _sample_members(fit, ndata, args, guide_names):
             {"sample_jackknife": jk.sample_jackknife_summary(full, loo, groups, names)})
 
 
+def _bootstrap_members(fit, ndata, args, guide_names):
+    full, boots = fit(model_run.run_inference_bootstrap, n_boot=int(args.bootstrap),
+                      boot_seed=int(getattr(args, "bootstrap_seed", model_run.SEED)))
+    return (full, _entries([{"screen": j} for j in range(len(boots))], boots),
+            {"bootstrap": jk.bootstrap_summary(full, boots)})
+
+
 # mode -> (what fits its members and returns (the fit the tables come from, the members' entry of the --save-raw
 #          pickle, write_result_table's keywords for their summary), the key of that entry)
 MEMBER_RUNS = {"seeds": (_seed_members, "ensemble"), "replicates": (_replicate_members, "jackknife"),
                "guides": (_guide_members, "guide_jackknife"), "sample": (_sample_members, "sample_jackknife"),
-               "condition": (_sample_members, "sample_jackknife")}
+               "condition": (_sample_members, "sample_jackknife"), "bootstrap": (_bootstrap_members, "bootstrap")}
 
 
 def main(args, return_data=False):

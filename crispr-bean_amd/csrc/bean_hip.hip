@@ -2762,3 +2762,48 @@ extern "C" int bean_hip_simulate(bean_hip_ctx* c, uint64_t seed, uint64_t draw, 
     HIP_OK(hipGetLastError());
     return 0;
 }
+
+// K replicate screens in one launch (k_simulate_members: a parametric bootstrap's screens, member-major - what
+// bean_hip_bind_member_counts binds).  The target / guide sites are those of draw first_draw, member k's pi, Dirichlet
+// and categorical draws those of draw first_draw + k.
+extern "C" int bean_hip_simulate_members(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                         void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes,
+                                         void* stream_) {
+    if (!c) return fail("bean_hip_simulate_members: null handle");
+    if (!predictive_shape_ok(c))
+        return fail("bean_hip_simulate_members: the count simulator does not take this handle "
+                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
+                    "covariates, one member, one particle");
+    if (!c->prepared) return fail("bean_hip_simulate_members: call bean_hip_prepare first");
+    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_MEMBERS)
+        return fail("bean_hip_simulate_members: n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) +
+                    "], got " + std::to_string(n_draws));
+    if (check_bound(c, false, false)) return -1;
+    const DevArgs& d0 = c->d;
+    const uint64_t n = (uint64_t)n_draws * d0.R * d0.B * d0.G;
+    const bool use_bc = (d0.flags & kUseBc) != 0;
+    const std::string shape = "(K, R, B, G) float32 with K = " + std::to_string(n_draws) + ", " + std::to_string(4 * n) +
+                              " bytes";
+    if (!x_out || x_bytes != 4 * n) return fail("bean_hip_simulate_members: x_out must hold " + shape);
+    if (use_bc && (!xbc_out || xbc_bytes != 4 * n))
+        return fail("bean_hip_simulate_members: this handle uses the barcode-matched counts: xbc_out must hold " + shape);
+    if (!use_bc && (xbc_out || xbc_bytes))
+        return fail("bean_hip_simulate_members: xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
+    hipStream_t stream = (hipStream_t)stream_;
+    c->d.seed = seed;
+    c->resume_ok = false;  // the workspace now holds draw first_draw and its tables
+    launch_set_step(c, stream, first_draw, 0, 0);
+    launch_param<false, false, true>(c, stream);
+    const DevArgs& d = c->d;
+    SimArgs sa;
+    sa.x_out = (float*)x_out;
+    sa.xbc_out = (float*)xbc_out;
+    sa.alpha_out = nullptr;
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)n_draws), block(64);
+    const size_t lds = simulate_wave2_lds(d.B);
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_simulate_members<fam(), acc()>), grid, block, lds, stream, d, sa);
+    });
+    HIP_OK(hipGetLastError());
+    return 0;
+}

@@ -1,4 +1,5 @@
-// k_simulate_wave2: replicate counts of the variant sorting families, drawn on the device (posterior predictive check).
+// k_simulate_wave2: replicate counts of the variant sorting families, drawn on the device (posterior predictive check);
+// k_simulate_members (at the end): K such screens in one launch, the member on blockIdx.y (parametric bootstrap).
 //
 // For one draw d of the latent sites - the draw bean_hip_elbo_grad(seed, step = d) evaluates, prepared by the same
 // k_set_step + PREP k_param launches - every (replicate, guide) forms the Dirichlet-Multinomial concentrations of its
@@ -46,12 +47,14 @@ __host__ __device__ inline size_t simulate_wave2_lds(int B) {
     return ((size_t)4 * B + (size_t)B * 64) * sizeof(double) + (size_t)B * 64 * sizeof(float);
 }
 
+// The per-lane body of both simulators: the workgroup blockIdx.x of one screen, drawn as draw `ctr.step` into the
+// planes of `s`.  `dump_pi` gates the BEAN_FLAG_DUMP_PI write (one screen has one pi_out).  One function, so that a plane
+// of k_simulate_members is bit for bit the screen k_simulate_wave2 leaves for the same draw (as guide_pair_math is the
+// one body of the guide kernels).
 template <int FAM, bool ACC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
-void k_simulate_wave2(DevArgs c, SimArgs s) {
+__device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimArgs& s, const StepCtr& ctr, double* sim_lds,
+                                                   const bool dump_pi) {
     constexpr bool MIX = FAM == kMixture;
-    extern __shared__ double sim_lds[];
-    const StepCtr ctr = *c.ctrB;
     const int wg = blockIdx.x;
     const int kk = wg >> 3;
     const int r = kk % c.R;
@@ -93,7 +96,7 @@ void k_simulate_wave2(DevArgs c, SimArgs s) {
             pi0 = c.pi_in[rgi * 2];
             pi1 = c.pi_in[rgi * 2 + 1];
         }
-        if ((c.flags & kDumpPi) && c.pi_out) {
+        if (dump_pi && (c.flags & kDumpPi) && c.pi_out) {
             c.pi_out[rgi * 2] = pi0;
             c.pi_out[rgi * 2 + 1] = pi1;
         }
@@ -196,6 +199,37 @@ void k_simulate_wave2(DevArgs c, SimArgs s) {
 #pragma unroll 1
         for (int b = 0; b < B; ++b) out[((long)r * B + b) * G + g] = xs[b * 64];
     }
+}
+
+template <int FAM, bool ACC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
+void k_simulate_wave2(DevArgs c, SimArgs s) {
+    extern __shared__ double sim_lds[];
+    const StepCtr ctr = *c.ctrB;
+    simulate_pair_body<FAM, ACC>(c, s, ctr, sim_lds, true);
+}
+
+// k_simulate_members: K replicate screens of one fit in one launch (a parametric bootstrap's screens).  gridDim.x as
+// k_simulate_wave2, gridDim.y = K; blockIdx.y is the member (the convention of bean_ensemble.hpp), so a single-wave
+// workgroup is 64 guides of one replicate of one member.  The per-target and per-guide Normal sites, the tables and lpn
+// are those of the ONE PREP k_param launch (draw ctrB->step, or the injected values); member k's per-(replicate, guide)
+// sites - the pi draw, the gammas, the categorical draws - use draw ctrB->step + k wherever k_simulate_wave2 uses
+// ctr.step: a StepCtr copy with that step is all simulate_pair_body and guide_pair_draw read.  Member k writes plane k of
+// x_out / xbc_out, (K, R, B, G) member-major: what bean_hip_bind_member_counts binds.  pi_in is every member's; with
+// BEAN_FLAG_DUMP_PI member 0 alone writes pi_out.  LDS, scratch, atomics and stores as k_simulate_wave2.
+template <int FAM, bool ACC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
+void k_simulate_members(DevArgs c, SimArgs s) {
+    extern __shared__ double sim_lds[];
+    StepCtr ctr = *c.ctrB;
+    const unsigned member = blockIdx.y;
+    ctr.step += (unsigned long long)member;
+    const size_t plane = (size_t)member * (size_t)c.R * (size_t)c.B * (size_t)c.G;
+    SimArgs sm;
+    sm.x_out = s.x_out + plane;
+    sm.xbc_out = s.xbc_out ? s.xbc_out + plane : nullptr;
+    sm.alpha_out = nullptr;
+    simulate_pair_body<FAM, ACC>(c, sm, ctr, sim_lds, member == 0);
 }
 
 }  // namespace bean

@@ -842,6 +842,34 @@ class HipSVI:
             out["alpha"] = al
         return out
 
+    def simulate_members(self, first_draw: int, n_draws: int, seed: int = 101) -> Dict[str, torch.Tensor]:
+        """``n_draws`` replicate screens in one launch (``bean_hip_simulate_members``): ``X`` (K, R, B, G) float32 and,
+        where the fit uses the barcode-matched counts, ``X_bcmatch`` - device tensors, member-major, what
+        ``HipSVI(member_counts=...)`` binds.  The per-target and per-guide Normal sites are those of draw ``first_draw``
+        (or the injected ones, ``set_noise``) for every member; member k's pi, Dirichlet and categorical draws are
+        those of draw ``first_draw + k``: plane 0 is ``simulate(first_draw)``, and with every Normal site injected plane
+        k is ``simulate(first_draw + k)``, bit for bit.  Leaves the fit alone as ``simulate`` does; the next
+        ``run(resume=True)`` is a plain run."""
+        if not self.predictive_supported:
+            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
+                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        K = int(n_draws)
+        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
+        shape = (max(K, 0), R, B, G)
+        x = torch.empty(shape, dtype=torch.float32, device=self.device)
+        xbc = torch.empty(shape, dtype=torch.float32, device=self.device) if self.use_bcmatch else None
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
+        with self._on_stream():
+            self._check(self.lib.bean_hip_simulate_members(self._h, int(seed), int(first_draw), K, ptr(x), nb(x), ptr(xbc),
+                                                           nb(xbc), self._sptr()), "simulate_members")
+        self.invalidate_resume()
+        out = {"X": x}
+        if xbc is not None:
+            out["X_bcmatch"] = xbc
+        return out
+
     def run_ensemble(self, n_steps: int, seeds, graph_chunk: int = 50, first_step: Optional[int] = None):
         """Enqueue ``n_steps`` SVI steps of all ``n_members`` fits, member k with ``seeds[k]`` (no host
         synchronisation).  Member k is, bit for bit, a single engine's ``run(n_steps, seed=seeds[k])``;

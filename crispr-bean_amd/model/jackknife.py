@@ -27,6 +27,13 @@ The counts matter: the (replicate, guide) site of a masked sample stays on, and 
 bin whatever the sample mask says, so the members of such a jackknife differ in their data, not in their masks alone
 (``sample_member_masks``, ``sample_member_counts``, ``sample_jackknife_summary``).
 
+Parametric bootstrap: how far would ``mu`` move if the experiment were repeated under the fitted model
+(``run_inference_bootstrap``, ``bean run --bootstrap K``).
+
+K screens drawn from the fitted model on the device (``HipSVI.simulate_members``) and refitted with the screen's seed:
+``bootstrap_plan``, ``bootstrap_summary``.  The members differ in their counts alone; everything derived from the observed
+screen is conditioned on.
+
 Each of these, and the seed ensemble, is K fits of one screen: a ``MemberPlan``, fitted by ``model/run.py::_fit_plan``.
 
 Pure torch: no GPU involved in this file.
@@ -415,3 +422,49 @@ def sample_jackknife_summary(full, loo, groups, names: Sequence) -> Dict[str, ob
     }
     return {"mu_sjk_max_shift": far, "mu_sjk_max_shift_sample": [str(names[int(j)]) for j in worst], "n_sjk": n,
             "influence": influence}
+
+
+# ---------------------------------------------------------------- parametric bootstrap
+def bootstrap_plan(data, seed, x, x_bcmatch=None) -> MemberPlan:
+    """A parametric bootstrap: member 0 is the screen, member 1 + j a ``copy.copy(data)`` whose ``X_masked`` is plane j
+    of ``x`` (K, R, B, G) and, where ``x_bcmatch`` is given, whose ``X_bcmatch_masked`` is plane j of it - the screens
+    ``HipSVI.simulate_members`` drew from the fitted model.
+
+    Conditioned on: everything else is the observed screen's, shared with ``data`` - both masks, the size factors,
+    ``a0`` / ``a0_bcmatch``, ``pi_a0`` and the control allele counts it derives from, and every (replicate, guide)
+    total (the simulator keeps them).  The bootstrap answers "how far does mu move when the sorted counts are redrawn at
+    this depth, dispersion and prior", not what re-deriving those from each redrawn screen would add.
+
+    Every member gets ``seed``: common random numbers, so the members differ through their data and not through the
+    stream.  An engine run holds the screen and at most 63 bootstrap screens.  ``data`` is not modified."""
+    seed = int(seed)
+    K = int(x.shape[0])
+    if x_bcmatch is not None and tuple(x_bcmatch.shape) != tuple(x.shape):
+        raise ValueError(f"x_bcmatch has shape {tuple(x_bcmatch.shape)}, x {tuple(x.shape)}")
+
+    def screen(data, j):
+        out = copy.copy(data)
+        out.X_masked = x[j]
+        if x_bcmatch is not None:
+            out.X_bcmatch_masked = x_bcmatch[j]
+        return out
+
+    return _leave_one_out_plan(data, seed, list(range(K)), label=lambda j: f"bootstrap screen {j}",
+                               tag=lambda j: f"bootstrap{j}", key="bootstrap", value=lambda j: j, leave=screen,
+                               differ_in=("masks", "counts"), per_run=MAX_GUIDE_POSITIONS, label_halts=True)
+
+
+def bootstrap_summary(full, boots) -> Dict[str, object]:
+    """Parametric-bootstrap summary of ``mu_loc`` (float64).  With ``m_j`` the ``mu_loc`` of ``boots[j]``:
+
+    * ``mu_boot_se``: the standard deviation of ``m_j`` over j, unbiased (n - 1) - the frequentist spread the
+      mean-field ``mu_sd`` can be held against;
+    * ``mu_boot_bias = mean_j m_j - mu_loc_full``;
+    * ``n_boot = len(boots)``.
+
+    Fewer than two fits are a ``ValueError``."""
+    n = len(boots)
+    if n < 2:
+        raise ValueError(f"bootstrap_summary needs at least two bootstrap fits, got {n}")
+    m = torch.stack([_mu_loc(r) for r in boots])
+    return {"mu_boot_se": m.std(0, unbiased=True), "mu_boot_bias": m.mean(0) - _mu_loc(full), "n_boot": n}

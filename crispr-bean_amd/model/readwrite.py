@@ -154,13 +154,13 @@ def _flat(v) -> np.ndarray:
     return np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)
 
 
-def _add_summary_columns(element: pd.DataFrame, summary: dict, what: str, numeric: Sequence[str], names: str, count: str,
-                         count_per_target: bool = False) -> None:
+def _add_summary_columns(element: pd.DataFrame, summary: dict, what: str, numeric: Sequence[str], names: Optional[str],
+                         count: str, count_per_target: bool = False) -> None:
     """A member set's summary into the element table, in place and in this order: its ``numeric`` columns, its column
-    of ``names`` and its ``count`` (one number or, ``count_per_target``, an int64 per target).  Every per-target entry
-    must have the table's length."""
+    of ``names`` (``None``: the set has none) and its ``count`` (one number or, ``count_per_target``, an int64 per
+    target).  Every per-target entry must have the table's length."""
     n = [int(summary[count])] * len(element) if not count_per_target else _flat(summary[count]).astype(np.int64)
-    columns = {**{k: _flat(summary[k]) for k in numeric}, names: list(summary[names]), count: n}
+    columns = {**{k: _flat(summary[k]) for k in numeric}, **({names: list(summary[names])} if names else {}), count: n}
     if any(len(v) != len(element) for v in columns.values()):
         raise ValueError(f"{what} has {len(columns[numeric[0]])} entries for {len(element)} targets")
     for k, v in columns.items():
@@ -187,6 +187,7 @@ def write_result_table(
     jackknife: Optional[dict] = None,
     guide_jackknife: Optional[dict] = None,
     sample_jackknife: Optional[dict] = None,
+    bootstrap: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -212,7 +213,11 @@ def write_result_table(
     exactly the columns ``mu_sjk_max_shift``, ``mu_sjk_max_shift_sample`` and ``n_sjk`` (on the scale of ``mu``, not
     rescaled), and the summary's influence table - one row per left-out sample or condition - is written next to the
     element table as ``bean_sample_influence.<model_label><suffix>.csv``, also with ``return_result``.  With ``None``
-    both tables are byte for byte what they were and no third one is written."""
+    both tables are byte for byte what they were and no third one is written.
+
+    ``bootstrap`` (a parametric bootstrap, ``model/jackknife.py::bootstrap_summary``): the element table gets exactly
+    the columns ``mu_boot_se``, ``mu_boot_bias`` and ``n_boot`` (on the scale of ``mu``, not rescaled); every other
+    column and the sgRNA table are those of the run without it."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -237,6 +242,8 @@ def write_result_table(
     if sample_jackknife is not None:
         _add_summary_columns(element, sample_jackknife, "the sample jackknife summary", ("mu_sjk_max_shift",),
                              "mu_sjk_max_shift_sample", "n_sjk")
+    if bootstrap is not None:
+        _add_summary_columns(element, bootstrap, "the bootstrap summary", ("mu_boot_se", "mu_boot_bias"), None, "n_boot")
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

@@ -18,8 +18,8 @@ import torch
 
 from ..engine import HipSVI
 from . import model as sorting_model
-from .jackknife import (guide_plan, particle_seeds, replicate_plan, sample_plan, seed_plan, stack_counts,  # noqa: F401
-                        stack_masks)
+from .jackknife import (bootstrap_plan, guide_plan, particle_seeds, replicate_plan, sample_plan, seed_plan,  # noqa: F401
+                        stack_counts, stack_masks)
 from .model import ModelSpec
 
 logger = logging.getLogger(__name__)
@@ -461,6 +461,99 @@ def run_posterior_predictive(model, guide, data, param_store, n_draws: int = 200
     finally:
         eng.close()
     return summary
+
+
+def bootstrap_engine(model, guide, data, param_store) -> HipSVI:
+    """The engine a parametric bootstrap draws its screens from: built for ``data`` as ``run_posterior_predictive``
+    builds its own, the fitted parameters of ``param_store`` loaded, and zero standard-normal draws injected into every
+    per-target and per-guide Normal site the family has (``mu``, ``sd`` and, with accessibility scaling, the guide noise
+    site) - the plug-in: the global latents sit at their guide's locations, only the per-(replicate, guide) ``pi`` draws
+    and the counts are fresh per screen.  The caller closes it."""
+    device = torch.device("cuda", torch.cuda.current_device())
+    eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
+    try:
+        load_parameters(eng, param_store)
+        zeros = lambda n: torch.zeros(int(n), dtype=torch.float64, device=device)  # noqa: E731
+        noise = {"eps_mu": zeros(eng.T), "eps_sd": zeros(eng.T)}
+        if eng.scale_by_accessibility:
+            noise["eps_noise"] = zeros(data.n_guides)
+        eng.set_noise(noise)
+    except BaseException:
+        eng.close()
+        raise
+    return eng
+
+
+def bootstrap_screens(eng: HipSVI, n_boot: int, boot_seed: int = SEED):
+    """``(X (n_boot, R, B, G), X_bcmatch or None)``, device tensors: screen j is draw j of
+    ``eng.simulate_members(..., seed=boot_seed)`` whatever the batching - calls of at most ``MAX_MEMBERS`` screens, each
+    starting at the number of screens already drawn."""
+    from .._lib import MAX_MEMBERS
+
+    xs, xbcs = [], []
+    done = 0
+    while done < n_boot:
+        k = min(MAX_MEMBERS, n_boot - done)
+        sim = eng.simulate_members(done, k, seed=boot_seed)
+        xs.append(sim["X"])
+        if "X_bcmatch" in sim:
+            xbcs.append(sim["X_bcmatch"])
+        done += k
+    return torch.cat(xs), (torch.cat(xbcs) if xbcs else None)
+
+
+def run_inference_bootstrap(model, guide, data, n_boot: int = 32, seed: int = SEED, boot_seed: int = SEED, initial_lr=0.01,
+                            gamma=0.1, num_steps=2000, report_every: int = 100, verbose: bool = True,
+                            max_per_run: int = 63):
+    """Parametric bootstrap: fit the screen, draw ``n_boot`` screens from the fitted model on the device, and refit
+    every one of them with the same ``seed`` (``model/jackknife.py::bootstrap_plan``) - how far would ``mu`` move if the
+    experiment were repeated under the model just fitted.
+
+    The screens come from the plug-in (``bootstrap_engine``): ``mu``, ``sd`` and the guide noise at their fitted
+    locations; per (replicate, guide) a fresh ``pi ~ q(pi)``, ``p ~ Dirichlet(alpha)`` and ``x ~ Multinomial(n_obs, p)``
+    with the streams of ``boot_seed``, screen j being draw j.  Masks, size factors, ``a0``, ``pi_a0``, the control allele
+    counts and every (replicate, guide) total are the observed screen's: the bootstrap conditions on them.
+
+    Returns ``(full, boots)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns, ``boots[j]`` exactly
+    what it returns for the screen with the counts of draw j - bit for bit.  The refits are members of one engine next
+    to the screen, at most ``max_per_run`` (1 ... 63) per engine run, where the batched kernels take the shape; else one
+    after the other (``_fit_plan``).  Raises ``PredictiveUnsupported`` - the message names the family - for tiling and
+    survival screens, ``ControlNormal``, sample covariates and several ranks; ``n_boot < 2`` is a ``ValueError``.  A
+    non-finite loss of any member halts the fit; message and dump file (``tmp_result.full.pkl`` /
+    ``tmp_result.bootstrap<j>.pkl``, with ``"bootstrap": j``) name the screen."""
+    import dataclasses
+
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+    from .jackknife import MAX_GUIDE_POSITIONS
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _predictive_refusal(spec, data, world)
+    if why is not None:
+        raise PredictiveUnsupported(f"a parametric bootstrap is not available for {why}: the count simulator serves the "
+                                    "sorting variant Normal and MixtureNormal models on one GPU")
+    n_boot, per_run = int(n_boot), int(max_per_run)
+    if n_boot < 2:
+        raise ValueError(f"a parametric bootstrap needs at least 2 screens, got {n_boot}")
+    if not 1 <= per_run <= MAX_GUIDE_POSITIONS:
+        raise ValueError(f"max_per_run must be in [1, {MAX_GUIDE_POSITIONS}] (the screen is member 0 of every run), "
+                         f"got {per_run}")
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+    first = run_inference(model, guide, data, seed=seed, report_every=report_every, verbose=verbose, **common)
+    eng = bootstrap_engine(model, guide, data, first[0])
+    try:
+        x, x_bc = bootstrap_screens(eng, n_boot, boot_seed)
+        torch.cuda.synchronize(eng.device)
+    finally:
+        eng.close()
+    home = lambda t, like: None if t is None else t.to(like.device, like.dtype)  # noqa: E731
+    plan = bootstrap_plan(data, seed, home(x, data.X_masked),
+                          home(x_bc, data.X_bcmatch_masked) if x_bc is not None else None)
+    plan = dataclasses.replace(plan, per_run=per_run)
+    results = _fit_plan(model, guide, data, plan, common, report_every, verbose)
+    return results[0], results[1:]
 
 
 def identify_model_guide(args):
