@@ -37,12 +37,43 @@
 // chains side by side instead of two; same bits): 50.4 - 51.5 us against 50.7 - two chains already issue a float64
 // instruction every ~5.5 cycles, the pipe's rate for one wave.)
 //
-// Where a wave's time goes at the metric shape, two waves per SIMD (scripts/async_timeline.py, a -DBEAN_ASYNC_STAMP
-// build; medians): an item waits 1.2 us for its dependencies (the poll's own round trip), computes for 19.1 us (a lone
-// wave's chain: the SIMD's second wave fills 65 % of its issue slots), drains its stores and arrives in 1.4 us; one
-// item in five then finishes its tile in 18.8 us - the call and the boundary counters 3.6, sums / ClippedAdam / draw
-// 4.7, Phi tables 2.8, the guides' alpha_pi and digamma tables 5.0, loss parts + store drain + publish 2.8.  A wave is
-// busy for 90 - 93 % of a step.
+// Where a wave's time goes at the metric shape, two item waves per SIMD and finisher roles (scripts/async_timeline.py, a
+// -DBEAN_ASYNC_STAMP build; medians, profiles/r07_async_timeline_50000_*.json): from the pull to "dependencies seen" 2.3 us -
+// the first poll's round trip, and under it the DevArgs copy, the static loads' issue and the draw's first Philox block
+// (below) - 1.2 us more until alpha_pi has arrived and the draw starts, 16.2 us of arithmetic (a lone wave's chain: the
+// SIMD's second wave fills 65 % of its issue slots), 1.0 us to drain the stores and arrive.  Before the items were
+// prepared the same three pieces were 1.0 (two polls, one after the other), 2.2 (DevArgs, the tile's lookups, then the
+// batch: dependent round trips in which the wave issued nothing) and 16.9 us.  A tile's finish: DESIGN.md section 4.
+//
+// PREPARE (items).  An item wave knows its (step, tile, replicate) from the pull, before the previous step of its tile
+// has been finished.  What it reads falls into two classes: STATIC inputs, written by no wave of any launch - DevArgs,
+// g2t, toff, the counts X / Xbc, pi_a0, a0, a0_bc, rg, the control allele counts, kacc, the per-bin constants sf, sf_bc,
+// smask, P0 - and what the previous step's finish wrote: alpha_pi, tabP / tabPmu / tabPy, lpn, dgq.  The item loop asks
+// for its dependencies FIRST (one load, every lane: below), and while that answer is on its way it loads DevArgs into
+// SGPRs (once per item, one batch of scalar loads), issues every static load (guide_wave2_prepare, bean_guide_v2.hpp:
+// the tile's two lookups ride on two lanes of one load that is made scalar only after the poll) and computes the first
+// Philox block of the pi draw, which needs the step and the guide index only.  Nothing prepared is waited for before
+// the poll's answer is looked at.  Dependencies met at the first look (the common case: a wave has ~2 items per step):
+// the rest of the item (guide_wave2_rest) asks for alpha_pi and the tables, puts the prepared values into their LDS
+// slots under THAT round trip - loads return in issue order, so alpha_pi cannot arrive before them - and starts the draw.
+// Not met: the prepared values go into LDS at once (no prepared register lives across the polls) and the wave polls.
+// A waiting wave that takes a filled finish-ring position runs async_finish_tile over the same LDS and registers; its
+// item stays pulled, and when the loop comes round it is prepared again from the start - nothing is assumed to have
+// survived.  Items of a call's first step take the same path and ask for the abort word only.  No arithmetic changes and
+// no addition changes its order: same bits (tests/test_gpu_async_prepare.py).
+// What paid, in the order tried (profiles/r07_bench_ab*.jsonl; bench.py, 2 000 steps, five alternating runs each, us per
+// step, parent / new).  (1) Prepare, stage into LDS, THEN poll - the first form: 45.43 - 45.84 / 45.40 - 45.70,
+// nothing.  The poll's answer returns in issue order behind ~25 static loads, and the two conditional poll loads were
+// each waited for where their lane condition ends: "pull -> dependencies seen" went from 1.0 to 2.5 us while
+// "dependencies seen -> draw" fell from 2.2 to 0.9.  (2) The poll issued first, staging under alpha_pi's round trip:
+// 45.58 - 45.75 / 45.07 - 45.41, every run faster, -0.9 %.  (3) The poll as ONE unconditional load of every lane (lanes
+// 0 - 3 the four words, lane 4 the abort word, the others their tile's word, dropped), so that it really stays in flight
+// over the prepare and a repeat is one round trip instead of two; DevArgs words of the static part requested as one
+// batch: 45.59 - 45.75 / 44.09 - 44.42; the final build 45.42 - 45.71 / 44.13 - 44.29, -3.0 %; 20 steps after 5: 49.91 - 50.34 /
+// 48.67 - 48.96.  Not adopted: the same
+// one-load form for the FINISHERS' poll (async_finish_tile) - 44.09 - 44.51 without / 44.78 - 44.99 with it: the finisher
+// waves poll twice as often and take issue slots from their SIMD's item waves.  Not built: the targets' next-step
+// normals and ue_idx / ue_z ahead of the ring poll.
 //
 // Order and progress.  The queue is one counter per XCD group (blockIdx & 7, a label: the blocks that share a label
 // share an L2; nothing depends on it but speed), items in (step, tile, replicate) order; tile k belongs to group
@@ -191,11 +222,13 @@ constexpr long kAsyncStampFinOff = 1l << 22;  // words between an item's row and
     }
 #define BEAN_ASYNC_ST_ARG , unsigned long long* st_row
 #define BEAN_ASYNC_ST_PASS , st_row
+#define BEAN_ASYNC_ST_DRAW , (st_row ? st_row + 3 : nullptr)
 #else
 #define BEAN_ASYNC_T(k)
 #define BEAN_ASYNC_TF(k)
 #define BEAN_ASYNC_ST_ARG
 #define BEAN_ASYNC_ST_PASS
+#define BEAN_ASYNC_ST_DRAW
 #endif
 
 // DevArgs as the kernel received them -> their copy in global memory (stream-ordered, no host staging)
@@ -320,6 +353,8 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
     if (wait_slot) {
         int spins = 0;
         for (;;) {
+            // (two loads under lane conditions: two round trips in a row.  As ONE load of every lane, the form of the items'
+            // poll, the finishers poll twice as often and the step got slower - 44.9 against 44.3 us, header)
             int v = 0, ab = 0;
             if (lane == 0) v = __hip_atomic_load(wait_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (lane == 1) ab = __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -545,14 +580,14 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
     return kAsyncFinDone;
 }
 
-// One item: k_guide_wave2's wave work on (tile, r) at the step, this wave's loss part, the arrival.  Returns
-// {t0, number of the tile's targets} when this wave completed the tile (it then finishes it), {-1, 0} otherwise.
+// One item, from the point where its dependencies are met: the rest of k_guide_wave2's wave work on (tile, r) at the
+// step (guide_wave2_rest: the item loop has prepared and staged the static inputs before it polled, with the same
+// DevArgs copy `c`), this wave's loss part, the arrival.  Returns {1, 0} when this wave completed the tile (it then
+// finishes it, or fills the tile's ring positions), {-1, 0} otherwise.
 template <int FAM, bool ACC>
-__device__ BEAN_ASYNC_INLINE int2 async_guide_item(const DevArgs* cp, unsigned long long step, unsigned long long slot,
-                                              float step_size, int tile, int r BEAN_ASYNC_ST_ARG) {
-    const DevArgs c = dev_args_in_sgprs(cp);
-    tile = rfl_i(tile);
-    r = rfl_i(r);
+__device__ BEAN_ASYNC_INLINE int2 async_guide_item(const DevArgs& c, W2Prep& pp, bool stage_now, unsigned long long step,
+                                              unsigned long long slot, float step_size, int tile,
+                                              int r BEAN_ASYNC_ST_ARG) {
     StepCtr ctr;
     ctr.step = rfl_u64(step);
     ctr.slot = rfl_u64(slot);
@@ -562,7 +597,7 @@ __device__ BEAN_ASYNC_INLINE int2 async_guide_item(const DevArgs* cp, unsigned l
     const int wg = ((tile >> 3) * R + r) * 8 + (tile & 7);  // the wave's id in the grid of padded tiles x replicates
     int t0, nt;
     double tot;
-    guide_wave2_tile<FAM, ACC, 2>(c, ctr, tile, r, wg, t0, nt, tot);
+    guide_wave2_rest<FAM, ACC, 2>(c, ctr, tile, r, wg, pp, stage_now, t0, nt, tot BEAN_ASYNC_ST_DRAW);
     BEAN_ASYNC_T(4);
     if (lane == 0) {
         long long w0 = 0, w1 = 0, w2 = 1;
@@ -669,27 +704,49 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
             }
 #endif
             BEAN_ASYNC_T(0);
-            // ---- wait until the previous step of this tile and of its two neighbours (a target may straddle a tile
-            // boundary, and is finished by whichever of the two tiles completes second) has been finished: lanes 0 - 2
-            // poll one word each, lane 3 the abort word.  With finisher roles a wave that has waited for a while looks
-            // into the finish ring and takes the oldest finish that nobody has taken (the finishers need not be
-            // resident for the launch to make progress).
-            bool ready = false;
-            {
-                // (done[2 k]: tile k's targets, done[2 k + 1]: its guides; a neighbour matters through the targets it shares)
-                const int tq = (lane == 0 || lane == 3) ? tile : (lane == 1 ? tile - 1 : tile + 1);
-                const bool need = s > 0 && lane < 4 && tq >= 0 && tq < n_tiles;
+            // ---- the first poll and the prepare, side by side.  The item waits until the previous step of its tile and
+            // of the tile's two neighbours (a target may straddle a tile boundary, and is finished by whichever of the two
+            // tiles completes second) has been finished: lanes 0 - 2 ask for the targets' word of one tile each, lane 3
+            // for the guides' word of its own, lane 4 for the abort word.  The first of these loads goes out at once;
+            // behind it DevArgs come into SGPRs (once per item: the rest of the item uses this copy) and everything the item
+            // reads that no wave of the launch writes is ISSUED - and the first Philox block of its draw computed - while
+            // the poll's answer is on its way.  Nothing of it is waited for here.  (The other way round - the poll behind
+            // the prepared loads - the answer, which returns in issue order, waited for all of them: measured, header.)
+            // An item whose wait ends in a stolen finish comes round with `item` still set and prepares again from the
+            // start: the finish has used the wave's LDS and registers, and nothing prepared is assumed to survive it.
+            // Items of the call's first step take the same path and ask for the abort word only.
+            // (done[2 k]: tile k's targets, done[2 k + 1]: its guides; a neighbour matters through the targets it shares)
+            const int tq = (lane == 0 || lane == 3) ? tile : (lane == 1 ? tile - 1 : tile + 1);
+            const bool need = s > 0 && lane < 4 && tq >= 0 && tq < n_tiles;
+            // (ONE load for the wave, every lane of it: a load under a lane condition is waited for where the condition
+            // ends - the two polls were two round trips in a row, and the first could not stay in flight over the prepare;
+            // the lanes that ask for nothing read their tile's word and drop it)
+            const int* const pw = lane == 4 ? a.abort_flag : a.done + (need ? 2 * tq + (lane == 3 ? 1 : 0) : 2 * tile);
+            int w = __hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::: "memory");  // (the first poll is issued above this line)
+            const DevArgs c = dev_args_in_sgprs(cp);
+            const int tile_u = rfl_i(tile), r_u = rfl_i(r);
+            const unsigned long long step = a.step0 + (unsigned long long)s, slot = a.slot0 + (unsigned long long)s;
+            W2Prep pp;
+            guide_wave2_prepare<FAM, ACC, 2>(c, rfl_u64(step), tile_u, r_u, pp);
+            int v = need ? w : s, ab = lane == 4 ? w : 0;
+            if (__any(ab != 0)) return;
+            bool ready = __all(v >= s);
+            // (dependencies met at the first look, the common case: the prepared values stay in registers until the rest of
+            // the item has asked for alpha_pi and the tables, and go into LDS under that round trip)
+            const bool fast = ready;
+            if (!ready) {
+                // ---- not yet: what was prepared goes into its LDS slots (the wave has nothing else to do, and no
+                // prepared register lives across the polls), then the wave polls.  With finisher roles a wave that has
+                // waited for a while looks into the finish ring and takes the oldest finish that nobody has taken (the
+                // finishers need not be resident for the launch to make progress).
+                {
+                    const int lane_st = w2_lane_here();
+                    guide_wave2_stage_counts<FAM>(c, lane_st, tile_u, r_u, pp);
+                    guide_wave2_stage<FAM, 3>(c, lane_st, tile_u, r_u, pp);
+                }
                 int spins = 0;
                 for (;;) {
-                    int v = s;
-                    if (need) v = __hip_atomic_load(a.done + 2 * tq + (lane == 3 ? 1 : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    int ab = 0;
-                    if (lane == 4) ab = __hip_atomic_load(a.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (__any(ab != 0)) return;
-                    if (__all(v >= s)) {
-                        ready = true;
-                        break;
-                    }
                     if (++spins > kAsyncSpinMax) {
                         if (lane == 0) async_give_up(cp, a);
                         return;
@@ -715,13 +772,20 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
                         }
                     }
                     __builtin_amdgcn_s_sleep(BEAN_ASYNC_SLEEP);
+                    w = __hip_atomic_load(pw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    v = need ? w : s;
+                    ab = lane == 4 ? w : 0;
+                    if (__any(ab != 0)) return;
+                    if (__all(v >= s)) {
+                        ready = true;
+                        break;
+                    }
                 }
-                asm volatile("" ::: "memory");  // (nothing below is loaded before the poll has matched)
             }
+            asm volatile("" ::: "memory");  // (nothing below is loaded before the poll has matched)
             BEAN_ASYNC_T(1);
             if (ready) {
-                const unsigned long long step = a.step0 + (unsigned long long)s, slot = a.slot0 + (unsigned long long)s;
-                const int2 fin = async_guide_item<FAM, ACC>(cp, step, slot, a.step_sizes[s], tile, r BEAN_ASYNC_ST_PASS);
+                const int2 fin = async_guide_item<FAM, ACC>(c, pp, fast, step, slot, a.step_sizes[s], tile_u, r_u BEAN_ASYNC_ST_PASS);
                 item = -1;
                 BEAN_ASYNC_T(2);
                 if (fin.x >= 0) {

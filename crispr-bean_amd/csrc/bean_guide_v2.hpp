@@ -407,16 +407,137 @@ __device__ __forceinline__ void target_part_sums(const DevArgs& c, int lane, int
     }
 }
 
+// diagnostic builds (-DBEAN_ASYNC_STAMP, bean_async_v2.hpp): the real-time clock when the wave's inputs are staged - the
+// batch is issued, alpha_pi and pi_a0 have arrived - and the draw's arithmetic starts
+#ifdef BEAN_ASYNC_STAMP
+#define BEAN_W2_STAMP_DRAW(ptr, a0_, a1_, pa_)                                                       \
+    if (ptr) {                                                                                       \
+        asm volatile("" ::"v"(a0_), "v"(a1_), "v"(pa_));                                             \
+        unsigned long long u_;                                                                       \
+        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(u_)::"memory");               \
+        if (lane == 0) *(ptr) = u_;                                                                  \
+    }
+#else
+#define BEAN_W2_STAMP_DRAW(ptr, a0_, a1_, pa_) (void)(ptr)
+#endif
+
 // The work of one wave = 64 consecutive guides of one replicate (tile k holds the guides whose GLOBAL index
 // g_off + g lies in [64 (k + g_off / 64), + 64): DevArgs::g_sh = g_off % 64 lanes of a shard's first tile
 // are empty).  Returns false for the padded tiles of the XCD-aware grid; otherwise the wave's part of the
 // loss in `tot` (valid in lane 0).
 // guide_wave2_tile: the work on (tile, replicate r); `wg` = the wave's id in the 1-D grid of padded tiles x replicates
 // (index of its loss part, stamps).
-template <int FAM, bool ACC, int STEP>
-__device__ __forceinline__ void guide_wave2_tile(const DevArgs& c, const StepCtr& ctr, const int tile, const int r,
-                                                 const int wg, int& t0_o, int& nt_o, double& tot_o) {
+//
+// PREPARE and the rest.  What the wave reads falls into two classes.  STATIC inputs are written by no wave of any
+// launch of a fit: the tile's first and last target (g2t), the counts of both likelihoods, the repguide mask, a0,
+// a0_bcmatch, pi_a0, the control allele counts, the replicate's per-bin constants - and the first Philox block of the pi
+// draw, which needs the step and the guide index only.  The rest comes from the previous step's finish: alpha_pi, the
+// three Phi tables, and in guide_pair_math lpn and the tabulated digammas.  The two launches per step read both in ONE
+// batch (PHASE 0: the order of that batch is part of what they cost - loads return in issue order and the draw waits
+// for the first three).  k_svi_async's item wave knows its (step, tile, replicate) before the previous step of its tile
+// has been finished, so it runs the static part BEFORE it polls (PHASE 1: the loads are issued and the Philox block
+// computed, nothing is waited for), puts what arrived into its LDS slots while the poll's first answer is on its way
+// (guide_wave2_stage), and runs the rest once the poll has matched (PHASE 2).  Same loads, same arithmetic, same bits;
+// only when the static loads are made moves.
+struct W2Prep {
+    int look;     // PHASE 1: lane 0 g2t[g_first], lane 1 g2t[g_last] - ONE load, made scalar only in PHASE 2
+    int g2tv;     // the lane's target
+    int rgv;      // its repguide mask word
+    double pa0;
+    uint4 philox_first;
+    float xv[2][kBMax];
+    double cv, a00, a01;
+    float alc0, alc1;
+    double cnt0, cnt1;  // the control allele counts summed over the control conditions (guide_wave2_stage_counts)
+};
+
+// The lane index as a value the compiler does not follow back to threadIdx.x: the addresses the staging derives from it
+// are computed where they are used.  (Derived from threadIdx.x they are loop-invariant in k_svi_async's item loop,
+// hoisted in front of it and - live across the whole loop - kept in scratch: 16 B per lane more than before.)
+__device__ __forceinline__ int w2_lane_here() {
+    int lane = threadIdx.x;
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+
+// The wave's LDS: [3][B][ntm] table columns | [4][B] sf, sf_bc, sample mask, P0 of this replicate |
+//                 [B][64] digamma differences | [kW2Misc][64] per-guide values | [2][B][64] counts (float)
+// What of the prepared values goes where (PART 1: the counts of both likelihoods, with the conditions beyond the
+// register batch; PART 2: the per-bin constants, a0, a0_bcmatch and the control allele counts of every control condition).
+// Reads static data only; writes whatever it is given again when it is called again (an item wave whose wait ended in a
+// stolen finish prepares and stages anew: the finish has used the same LDS).
+template <int FAM, int PART>
+__device__ __forceinline__ void guide_wave2_stage(const DevArgs& c, const int lane, const int tile, const int r, W2Prep& pp) {
     constexpr bool MIX = FAM == kMixture;
+    extern __shared__ double tabs[];
+    const int G = c.G, B = c.B;
+    const int g = tile * 64 + lane - c.g_sh;
+    const int gc = g >= 0 && g < G ? g : (g < 0 ? 0 : G - 1);
+    const bool use_bc = (c.flags & kUseBc) != 0;
+    double* cst = tabs + 3 * B * c.tile_targets;
+    double* ms = cst + 4 * B + B * 64 + lane;         // ms[q * 64]
+    float* xs = (float*)(cst + 4 * B + B * 64 + kW2Misc * 64);
+    if (PART & 1) {
+#pragma unroll
+        for (int b = 0; b < kBMax; ++b) {
+            const int bb = b < B ? b : B - 1;
+            xs[(0 * B + bb) * 64 + lane] = pp.xv[0][b];
+            xs[(1 * B + bb) * 64 + lane] = pp.xv[1][b];
+        }
+        for (int b = kBMax; b < B; ++b) {  // more conditions than the register batch holds (B <= kBCap)
+            const long xo = ((long)r * B + b) * G + gc;
+            xs[(0 * B + b) * 64 + lane] = c.X[xo];
+            xs[(1 * B + b) * 64 + lane] = use_bc ? c.Xbc[xo] : 0.f;
+        }
+    }
+    if (PART & 2) {
+        {
+            const int kq = lane >> 3, bq = lane & 7;
+            if (kq < 4 && bq < B) cst[kq * B + bq] = pp.cv;
+            for (int b2 = 8 + bq; b2 < B; b2 += 8) {  // bins 8 .. B - 1
+                if (kq < 4) {
+                    const double* src = kq == 0 ? c.sf + r * B : (kq == 1 ? (use_bc ? c.sf_bc : c.sf) + r * B
+                                                                          : (kq == 2 ? c.smask + r * B : c.P0));
+                    cst[kq * B + b2] = (MIX || kq != 3) ? src[b2] : 0.0;
+                }
+            }
+        }
+        ms[0 * 64] = pp.a00;
+        ms[1 * 64] = pp.a01;
+        ms[2 * 64] = pp.cnt0;
+        ms[3 * 64] = pp.cnt1;
+    }
+}
+
+// (the control allele counts, summed over the control conditions - after the draw in the one-batch form - and handed to
+// guide_wave2_stage in the prepared struct)
+template <int FAM>
+__device__ __forceinline__ void guide_wave2_stage_counts(const DevArgs& c, const int lane, const int tile, const int r,
+                                                         W2Prep& pp) {
+    constexpr bool MIX = FAM == kMixture;
+    const int G = c.G;
+    const int g = tile * 64 + lane - c.g_sh;
+    const int gc = g >= 0 && g < G ? g : (g < 0 ? 0 : G - 1);
+    // (opaque to the compiler, or it converts the two counts where they are loaded - a full wait before the draw)
+    asm volatile("" : "+v"(pp.alc0), "+v"(pp.alc1));
+    double cnt0 = c.C > 0 ? (double)pp.alc0 : 0.0, cnt1 = c.C > 0 ? (double)pp.alc1 : 0.0;
+    if (MIX)
+        for (int cc = 1; cc < c.C; ++cc) {
+            const float* al = c.allele + (((long)r * c.C + cc) * G + gc) * 2;
+            cnt0 += (double)al[0];
+            cnt1 += (double)al[1];
+        }
+    pp.cnt0 = cnt0;
+    pp.cnt1 = cnt1;
+}
+
+template <int FAM, bool ACC, int STEP, int PHASE>
+__device__ __forceinline__ void guide_wave2_phase(const DevArgs& c, const StepCtr& ctr, const int tile, const int r,
+                                                  const int wg, W2Prep& pp, int& t0_o, int& nt_o, double& tot_o,
+                                                  const bool stage_now = false, unsigned long long* st_draw = nullptr) {
+    constexpr bool MIX = FAM == kMixture;
+    // ST: this call makes the static loads; DY: it makes the loads of what a finish writes and does the arithmetic
+    constexpr bool ST = PHASE != 2, DY = PHASE != 1;
     extern __shared__ double tabs[];
     const int lane = threadIdx.x;
     const int G = c.G, T = c.T, B = c.B, R = c.R;
@@ -430,43 +551,67 @@ __device__ __forceinline__ void guide_wave2_tile(const DevArgs& c, const StepCtr
     BEAN_STAMP_AT(0);
     BEAN_STAMP_CLK(0);
 
+    if (PHASE == 1) {
+        // (every DevArgs word the static part uses, asked for as ONE batch of scalar loads: left to itself the compiler
+        // fetches each pointer where its first address is formed - some ten scalar round trips in a row at the head of
+        // the item, each waited for before the next)
+        asm volatile("" ::"s"(c.g2t), "s"(c.X), "s"(c.Xbc), "s"(c.pi_a0), "s"(c.sf), "s"(c.sf_bc), "s"(c.smask), "s"(c.P0),
+                     "s"(c.rg), "s"(c.a0), "s"(c.a0_bc), "s"(c.allele), "s"(c.pi_in), "s"(c.seed), "s"(c.G), "s"(c.B),
+                     "s"(c.g_sh), "s"(c.flags), "s"(c.C), "s"(c.G_tot), "s"(c.g_off));
+    }
     const int g_first = tile * 64 - c.g_sh > 0 ? tile * 64 - c.g_sh : 0;
     const int g_last = (tile * 64 + 63 - c.g_sh < G ? tile * 64 + 63 - c.g_sh : G - 1);
-    const int t0 = __builtin_amdgcn_readfirstlane(c.g2t[g_first]);
-    const int nt = __builtin_amdgcn_readfirstlane(c.g2t[g_last]) - t0 + 1;
+    int t0 = 0, nt = 0;
+    if (PHASE == 0) {
+        t0 = __builtin_amdgcn_readfirstlane(c.g2t[g_first]);
+        nt = __builtin_amdgcn_readfirstlane(c.g2t[g_last]) - t0 + 1;
+    } else if (PHASE == 1) {
+        // (the two lookups ride on lanes 0 and 1 of ONE load that nothing waits for here: a uniform value's load is waited
+        // for where it is made scalar, and that is PHASE 2, after the poll)
+        pp.look = c.g2t[lane == 0 ? g_first : g_last];
+    } else {
+        t0 = __builtin_amdgcn_readlane(pp.look, 0);
+        nt = __builtin_amdgcn_readlane(pp.look, 1) - t0 + 1;
+    }
     // did the tile's first target begin in the previous tile?  (wave-uniform; used when the sums are stored)
-    const int tof_first = c.tsum_direct ? uniform_ld_i(c.toff, t0) : 0;
+    const int tof_first = DY && c.tsum_direct ? uniform_ld_i(c.toff, t0) : 0;
     const int ntm = c.tile_targets;
     t0_o = t0;
     nt_o = nt;
-    // LDS: [3][B][ntm] table columns | [4][B] sf, sf_bc, sample mask, P0 of this replicate |
-    //      [B][64] digamma differences | [kW2Misc][64] per-guide values | [2][B][64] counts (float)
+    // (LDS layout: guide_wave2_stage)
     double* cst = tabs + 3 * B * ntm;
     double* dps = cst + 4 * B + lane;                 // dps[b * 64]
     double* ms = cst + 4 * B + B * 64 + lane;         // ms[q * 64]
     float* xs = (float*)(cst + 4 * B + B * 64 + kW2Misc * 64);
     const bool use_bc = (c.flags & kUseBc) != 0;
     int tcol = 0;
-    uint4 philox_first = make_uint4(0u, 0u, 0u, 0u);
     bool rgm = false;
     float api0 = 0.f, api1 = 0.f;
-    double pa0 = 0.0, pi0 = 0.0, pi1 = 1.0;
+    double pi0 = 0.0, pi1 = 1.0;
+    if (ST) {
+        pp.philox_first = make_uint4(0u, 0u, 0u, 0u);
+        pp.pa0 = 0.0;
+    }
     {
-        // everything the wave reads from global memory, issued as one batch before the first wait
+        // everything the wave reads from global memory, issued as one batch before the first wait (PHASE 0; with the
+        // phases apart, the static loads of the batch in PHASE 1 and the others in PHASE 2, each in this order)
         const int gc = valid ? g : (g < 0 ? 0 : G - 1);
         const long rgc = (long)r * G + gc;
         // (first in the batch: loads return in issue order, and the draw below waits for these three only)
         if (MIX) {
-            api0 = w2_ld<STEP>(c.p[4] + 2 * gc);
-            api1 = w2_ld<STEP>(c.p[4] + 2 * gc + 1);
-            pa0 = c.pi_a0[gc];
+            if (DY) {
+                api0 = w2_ld<STEP>(c.p[4] + 2 * gc);
+                api1 = w2_ld<STEP>(c.p[4] + 2 * gc + 1);
+            }
+            if (ST) pp.pa0 = c.pi_a0[gc];
         }
-        float xv[2][kBMax];
+        if (ST) {
 #pragma unroll
-        for (int b = 0; b < kBMax; ++b) {
-            const long xo = ((long)r * B + (b < B ? b : B - 1)) * G + gc;
-            xv[0][b] = c.X[xo];
-            xv[1][b] = use_bc ? c.Xbc[xo] : 0.f;
+            for (int b = 0; b < kBMax; ++b) {
+                const long xo = ((long)r * B + (b < B ? b : B - 1)) * G + gc;
+                pp.xv[0][b] = c.X[xo];
+                pp.xv[1][b] = use_bc ? c.Xbc[xo] : 0.f;
+            }
         }
         // table rows (which, b) are packed `per` rows to a load: P = pow2 >= nt lanes per row
         int lg2 = 0;
@@ -478,74 +623,83 @@ __device__ __forceinline__ void guide_wave2_tile(const DevArgs& c, const StepCtr
         const long covoff = c.n_cov ? (long)r * B * T : 0;  // sample covariates: tables per replicate
         double tv[kTabLoads];
         int wbv[kTabLoads];
-        // (the three table pointers as register values: left to itself the compiler turns the selection below into
-        // a per-lane LOAD of the pointer from the kernel-argument segment, i.e. one more round trip before the
-        // table loads can be issued)
-        // (and as GLOBAL pointers: through the asm the compiler no longer knows the address space, and a flat load
-        // in flight makes every later wait a full one)
-        typedef const double __attribute__((address_space(1))) * GlobalTab;
-        const double *tabP_ = c.tabP, *tabPmu_ = c.tabPmu, *tabPy_ = c.tabPy;
-        asm volatile("" : "+s"(tabP_), "+s"(tabPmu_), "+s"(tabPy_));
-        const GlobalTab tabP = (GlobalTab)tabP_, tabPmu = (GlobalTab)tabPmu_, tabPy = (GlobalTab)tabPy_;
+        if (DY) {
+            // (the three table pointers as register values: left to itself the compiler turns the selection below into
+            // a per-lane LOAD of the pointer from the kernel-argument segment, i.e. one more round trip before the
+            // table loads can be issued)
+            // (and as GLOBAL pointers: through the asm the compiler no longer knows the address space, and a flat load
+            // in flight makes every later wait a full one)
+            typedef const double __attribute__((address_space(1))) * GlobalTab;
+            const double *tabP_ = c.tabP, *tabPmu_ = c.tabPmu, *tabPy_ = c.tabPy;
+            asm volatile("" : "+s"(tabP_), "+s"(tabPmu_), "+s"(tabPy_));
+            const GlobalTab tabP = (GlobalTab)tabP_, tabPmu = (GlobalTab)tabPmu_, tabPy = (GlobalTab)tabPy_;
 #pragma unroll
-        for (int q = 0; q < kTabLoads; ++q) {
-            const int wb = q * per + sub;
-            const bool ok = wb < n_rows && j < nt;
-            const int wbc = ok ? wb : 0;
-            const int which = (wbc >= B) + (wbc >= 2 * B), bb = wbc - which * B;
-            const GlobalTab tab = which == 0 ? tabP : (which == 1 ? tabPmu : tabPy);
-            tv[q] = w2_ld_g<STEP>(tab + (covoff + (long)bb * T + t0 + (ok ? j : 0)));
-            wbv[q] = ok ? wb : -1;
+            for (int q = 0; q < kTabLoads; ++q) {
+                const int wb = q * per + sub;
+                const bool ok = wb < n_rows && j < nt;
+                const int wbc = ok ? wb : 0;
+                const int which = (wbc >= B) + (wbc >= 2 * B), bb = wbc - which * B;
+                const GlobalTab tab = which == 0 ? tabP : (which == 1 ? tabPmu : tabPy);
+                tv[q] = w2_ld_g<STEP>(tab + (covoff + (long)bb * T + t0 + (ok ? j : 0)));
+                wbv[q] = ok ? wb : -1;
+            }
         }
-        // wave-uniform per-bin constants of this replicate: lane k * 8 + b loads constant k of bin b
-        double cv = 0.0;
-        {
-            const int kq = lane >> 3, bq = lane & 7;  // kBMax <= 16: two rounds when B > 8
-            const double* src = kq == 0 ? c.sf + r * B : (kq == 1 ? (use_bc ? c.sf_bc : c.sf) + r * B
-                                                                  : (kq == 2 ? c.smask + r * B : c.P0));
-            if (kq < 4 && bq < B && (MIX || kq != 3)) cv = src[bq];
+        if (ST) {
+            // wave-uniform per-bin constants of this replicate: lane k * 8 + b loads constant k of bin b
+            pp.cv = 0.0;
+            {
+                const int kq = lane >> 3, bq = lane & 7;  // kBMax <= 16: two rounds when B > 8
+                const double* src = kq == 0 ? c.sf + r * B : (kq == 1 ? (use_bc ? c.sf_bc : c.sf) + r * B
+                                                                      : (kq == 2 ? c.smask + r * B : c.P0));
+                if (kq < 4 && bq < B && (MIX || kq != 3)) pp.cv = src[bq];
+            }
+            pp.g2tv = c.g2t[gc];
+            pp.rgv = c.rg[rgc];
+            pp.a00 = c.a0[gc];
+            pp.a01 = use_bc ? c.a0_bc[gc] : 0.0;
+            // the draw's first Philox block needs the step and the guide index only: computed here, while
+            // the loads above are in flight (after a kernel boundary they take ~3.5 us and every wave of the
+            // SIMD waits for them at the same time)
+            if (MIX && !c.pi_in) pp.philox_first = philox_block(c.seed, ((unsigned long long)kSitePi << 48) +
+                                                                          ((unsigned long long)r * c.G_tot + (c.g_off + gc)),
+                                                                ctr.step * 256ull);
+            // control allele counts of the first control condition (a branch-free load: with no control condition
+            // two words of pi_a0 are read in their place and dropped below)
+            pp.alc0 = 0.f;
+            pp.alc1 = 0.f;
+            if (MIX) {
+                const float* al = c.C > 0 ? c.allele + ((long)r * c.C * G + gc) * 2 : (const float*)(c.pi_a0 + gc);
+                pp.alc0 = al[0];
+                pp.alc1 = al[1];
+            }
         }
-        tcol = c.g2t[gc] - t0;
-        rgm = c.rg[rgc] != 0;
-        const double a00 = c.a0[gc], a01 = use_bc ? c.a0_bc[gc] : 0.0;
-        // the draw's first Philox block needs the step and the guide index only: computed here, while
-        // the loads above are in flight (after a kernel boundary they take ~3.5 us and every wave of the
-        // SIMD waits for them at the same time)
-        if (MIX && !c.pi_in) philox_first = philox_block(c.seed, ((unsigned long long)kSitePi << 48) +
-                                                                   ((unsigned long long)r * c.G_tot + (c.g_off + gc)),
-                                                         ctr.step * 256ull);
-        // control allele counts of the first control condition (a branch-free load: with no control condition
-        // two words of pi_a0 are read in their place and dropped below)
-        float alc0 = 0.f, alc1 = 0.f;
-        if (MIX) {
-            const float* al = c.C > 0 ? c.allele + ((long)r * c.C * G + gc) * 2 : (const float*)(c.pi_a0 + gc);
-            alc0 = al[0];
-            alc1 = al[1];
+        if (PHASE == 1) {
+            // (the loads are issued and the Philox block is computed HERE, in front of the caller's poll, not sunk to their
+            // uses behind it)
+            asm volatile("" ::: "memory");
+            asm volatile("" : "+v"(pp.philox_first.x), "+v"(pp.philox_first.y), "+v"(pp.philox_first.z), "+v"(pp.philox_first.w));
+            tot_o = 0.0;
+            return;
         }
+        tcol = pp.g2tv - t0;
+        rgm = pp.rgv != 0;
         // ---- the draw, under the loads: it is a fifth of a wave's arithmetic and needs none of the counts or
         // tables; after a kernel boundary all waves of the chip issue their loads within 1.6 us and wait ~3.5 us
         // for them - with nothing to issue from, since every wave of a SIMD is at the same point
         asm volatile("" ::: "memory");  // (the loads above are issued here, not sunk below the draw to their uses)
-        if (valid) guide_pair_draw<FAM>(c, ctr, r, g, api0, api1, pa0, &philox_first, ms + 4 * 64, ms + 5 * 64, pi0, pi1);
-        // (opaque to the compiler, or it converts the two counts where they are loaded - a full wait before the draw)
-        asm volatile("" : "+v"(alc0), "+v"(alc1));
-        double cnt0 = c.C > 0 ? (double)alc0 : 0.0, cnt1 = c.C > 0 ? (double)alc1 : 0.0;
-        if (MIX)
-            for (int cc = 1; cc < c.C; ++cc) {
-                const float* al = c.allele + (((long)r * c.C + cc) * G + gc) * 2;
-                cnt0 += (double)al[0];
-                cnt1 += (double)al[1];
-            }
-#pragma unroll
-        for (int b = 0; b < kBMax; ++b) {
-            const int bb = b < B ? b : B - 1;
-            xs[(0 * B + bb) * 64 + lane] = xv[0][b];
-            xs[(1 * B + bb) * 64 + lane] = xv[1][b];
+        if (PHASE == 2 && stage_now) {
+            // (an item whose first poll matched still holds what it prepared in registers: it goes into LDS here, while
+            // alpha_pi is on its way - loads return in issue order, so alpha_pi cannot arrive before the prepared values)
+            const int lane_st = w2_lane_here();
+            guide_wave2_stage_counts<FAM>(c, lane_st, tile, r, pp);
+            guide_wave2_stage<FAM, 3>(c, lane_st, tile, r, pp);
         }
-        for (int b = kBMax; b < B; ++b) {  // more conditions than the register batch holds (B <= kBCap)
-            const long xo = ((long)r * B + b) * G + gc;
-            xs[(0 * B + b) * 64 + lane] = c.X[xo];
-            xs[(1 * B + b) * 64 + lane] = use_bc ? c.Xbc[xo] : 0.f;
+        BEAN_W2_STAMP_DRAW(st_draw, api0, api1, pp.pa0);
+        if (valid)
+            guide_pair_draw<FAM>(c, ctr, r, g, api0, api1, pp.pa0, &pp.philox_first, ms + 4 * 64, ms + 5 * 64, pi0, pi1);
+        if (PHASE == 0) {
+            guide_wave2_stage_counts<FAM>(c, lane, tile, r, pp);
+            guide_wave2_stage<FAM, 1>(c, lane, tile, r, pp);
         }
 #pragma unroll
         for (int q = 0; q < kTabLoads; ++q)
@@ -558,21 +712,7 @@ __device__ __forceinline__ void guide_wave2_tile(const DevArgs& c, const StepCtr
                 tabs[wb * ntm + j] = w2_ld<STEP>(tab + (covoff + (long)bb * T + t0 + j));
             }
         }
-        {
-            const int kq = lane >> 3, bq = lane & 7;
-            if (kq < 4 && bq < B) cst[kq * B + bq] = cv;
-            for (int b2 = 8 + bq; b2 < B; b2 += 8) {  // bins 8 .. B - 1
-                if (kq < 4) {
-                    const double* src = kq == 0 ? c.sf + r * B : (kq == 1 ? (use_bc ? c.sf_bc : c.sf) + r * B
-                                                                          : (kq == 2 ? c.smask + r * B : c.P0));
-                    cst[kq * B + b2] = (MIX || kq != 3) ? src[b2] : 0.0;
-                }
-            }
-        }
-        ms[0 * 64] = a00;
-        ms[1 * 64] = a01;
-        ms[2 * 64] = cnt0;
-        ms[3 * 64] = cnt1;
+        if (PHASE == 0) guide_wave2_stage<FAM, 2>(c, lane, tile, r, pp);
     }
     __syncthreads();
 
@@ -585,6 +725,34 @@ __device__ __forceinline__ void guide_wave2_tile(const DevArgs& c, const StepCtr
     tot_o = wave_sum(loss);
     BEAN_STAMP_AT(7);
     BEAN_STAMP_CLK(2);
+}
+
+// The two launches per step, the one-launch step and the ensemble kernel: both halves in one batch
+template <int FAM, bool ACC, int STEP>
+__device__ __forceinline__ void guide_wave2_tile(const DevArgs& c, const StepCtr& ctr, const int tile, const int r,
+                                                 const int wg, int& t0_o, int& nt_o, double& tot_o) {
+    W2Prep pp;
+    guide_wave2_phase<FAM, ACC, STEP, 0>(c, ctr, tile, r, wg, pp, t0_o, nt_o, tot_o);
+}
+// k_svi_async's item: everything that reads only what no wave of the launch writes, issued and not waited for ...
+template <int FAM, bool ACC, int STEP>
+__device__ __forceinline__ void guide_wave2_prepare(const DevArgs& c, const unsigned long long step, const int tile,
+                                                    const int r, W2Prep& pp) {
+    StepCtr ctr;
+    ctr.step = step;
+    ctr.slot = 0;
+    ctr.step_size = 0.f;
+    ctr.pad_ = 0.f;
+    int t0, nt;
+    double tot;
+    guide_wave2_phase<FAM, ACC, STEP, 1>(c, ctr, tile, r, 0, pp, t0, nt, tot);
+}
+// ... and, after guide_wave2_stage_counts + guide_wave2_stage<FAM, 3>, the rest
+template <int FAM, bool ACC, int STEP>
+__device__ __forceinline__ void guide_wave2_rest(const DevArgs& c, const StepCtr& ctr, const int tile, const int r,
+                                                 const int wg, W2Prep& pp, const bool stage_now, int& t0_o, int& nt_o,
+                                                 double& tot_o, unsigned long long* st_draw = nullptr) {
+    guide_wave2_phase<FAM, ACC, STEP, 2>(c, ctr, tile, r, wg, pp, t0_o, nt_o, tot_o, stage_now, st_draw);
 }
 #undef W2_ROW_STORE
 

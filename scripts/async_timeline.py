@@ -1,6 +1,7 @@
 """Item and finish timeline of k_svi_async from a -DBEAN_ASYNC_STAMP build (BEAN_HIP_LIB=<that build>):
     python scripts/async_timeline.py [guides] [item blocks] [finisher blocks]
-Per item of four consecutive steps (real-time clock, 10 ns): pulled, dependencies seen, guide math done, arrived; per tile:
+Per item of four consecutive steps (real-time clock, 10 ns): pulled, dependencies seen, draw started (inputs staged, alpha_pi
+arrived), guide math done, arrived; per tile:
 when its last wave arrived, when the targets' / the guides' part of its finish started and was published, the phases of
 the targets' part.  Prints where a wave's time goes."""
 import ctypes
@@ -47,6 +48,9 @@ out = {"guides": G, "item_blocks": os.environ.get("BEAN_HIP_ASYNC_BLOCKS", "defa
 for s in range(4):
     m = ok[s]
     pull, ready, arrived, math = (st[s, :, k][m] for k in (0, 1, 2, 4))
+    # word 3: inputs staged (batch issued, alpha_pi arrived), the draw's arithmetic starts; zero in builds without it
+    draw = st[s, :, 3][m]
+    have_d = draw > 0
     # per tile: rows of replicate 0 carry the finish stamps; the tile is complete when its last wave has arrived
     tiles = np.arange(n_tiles)
     rows0 = tiles * R
@@ -58,6 +62,8 @@ for s in range(4):
         "pulled_at": q((pull - t0) / 100.0),
         "wait_for_dependencies": q((ready - pull) / 100.0),
         "guide_math": q((math - ready) / 100.0),
+        "dependencies_seen_to_draw_started": q((draw - ready)[have_d] / 100.0),
+        "draw_started_to_guide_math_done": q((math - draw)[have_d] / 100.0),
         "store_drain_and_arrival": q((arrived - math) / 100.0),
         "tile_complete_to_targets_part_started": q((f[have_t, 4] - complete[have_t]) / 100.0),
         "targets_part (start to published)": q((f[have_t, 5] - f[have_t, 4]) / 100.0),
