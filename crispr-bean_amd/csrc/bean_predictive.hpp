@@ -15,7 +15,9 @@
 //   * Dirichlet: B gammas from the Marsaglia-Tsang pair sampler on site kSiteSimGamma (bins two by two), floored at
 //     kDblMin, normalised in float64.  A concentration on the 1e-5 floor takes the sampler's alpha < 1 boost
 //     U^(1 / alpha), which underflows to zero for all but ~0.7 % of the draws: such a bin then holds the kDblMin floor,
-//     i.e. a probability below 1e-300 - what Gamma(1e-5) is.
+//     i.e. a probability below 1e-300 - what Gamma(1e-5) is.  Where EVERY bin of a pair underflows (concentrations of
+//     1e-3 in all of them: 8e-4 of the draws at a0 = 0.01) the floors would make the bins equal; such a pair is drawn
+//     again in logs from the same counters (kSimLogBelow), so that the largest gamma takes the reads as it must.
 //   * Multinomial: n_obs categorical draws by inversion on the float64 cumulative of p; one Philox block of site
 //     kSiteSimCat gives four uniforms u = (w + 0.5) 2^-32; the bin is the number of cumulative values <= u among
 //     the first B - 1, so the last bin takes what the cumulative leaves.  Exact for any n: no approximation branch,
@@ -41,6 +43,9 @@ struct SimArgs {
 constexpr unsigned long long kSimGammaWords = 512;   // words reserved per pair of bins
 constexpr unsigned long long kSimPairSlots = 32;     // pairs of bins per (likelihood, draw)
 constexpr unsigned long long kSimCatWords = 1ull << 24;  // words per (likelihood, draw): one per categorical draw
+// A pair whose floored gammas add up to less than this is normalised in logs.  Above it a floored bin's share is below
+// kDblMin / 1e-290 = 2e-18 whether floored or not: no read lands there either way, and the draw keeps its bits.
+constexpr double kSimLogBelow = 1e-290;
 static_assert(kBCap <= 2 * kSimPairSlots, "the gamma windows hold kBCap conditions");
 
 __host__ __device__ inline size_t simulate_wave2_lds(int B) {
@@ -161,7 +166,46 @@ __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimAr
                 gsum += gm1;
             }
         }
-        const double rs = frcp(gsum);
+        double rs = frcp(gsum);
+        if (gsum < kSimLogBelow) {
+            // every gamma of this pair is at or near the kDblMin floor (concentrations of ~1e-3 and below in every bin):
+            // floored, the bins would share the reads evenly, where the Dirichlet gives nearly all of them to the bin
+            // with the largest gamma.  The same draws again in logs: log gamma = log(Marsaglia-Tsang draw of alpha + 1)
+            // + log U / alpha, from the same counters (the boost's block first, then the rounds), less their maximum.
+            // The column holds the gammas by now, so the concentrations are formed again: same operands, same bits.
+            const auto conc = [&](int b) {
+                const double ar = alpha_raw(w0, MIX ? c_p0[b] : 0.0, w1, c.tabP[(long)b * c.T + tcol], sf[b], epsB,
+                                            ai * c_sm[b]);
+                return ar < kEps ? kEps : ar;
+            };
+            double mx = -INFINITY;
+#pragma unroll 1
+            for (int b = 0; b < B; b += 2) {
+                const bool two = b + 1 < B;
+                const double al0 = conc(b), al1 = two ? conc(b + 1) : 1.0;
+                const bool lo0 = al0 < 1.0, lo1 = al1 < 1.0;
+                const unsigned long long off = (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords;
+                Rng rng(c.seed, kSiteSimGamma, sub, off + ((lo0 || lo1) ? 4ull : 0ull));
+                const uint4 ub = philox_block(c.seed, rng.sub, off);
+                const GammaPair gp = sample_gamma_pair_inl(lo0 ? al0 + 1.0 : al0, lo1 ? al1 + 1.0 : al1, rng);
+                const double lg0 = log(gp.g0) + (lo0 ? log(Rng::to_unit(ub.x, ub.y)) / al0 : 0.0);
+                col[b * 64] = lg0;
+                mx = fmax(mx, lg0);
+                if (two) {
+                    const double lg1 = log(gp.g1) + (lo1 ? log(Rng::to_unit(ub.z, ub.w)) / al1 : 0.0);
+                    col[(b + 1) * 64] = lg1;
+                    mx = fmax(mx, lg1);
+                }
+            }
+            gsum = 0.0;
+#pragma unroll 1
+            for (int b = 0; b < B; ++b) {
+                const double w = exp(col[b * 64] - mx);
+                col[b * 64] = w;
+                gsum += w;
+            }
+            rs = 1.0 / gsum;
+        }
         double cum = 0.0;
 #pragma unroll 1
         for (int b = 0; b < B; ++b) {

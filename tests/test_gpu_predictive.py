@@ -16,6 +16,7 @@ from bean_amd import _lib
 from bean_amd.preprocessing.synthetic import (_dirmult_counts, make_sorting_tiling_screen, make_sorting_variant_screen,
                                                make_survival_variant_screen)
 
+from dm_reference import flat_screen
 from members_common import CONFIGS, DEV, VAR, _h5ad_reader_present, _kw_of, _mini, _run, _state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -202,35 +203,12 @@ def test_concentrations_are_the_oracles(engines, screens, family, kw):
 
 
 # ------------------------------------------------------------------ 3. distribution
-def _flat_screen():
-    """128 guides x 2 replicates x 5 conditions, no masks, totals 400 ... 600 (not all multiples of 4), a0 = 50 and unit
-    size factors, for both likelihoods."""
-    data = make_sorting_variant_screen(128, 2, seed=4)
-    R, B, G = data.n_reps, data.n_condits, data.n_guides
-    rng = np.random.default_rng(8)
-    n = rng.integers(400, 601, (R, G))
-    share = np.array([0.2 if not (lo == 0 and hi == 1) else 1.0 for lo, hi in zip(data.lower_bounds.tolist(), data.upper_bounds.tolist())])
-    x = np.floor(n[:, None, :] * (share / share.sum())[None, :, None])
-    x[:, 0, :] += n - x.sum(1)
-    x = torch.as_tensor(x, dtype=torch.float32)
-    out = copy.copy(data)
-    out.X = out.X_masked = x
-    out.X_bcmatch = out.X_bcmatch_masked = x.clone()
-    out.size_factor = torch.ones((R, B), dtype=torch.float64)
-    out.size_factor_bcmatch = torch.ones((R, B), dtype=torch.float64)
-    out.a0 = torch.full((G,), 50.0, dtype=torch.float64)
-    out.a0_bcmatch = torch.full((G,), 50.0, dtype=torch.float64)
-    out.repguide_mask = torch.ones((R, G), dtype=torch.bool)
-    out.sample_mask = torch.ones((R, B), dtype=data.sample_mask.dtype)
-    return out
-
-
 @pytest.mark.parametrize("family", ["Normal", "MixtureNormal"])
 def test_draws_have_the_dirichlet_multinomial_moments(family):
     from bean_amd import engine
 
     S = 512
-    data = _flat_screen()
+    data = flat_screen()  # 128 guides x 2 replicates x 5 conditions, no masks, totals 400 ... 600, a0 = 50
     kw = dict(use_bcmatch=False) if family == "Normal" else {}
     eng = engine.HipSVI(family, data.to(DEV), num_steps=50, **kw)
     for k in ("mu_scale", "sd_scale"):
