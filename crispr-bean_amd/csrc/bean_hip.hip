@@ -1,7 +1,8 @@
 // libbean_hip.so: C ABI over the BEAN SVI kernels (see include/bean_hip.h).
 //
 // Contents, in this order:
-//   context              bean_hip_ctx, the kernel-template dispatch, expected_bytes, sync_devargs, the graph caches
+//   context              bean_hip_ctx and ArgSet, the kernel-template dispatch, expected_bytes, sync_devargs, the graph
+//                        caches, an ArgSet's device array, the list of workspace regions (workspace_regions)
 //   create/bind/prepare  bean_hip_create ... bean_hip_prepare
 //   launches             launch_timed, launch_param, launch_guide and its forms, set_step / finalize, elbo_grad / adam
 //   stepping             what the entry points share (begin_steps / first_draw / mark_resumable, the noise predicates,
@@ -44,108 +45,113 @@ static int fail(const std::string& msg) {
     } while (0)
 
 // ------------------------------------------------------------------ context
+// The arguments of the n copies of a fit that the `_ens` launches step together - the members of an ensemble, or the
+// particles of a fit - and the ladder of graphs that replays those launches.  A handle has one set of each kind, and
+// both can be live: a particle handle is also an ensemble of one (bean_hip_svi_run_ensemble).
+struct ArgSet {
+    DevArgs* dev = nullptr;             // device: DevArgs of the n copies; the launches, captured ones too, hold its address
+    std::vector<DevArgs> host;          // what `dev` holds
+    std::vector<uint64_t> seeds;        // ... and the seeds it was built with
+    bool dirty = true;                  // `dev` is older than the bound buffers
+    std::vector<hipGraphExec_t> ladder; // [k]: 2^k units of the set's entry point (the table in DESIGN.md, section 1)
+};
+
+// (what is not set here, bean_hip_create sets from the shape and the environment)
 struct bean_hip_ctx {
-    bean_hip_shape shape;
-    DevArgs d;
-    void* slot_ptr[BEAN_BUF_COUNT];
-    uint64_t slot_bytes[BEAN_BUF_COUNT];
-    void* workspace;
-    uint64_t workspace_bytes;
-    uint64_t loss_capacity;
-    bool prepared;
-    bool fused_guide;  // false: BEAN_HIP_GUIDE=split selects the sample / lik / pi-terms launches
-    bool wave_guide;   // sorting variant families, default: one wave per (guide tile, replicate)
-    bool wave2;        // ... in its second form, k_guide_wave2 (BEAN_HIP_GUIDE=wave1 selects the first)
-    bool surv_wave;    // survival variant families: k_guide_survival_wave (BEAN_HIP_SURVIVAL=block: k_guide_survival)
-    bool fused_step;   // bean_hip_svi_run steps with ONE launch, k_step_wave2 (bean_step_v2.hpp; BEAN_HIP_STEP=pair: two)
+    bean_hip_shape shape = {};
+    DevArgs d = {};
+    void* slot_ptr[BEAN_BUF_COUNT] = {};
+    uint64_t slot_bytes[BEAN_BUF_COUNT] = {};
+    void* workspace = nullptr;
+    uint64_t workspace_bytes = 0;
+    uint64_t loss_capacity = 0;
+    bool prepared = false;
+    bool fused_guide = true;  // false: BEAN_HIP_GUIDE=split selects the sample / lik / pi-terms launches
+    bool wave_guide = false;  // sorting variant families, default: one wave per (guide tile, replicate)
+    bool wave2 = false;       // ... in its second form, k_guide_wave2 (BEAN_HIP_GUIDE=wave1 selects the first)
+    bool surv_wave = false;   // survival variant families: k_guide_survival_wave (BEAN_HIP_SURVIVAL=block: k_guide_survival)
+    bool fused_step = false;  // bean_hip_svi_run steps with ONE launch, k_step_wave2 (bean_step_v2.hpp; BEAN_HIP_STEP=pair: two)
     std::vector<hipGraphExec_t> graphs_fused;  // [k]: 2^(k+1) launches of k_step_wave2
-    long long* loss_acc;  // library-owned fixed-point loss accumulators, kLossWords per loss_hist slot
-    int* tile_targets_dev;
-    double* tsum_buf;   // DevArgs::tsum / tdesc (sized by bean_hip_prepare: they depend on tile_targets)
-    int2* tdesc_buf;
-    int* live_slots;   // tiling: compact list of the allele slots that hold an allele (own allocation, (A - 1) G ints)
-    bool tiling_wave;  // tiling families, default: k_guide_tiling_wave (BEAN_HIP_TILING=block: k_guide_tiling)
-    bool tiling_wide;  // more alleles per guide than this build's kAMax: bean_tiling_wide.hpp
-    int tiling_rep_w;  // ... with this many waves per workgroup
-    bool tiling_rep;   // tiling families, default: k_guide_tiling_rep, the replicates of a guide share a wave (bean_tiling_v2.hpp)
+    long long* loss_acc = nullptr;  // library-owned fixed-point loss accumulators, kLossWords per loss_hist slot
+    int* tile_targets_dev = nullptr;  // (in the workspace: workspace_regions)
+    double* tsum_buf = nullptr;   // DevArgs::tsum / tdesc (sized by bean_hip_prepare: they depend on tile_targets)
+    int2* tdesc_buf = nullptr;
+    int* live_slots = nullptr;   // tiling: compact list of the allele slots that hold an allele (own allocation, (A - 1) G ints)
+    bool tiling_wave = false;  // tiling families, default: k_guide_tiling_wave (BEAN_HIP_TILING=block: k_guide_tiling)
+    bool tiling_wide = false;  // more alleles per guide than this build's kAMax: bean_tiling_wide.hpp
+    int tiling_rep_w = 0;      // ... with this many waves per workgroup
+    bool tiling_rep = false;   // tiling families, default: k_guide_tiling_rep, the replicates of a guide share a wave (bean_tiling_v2.hpp)
     // tiling: the allele tables (tabP, tabPmu, tabPy, mu_a, sig_a) belong to the draw that is on the device.  A PREP launch
     // of k_param<..., 3> with allele blocks leaves them so (round 5); any other PREP launch leaves a new draw and stale
     // tables, and launch_guide runs k_allele first.  BEAN_HIP_ALLELE=split: k_param never has allele blocks (A/B).
-    bool alleles_fresh;
-    bool allele_blocks;
-    bool resume_head_fresh;  // the resume graphs were captured with fresh tables at their head (their first node is a guide launch)
-    double* gsum_ws;  // library-owned normaliser buffer (replaced by BEAN_BUF_XCHG_GSUM when bound)
-    double* sq_ws;    // library-owned projection sums (replaced by BEAN_BUF_XCHG_SQ when bound)
-    double* cov_sum_ws;  // library-owned covariate gradient sums (replaced by BEAN_BUF_XCHG_COV when bound)
+    bool alleles_fresh = false;
+    bool allele_blocks = true;
+    bool resume_head_fresh = false;  // the resume graphs were captured with fresh tables at their head (their first node is a guide launch)
+    // in the workspace (workspace_regions); sync_devargs puts the caller's exchange buffer in their place when one is bound
+    double* gsum_ws = nullptr;     // normaliser buffer (replaced by BEAN_BUF_XCHG_GSUM when bound)
+    double* sq_ws = nullptr;       // projection sums (replaced by BEAN_BUF_XCHG_SQ when bound)
+    double* cov_sum_ws = nullptr;  // covariate gradient sums (replaced by BEAN_BUF_XCHG_COV when bound)
     // graph cache: graphs[k] replays 2^k {k_param, guide} pairs
     std::vector<hipGraphExec_t> graphs;
-    unsigned long long graph_seed;
+    unsigned long long graph_seed = 0;
     // profiling of the dominant kernel
-    bool profile;
-    bool profile_param;  // profile mode 2: time k_param<FINISH, ADAM, PREP> instead of the guide kernel
+    bool profile = false;
+    bool profile_param = false;  // profile mode 2: time k_param<FINISH, ADAM, PREP> instead of the guide kernel
     std::vector<hipEvent_t> ev;  // start/stop pairs
     // one launch per call for the variant sorting families (bean_tile_svi.hpp): target-aligned tiles
-    bool tile_svi;            // eligible shape and not switched off (BEAN_HIP_STEP=pair)
-    bool tile_ready;          // tile table built by bean_hip_prepare
-    int* tile_tab;            // device: tile_g0[n_tiles + 1], tile_t0[n_tiles + 1]
-    int n_tiles, tile_ntm, tile_gbm, tile_blocks;
-    float* step_sizes;        // device: ClippedAdam step sizes of the steps of one call
-    DevArgs* dargs_dev;       // device copy of DevArgs for k_svi_tile's out-of-line pieces
-    uint64_t step_sizes_cap;
+    bool tile_svi = false;    // eligible shape and not switched off (BEAN_HIP_STEP=pair)
+    bool tile_ready = false;  // tile table built by bean_hip_prepare
+    int* tile_tab = nullptr;  // device: tile_g0[n_tiles + 1], tile_t0[n_tiles + 1]
+    int n_tiles = 0, tile_ntm = 0, tile_gbm = 0, tile_blocks = 0;
+    float* step_sizes = nullptr;   // device: ClippedAdam step sizes of the steps of one call
+    DevArgs* dargs_dev = nullptr;  // device copy of DevArgs for k_svi_tile's out-of-line pieces
+    uint64_t step_sizes_cap = 0;
     std::vector<uint64_t> ev_steps;  // profile mode: SVI steps covered by each timed launch
     // RCCL communicator of a guide-sharded fit (bean_hip_comm_init) and graphs of 2^k exchanged steps
-    ncclComm_t comm;
-    int comm_world;
+    ncclComm_t comm = nullptr;
+    int comm_world = 0;
     std::vector<hipGraphExec_t> graphs_xchg;
     // bean_hip_svi_resume: graphs of 2^k {guide, k_param<FINISH, ADAM, PREP>} pairs, and what the last call left
     // prepared on the device: the draw and tables of step resume_next (same seed, same stream)
     std::vector<hipGraphExec_t> graphs_resume;
-    bool resume_ok;
-    uint64_t sharded_steps;  // bean_hip_sharded_update calls since bean_hip_sharded_begin: the slots its last call finalizes
-    uint64_t resume_next, resume_seed;
-    void* resume_stream;
+    bool resume_ok = false;
+    uint64_t sharded_steps = 0;  // bean_hip_sharded_update calls since bean_hip_sharded_begin: the slots its last call finalizes
+    uint64_t resume_next = 0, resume_seed = 0;
+    void* resume_stream = nullptr;
     // all the steps of a call in ONE launch, tile-asynchronous (bean_async_v2.hpp): eligible shape and switched on
-    bool async_step;
-    int* async_ws;      // device: 8 queue counters (kAsyncQueueStride apart), the abort word, done[n_tiles]
-    int async_blocks;   // grid: resident single-wave workgroups that pull items, a multiple of 8 (0: not yet measured)
-    int async_fin_blocks;  // ... and that only finish tiles (0: no roles, the last arriver finishes)
-    size_t async_ws_ints;
-    unsigned long long* async_stamps;  // diagnostic builds (-DBEAN_ASYNC_STAMP): the last call's item timeline
-    size_t async_stamp_words;
+    bool async_step = false;
+    int* async_ws = nullptr;   // device: 8 queue counters (kAsyncQueueStride apart), the abort word, done[n_tiles]
+    int async_blocks = 0;      // grid: resident single-wave workgroups that pull items, a multiple of 8 (0: not yet measured)
+    int async_fin_blocks = 0;  // ... and that only finish tiles (0: no roles, the last arriver finishes)
+    size_t async_ws_ints = 0;
+    unsigned long long* async_stamps = nullptr;  // diagnostic builds (-DBEAN_ASYNC_STAMP): the last call's item timeline
+    size_t async_stamp_words = 0;
     // seed ensemble (bean_ensemble.hpp): K members stepped by the same launches.  Member 0 is `d` itself; member k >= 1
     // has the k-th private copy of the workspace (member_ws), of tsum_buf and of loss_acc, and the k-th part of the
     // member-major parameter / gradient / moment / loss_hist buffers
-    int n_members;
-    bool bound_any;            // a buffer has been bound: bean_hip_set_members comes too late
-    char* member_ws;           // (K - 1) copies of the workspace, member_ws_stride bytes apart
-    size_t member_ws_stride;
-    size_t tsum_stride;        // doubles of tsum per member
-    DevArgs* members_dev;      // device: DevArgs of the K members
-    std::vector<DevArgs> members_host;
-    std::vector<uint64_t> member_seeds;
-    bool members_dirty;        // members_dev is older than the bound buffers / the seeds
-    std::vector<hipGraphExec_t> graphs_ens;  // [k]: 2^k {k_param_ens, k_guide_wave2_ens} pairs
+    int n_members = 1;
+    bool bound_any = false;       // a buffer has been bound: bean_hip_set_members comes too late
+    char* member_ws = nullptr;    // (K - 1) copies of the workspace, member_ws_stride bytes apart
+    size_t member_ws_stride = 0;
+    size_t tsum_stride = 0;       // doubles of tsum per member
+    ArgSet members;               // member_args of the K members; ladder of {k_param_ens, k_guide_wave2_ens} pairs
     // per-member masks (bean_hip_bind_member_masks): (K, R, G) uint8 and (K, R, B) float64 of the caller, member-major;
     // null: every member reads the shared BEAN_BUF_REPGUIDE / BEAN_BUF_SAMPLE_MASK
-    bool members_set;          // bean_hip_set_members has been called
-    const uint8_t* member_rg;
-    const double* member_smask;
+    bool members_set = false;     // bean_hip_set_members has been called
+    const uint8_t* member_rg = nullptr;
+    const double* member_smask = nullptr;
     // per-member counts (bean_hip_bind_member_counts): (K, R, B, G) float32 of the caller, member-major; null: every
     // member reads the shared BEAN_BUF_X / BEAN_BUF_X_BC
-    const float* member_x;
-    const float* member_xbc;
+    const float* member_x = nullptr;
+    const float* member_xbc = nullptr;
     // multi-particle SVI (bean_particles.hpp): P draws per step, one update with their mean gradient.  The particles are
     // members that share the caller's single-fit parameters and moments; particle p >= 1 has the p-th private copy of the
     // workspace (member_ws), of tsum_buf and of loss_acc, and every particle row p of particle_grad and particle_loss
-    int n_particles;
-    bool particles_set;        // bean_hip_set_particles has been called
-    float* particle_grad;      // per parameter array a (P, n) float32 block, the arrays end to end (particle_arrays)
-    double* particle_loss;     // (P, loss_capacity) losses of the particles; the caller's loss_hist holds their mean
-    DevArgs* particles_dev;    // device: DevArgs of the P particles
-    std::vector<DevArgs> particles_host;
-    std::vector<uint64_t> particle_seeds;
-    bool particles_dirty;      // particles_dev is older than the bound buffers / the seeds
-    std::vector<hipGraphExec_t> graphs_part;  // [k]: 2^k particle steps (four launches each)
+    int n_particles = 1;
+    bool particles_set = false;       // bean_hip_set_particles has been called
+    float* particle_grad = nullptr;   // per parameter array a (P, n) float32 block, the arrays end to end (particle_arrays)
+    double* particle_loss = nullptr;  // (P, loss_capacity) losses of the particles; the caller's loss_hist holds their mean
+    ArgSet particles;                 // particle_args of the P particles; ladder of particle steps (four launches each)
 };
 
 extern "C" const char* bean_hip_version(void) {
@@ -330,10 +336,10 @@ static void drop_graph(bean_hip_ctx* c) {
     destroy_graphs(c->graphs_fused);
     destroy_graphs(c->graphs_xchg);
     destroy_graphs(c->graphs_resume);
-    destroy_graphs(c->graphs_ens);
-    destroy_graphs(c->graphs_part);
-    c->members_dirty = true;
-    c->particles_dirty = true;
+    for (ArgSet* a : {&c->members, &c->particles}) {
+        destroy_graphs(a->ladder);
+        a->dirty = true;
+    }
     c->resume_ok = false;  // (called whenever a buffer, the shape-dependent state or the seed changes)
 }
 
@@ -343,6 +349,142 @@ static void drop_graph(bean_hip_ctx* c) {
 static void drop_graph_on_seed_change(bean_hip_ctx* c, unsigned long long seed) {
     const bool any = !c->graphs.empty() || !c->graphs_fused.empty() || !c->graphs_xchg.empty() || !c->graphs_resume.empty();
     if (any && c->graph_seed != seed) drop_graph(c);
+}
+
+// ---- an ArgSet's device array, and bringing it up to date
+static void free_args(ArgSet& a) {
+    destroy_graphs(a.ladder);  // (they hold the array's address)
+    if (a.dev) (void)hipFree(a.dev);
+    a.dev = nullptr;
+    a.seeds.clear();
+    a.dirty = true;
+}
+static int alloc_args(ArgSet& a, int n) {
+    free_args(a);
+    HIP_OK(hipMalloc((void**)&a.dev, (size_t)n * sizeof(DevArgs)));
+    return 0;
+}
+// The n copies' arguments, copy k as make(k, seeds[k]) gives it now, to the device array - unless the array was built
+// with these seeds and nothing has been bound since.  (The launches hold the ADDRESS of the array: new seeds need no
+// new graphs.)
+template <typename Make>
+static int refresh_args(ArgSet& a, int n, const uint64_t* seeds, hipStream_t stream, Make&& make) {
+    bool same = !a.dirty && (int)a.seeds.size() == n;
+    for (int k = 0; same && k < n; ++k) same = a.seeds[(size_t)k] == seeds[k];
+    if (same) return 0;
+    HIP_OK(hipStreamSynchronize(stream));  // no launch in flight reads the array while it changes
+    a.host.resize((size_t)n);
+    for (int k = 0; k < n; ++k) a.host[(size_t)k] = make(k, seeds[k]);
+    HIP_OK(hipMemcpyAsync(a.dev, a.host.data(), (size_t)n * sizeof(DevArgs), hipMemcpyHostToDevice, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    a.seeds.assign(seeds, seeds + n);
+    a.dirty = false;
+    return 0;
+}
+
+// ---- the workspace: ONE list of its regions
+// Every region of the workspace, in allocation order: v(pointer that owns the region, its size in doubles).  The
+// pointers are fields of `d` (tile_targets_dev, which is not one, comes back through `tile_targets_dev`).  The list has
+// three uses and no second copy: bean_hip_create sums the sizes, then hands out the allocation region by region
+// (c->d), and relocate_private moves a member's or particle's pointers to its own copy of the workspace.  A region the
+// shape does not have is not visited and its pointer stays null.  Needs the shape-dependent switches of `c` and the
+// scalars of `d` that bean_hip_create sets ahead of its first use (n_cov, n_tiles, n_gamma_blocks, n_arrival_ctr,
+// n_lpart).
+template <typename V>
+static void workspace_regions(const bean_hip_ctx* c, DevArgs& d, V&& v, int** tile_targets_dev = nullptr) {
+    const bean_hip_shape& s = c->shape;
+    const bool tiling = is_tiling(s), surv = is_survival(s);
+    const bool surv_mix = surv && s.family == BEAN_FAMILY_MIXTURE_NORMAL, surv_norm = is_surv_normal(s);
+    const uint64_t R = (uint64_t)d.R, B = (uint64_t)d.B, G = (uint64_t)d.G, T = (uint64_t)d.T, n_cov = (uint64_t)d.n_cov;
+    const uint64_t A1 = tiling ? (uint64_t)(d.A - 1) : 0;
+    auto opt = [&](auto& p, uint64_t n) {
+        if (n) v(p, n);
+    };
+    // tables: a column per allele slot, or per target (per replicate and target with sample covariates)
+    const uint64_t n_tab = B * (tiling ? A1 * G : T * (n_cov ? R : 1));
+    v(d.tabP, n_tab);
+    v(d.tabPmu, n_tab);
+    v(d.tabPy, n_tab);
+    v(d.P0, B);
+    v(d.mu_t, T);
+    v(d.y_t, T);
+    v(d.eps_mu, T);
+    v(d.eps_sd, T);
+    v(d.part, (uint64_t)(tiling ? (d.A > kAMax ? tq_num(d.A) : kTNumPart) : kNumPart) * G);
+    v(d.mu_a, A1 * G);
+    v(d.sig_a, A1 * G);
+    v(d.lpn, G);
+    v(d.eps_noise, G);
+    opt(d.kacc, (s.flags & BEAN_FLAG_SCALE_BY_ACC) ? G : 0);  // filled by bean_hip_prepare (k_acc_scale)
+    v(d.loss_const, 1);
+    v(d.const_acc, kLossWords);
+    int* tile_targets = nullptr;  // two ints: k_tile_targets, k_max_target_len
+    v(tile_targets, 1);
+    if (tile_targets_dev) *tile_targets_dev = tile_targets;
+    // arrival counters, n_arrival_ctr ints that k_set_step zeroes from tile_ctr on.  The fused step kernel's: per tile and
+    // per tile boundary, half each, then the distinct bin edges.  Tiling: k_param's allele blocks' counters and go flags
+    if (c->wave2) {
+        v(d.tile_ctr, (uint64_t)d.n_arrival_ctr / 4);
+        v(d.bnd_ctr, (uint64_t)d.n_arrival_ctr / 4);
+        v(d.ue_z, 2 * B);
+        v(d.ue_idx, B + 2);  // 2 B + 1 ints
+    } else {
+        opt(d.tile_ctr, (uint64_t)d.n_arrival_ctr / 2);
+    }
+#ifdef BEAN_STAMP
+    v(d.dbg, 8 * 2 * R * (((uint64_t)((G + 63) / 64 + 1) + 7) / 8 * 8));
+#endif
+    // per-replicate rows of the guide kernels
+    if (c->tiling_wave || c->tiling_wide) v(d.trow, (uint64_t)(c->tiling_wave ? kTNumPart : tq_num(d.A)) * R * G);
+    if (c->wave_guide && c->wave2) {
+        v(d.wrow, (uint64_t)kW2Rows * R * G);  // count totals are re-summed in the kernel: no nobs
+    } else if (c->wave_guide) {
+        v(d.wrow, (uint64_t)kNumPart * R * G);
+        v(d.nobs, 2 * R * G);
+    } else if (c->surv_wave) {
+        v(d.wrow, (uint64_t)kW2Rows * R * G);
+    }
+    if (!surv && !tiling && !c->fused_guide) {  // the split form
+        v(d.rrow, 3 * R * G);
+        if (is_mixture(s)) {
+            v(d.pi_ws, 2 * R * G);
+            v(d.gpi_ws, 2 * R * G);
+        }
+    }
+    // survival: the baseline draw; the Dirichlet-over-all-guides site (gsum: gsum_ws); where q_0 enters the likelihood,
+    // its gradient rows and their projection sums (sq: sq_ws)
+    if (surv_mix || (surv && tiling)) {
+        v(d.u_g, G);
+        v(d.eps_u, G);
+    }
+    if (surv_mix || surv_norm) {
+        v(d.gam, R * G);
+        v(d.gpart, (uint64_t)d.n_gamma_blocks * (R + 1));
+        v(d.gsum, R + 1);
+    }
+    if (surv_norm) {
+        v(d.gq, R * G);
+        v(d.sq, R);
+    }
+    if (n_cov) {
+        v(d.cov_mu, n_cov);
+        v(d.cov_eps, n_cov);
+        v(d.cov_shift, R);
+        v(d.cov_sum, R);  // (cov_sum_ws)
+    }
+    const bool wave_rows = c->wave2 || c->surv_wave;
+    opt(d.dgq, (wave_rows && s.family == BEAN_FAMILY_MIXTURE_NORMAL) ? 6 * G : 0);
+    opt(d.dgq_t, (c->tiling_wave || c->tiling_rep) ? (uint64_t)(kAMax + 1) * G : 0);
+    opt(d.lpart, 3 * (uint64_t)d.n_lpart);  // per-wave loss parts of the wave-form guide kernels
+    v(d.q0_ctr, 1);
+    static_assert(sizeof(StepCtr) == 24, "a StepCtr takes three doubles");
+    v(d.ctrA, 3);
+    v(d.ctrB, 3);
+    // Nobody's: the closed formula that sized the workspace before this list counted 2 doubles more than it handed out,
+    // and the covariate shifts and sums (2 R) for every shape.  Kept, at the end, so that workspace_bytes and the
+    // members' stride are what they were; shrinking it is a change of its own.
+    double* spare = nullptr;
+    v(spare, 2 + (n_cov ? 0 : 2 * R));
 }
 
 // ------------------------------------------------------------------ create / bind / prepare
@@ -382,11 +524,7 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
         return fail("bean_hip_create: shard offsets outside the whole screen");
 
     bean_hip_ctx* c = new bean_hip_ctx();
-    memset(&c->d, 0, sizeof(DevArgs));
-    memset(c->slot_ptr, 0, sizeof(c->slot_ptr));
-    memset(c->slot_bytes, 0, sizeof(c->slot_bytes));
     c->shape = *s;
-    c->prepared = false;
     {
         // diagnostic A/B switch for the sorting variant families: the split (three launch) form
         const char* env = getenv("BEAN_HIP_SPLIT_GUIDE");
@@ -413,56 +551,10 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
         }
 #endif
     }
-    c->graph_seed = 0;
-    c->resume_ok = false;
-    c->resume_next = c->resume_seed = 0;
-    c->sharded_steps = 0;
-    c->resume_stream = nullptr;
-    c->comm = nullptr;
-    c->comm_world = 0;
-    c->tile_svi = false;
-    c->tile_ready = false;
-    c->tile_tab = nullptr;
-    c->live_slots = nullptr;
-    c->alleles_fresh = false;
-    c->resume_head_fresh = false;
     {
         const char* am = getenv("BEAN_HIP_ALLELE");
         c->allele_blocks = !(am && !strcmp(am, "split"));
     }
-    c->n_tiles = c->tile_ntm = c->tile_gbm = c->tile_blocks = 0;
-    c->step_sizes = nullptr;
-    c->step_sizes_cap = 0;
-    c->dargs_dev = nullptr;
-    c->async_step = false;
-    c->async_ws = nullptr;
-    c->async_blocks = 0;
-    c->async_fin_blocks = 0;
-    c->async_ws_ints = 0;
-    c->async_stamps = nullptr;
-    c->async_stamp_words = 0;
-    c->n_members = 1;
-    c->bound_any = false;
-    c->member_ws = nullptr;
-    c->member_ws_stride = 0;
-    c->tsum_stride = 0;
-    c->members_dev = nullptr;
-    c->members_dirty = true;
-    c->members_set = false;
-    c->member_rg = nullptr;
-    c->member_smask = nullptr;
-    c->member_x = nullptr;
-    c->member_xbc = nullptr;
-    c->n_particles = 1;
-    c->particles_set = false;
-    c->particle_grad = nullptr;
-    c->particle_loss = nullptr;
-    c->particles_dev = nullptr;
-    c->particles_dirty = true;
-    c->loss_acc = nullptr;
-    c->profile = false;
-    c->profile_param = false;
-    c->loss_capacity = 0;
     DevArgs& d = c->d;
     d.R = s->n_reps; d.B = s->n_condits; d.G = s->n_guides; d.T = s->n_targets;
     d.A = s->n_max_alleles; d.C = s->n_ctrl; d.E = s->n_edits;
@@ -484,35 +576,19 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
     d.survival = is_survival(*s) ? 1 : 0;
     d.neg_loc = s->negctrl_loc; d.neg_scale = s->negctrl_scale;
 
-    const uint64_t B = d.B, T = d.T, G = d.G;
-    const uint64_t A1 = is_tiling(*s) ? (uint64_t)(d.A - 1) : 0;
-    const uint64_t n_cov = (uint64_t)s->n_sample_covariates;
-    // table columns: allele slots or targets (per replicate with sample covariates)
-    const uint64_t n_tab = is_tiling(*s) ? A1 * G : T * (n_cov ? (uint64_t)s->n_reps : 1);
-    const uint64_t n_part = is_tiling(*s) ? (uint64_t)(s->n_max_alleles > kAMax ? tq_num(s->n_max_alleles) : kTNumPart)
-                                          : (uint64_t)kNumPart;
+    const uint64_t G = d.G;
     const bool surv_mix = is_survival(*s) && s->family == BEAN_FAMILY_MIXTURE_NORMAL;
-    const bool surv_tiling = is_survival(*s) && is_tiling(*s);
     const bool surv_norm = is_surv_normal(*s);
     d.surv_q0lik = surv_norm ? 1 : 0;
     d.not_loss_owner = (s->flags & BEAN_FLAG_NOT_LOSS_OWNER) ? 1 : 0;
-    c->gsum_ws = nullptr;
-    c->sq_ws = nullptr;
-    c->cov_sum_ws = nullptr;
-    const uint64_t Rr = d.R;
     // guide blocks of k_param: kParamBlock guides each.  The survival families with a
     // Dirichlet-over-all-guides site have q0 blocks as well (after the alpha_pi blocks of MixtureNormal),
     // kParamBlock guides each: parameter update, gamma draws and normalisers of that site
     // (q0_draws_and_totals)
     d.q0_blocks = (surv_mix || surv_norm) ? 1 : 0;
     d.q0_blk0 = surv_mix ? (int)((G + kParamBlock - 1) / kParamBlock) : 0;
-    const uint64_t n_gblk = (G + kParamBlock - 1) / kParamBlock;
-    d.n_gamma_blocks = (int)n_gblk;
-    const uint64_t n_surv = (surv_mix ? 2 * G + Rr * G + n_gblk * (Rr + 1) + (Rr + 1) : 0) +
-                            (surv_norm ? 2 * Rr * G + n_gblk * (Rr + 1) + (Rr + 1) + Rr : 0) +
-                            (surv_tiling ? 2 * G : 0);
+    d.n_gamma_blocks = (int)((G + kParamBlock - 1) / kParamBlock);
     const bool split_ok = !is_survival(*s) && !is_tiling(*s);
-    const bool use_split = split_ok && !c->fused_guide;
     c->wave_guide = c->wave_guide && split_ok;
     c->wave2 = c->wave2 && c->wave_guide;
     if (s->n_sample_covariates > 0 && !c->wave2) {
@@ -529,9 +605,7 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
         d.seg_steps = 0;
         while ((1 << d.seg_steps) < seg) ++d.seg_steps;
     }
-    c->tsum_buf = nullptr;
-    c->tdesc_buf = nullptr;
-    c->surv_wave = c->surv_wave && is_survival(*s) && !is_tiling(*s);
+    c->surv_wave =c->surv_wave && is_survival(*s) && !is_tiling(*s);
     d.rows_v2 = (c->wave2 || c->surv_wave) ? 1 : 0;
 
     c->tiling_wide = is_tiling(*s) && s->n_max_alleles > kAMax;
@@ -584,9 +658,6 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
                       (s->family == BEAN_FAMILY_MIXTURE_NORMAL || s->family == BEAN_FAMILY_NORMAL) &&
                       gb >= 1 && s->max_target_len <= gb && (sm && !strcmp(sm, "tile"));
     }
-#else
-    c->fused_step = false;
-    c->tile_svi = false;
 #endif
     {
         // ALL the steps of a call in one launch, no grid-wide boundary between steps (bean_async_v2.hpp): the variant
@@ -603,28 +674,17 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
                         !c->fused_step && !c->tile_svi &&
                         (s->family == BEAN_FAMILY_MIXTURE_NORMAL || s->family == BEAN_FAMILY_NORMAL) && !is_survival(*s);
     }
-    const uint64_t n_trow = c->tiling_wave ? (uint64_t)kTNumPart * Rr * G
-                                           : (c->tiling_wide ? (uint64_t)tq_num(d.A) * Rr * G : 0);
-    const uint64_t n_split = use_split ? (3 + (is_mixture(*s) ? 4 : 0)) * Rr * G
-                                       : (c->wave_guide ? (uint64_t)(c->wave2 ? kW2Rows : kNumPart + 2) * Rr * G
-                                                        : (c->surv_wave ? (uint64_t)kW2Rows * Rr * G : 0));
-#ifdef BEAN_STAMP
-    const uint64_t n_dbg = 8 * 2 * Rr * (((uint64_t)((G + 63) / 64 + 1) + 7) / 8 * 8);
-#else
-    const uint64_t n_dbg = 0;
-#endif
-    // per-wave loss parts of the wave-form guide kernels (1-D grid of padded tiles x replicates)
-    const uint64_t n_lpart = (c->wave2 || c->surv_wave) ? ((uint64_t)d.n_tiles + 7) / 8 * 8 * Rr : 0;
-    const uint64_t n_dgq = ((c->wave2 || c->surv_wave) && s->family == BEAN_FAMILY_MIXTURE_NORMAL) ? 6 * G : 0;
-    const uint64_t n_dgq_t = (c->tiling_wave || c->tiling_rep) ? (uint64_t)(kAMax + 1) * G : 0;
-    // arrival counters of the fused step kernel: per tile and per tile boundary (ints, zero between launches)
-    const uint64_t n_ctr = c->wave2 ? ((uint64_t)d.n_tiles + 7) / 8 * 8 + 2 + 3 * B + 2 : 0;
-    const uint64_t n_kacc = (s->flags & BEAN_FLAG_SCALE_BY_ACC) ? G : 0;
-    // tiling, k_param's allele blocks: arrival counters and go flags, one 128-byte line each (kAlleleCtrLines)
-    const uint64_t n_actr = (!c->wave2 && is_tiling(*s)) ? (uint64_t)kAlleleCtrLines * 16 : 0;
-    const uint64_t n_dbl = n_actr + n_kacc + n_ctr + 3 * B * n_tab + B + 4 * T + n_part * G + 2 * G + 2 * A1 * G + 2 + 8 + kLossWords + n_surv +
-                           n_split + n_dbg + n_trow + 3 * n_lpart + n_dgq + n_dgq_t + 2 * n_cov + 2 * Rr + 1;
-    c->workspace_bytes = n_dbl * 8;
+    // the workspace (workspace_regions).  The scalars that go with two of its regions come first: the list takes those
+    // regions' sizes from them.  Arrival counters (ints, zero between launches): of the fused step kernel, per tile and
+    // per tile boundary - two even halves; tiling: of k_param's allele blocks, counters and go flags, one 128-byte line
+    // each (kAlleleCtrLines).  Per-wave loss parts of the wave-form guide kernels: padded tiles x replicates
+    const uint64_t tiles8 = ((uint64_t)d.n_tiles + 7) / 8 * 8;
+    d.n_arrival_ctr = c->wave2 ? (int)(2 * (tiles8 + 2)) : (is_tiling(*s) ? 2 * kAlleleCtrLines * 16 : 0);
+    d.n_lpart = (c->wave2 || c->surv_wave) ? (int)(tiles8 * (uint64_t)d.R) : 0;
+    d.tile_targets = 64;
+    uint64_t n_measured = 0;
+    workspace_regions(c, d, [&](auto&, uint64_t n) { n_measured += n; });
+    c->workspace_bytes = n_measured * 8;
     hipError_t e = hipMalloc(&c->workspace, c->workspace_bytes);
     if (e != hipSuccess) {
         delete c;
@@ -637,102 +697,21 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
         return fail(std::string("hipMemset workspace: ") + hipGetErrorString(e));
     }
     double* w = (double*)c->workspace;
-    d.tabP = w; w += B * n_tab;
-    d.tabPmu = w; w += B * n_tab;
-    d.tabPy = w; w += B * n_tab;
-    d.P0 = w; w += B;
-    d.mu_t = w; w += T;
-    d.y_t = w; w += T;
-    d.eps_mu = w; w += T;
-    d.eps_sd = w; w += T;
-    d.part = w; w += n_part * G;
-    d.mu_a = w; w += A1 * G;
-    d.sig_a = w; w += A1 * G;
-    d.lpn = w; w += G;
-    d.eps_noise = w; w += G;
-    if (n_kacc) {
-        d.kacc = w; w += G;  // filled by bean_hip_prepare (k_acc_scale)
+    workspace_regions(c, d, [&](auto& p, uint64_t n) {
+        p = (std::remove_reference_t<decltype(p)>)w;
+        w += n;
+    }, &c->tile_targets_dev);
+    if ((uint64_t)(w - (double*)c->workspace) != n_measured) {
+        const std::string msg = "bean_hip_create: the workspace regions take " + std::to_string(w - (double*)c->workspace) +
+                                " doubles, " + std::to_string(n_measured) + " were measured";
+        (void)hipFree(c->workspace);
+        delete c;
+        return fail(msg);
     }
-    d.loss_const = w; w += 1;
-    d.const_acc = (long long*)w; w += kLossWords;
-    c->tile_targets_dev = (int*)w; w += 1;
-    d.tile_targets = 64;
-    if (n_ctr) {
-        d.tile_ctr = (int*)w;
-        d.bnd_ctr = d.tile_ctr + (n_ctr - 3 * B - 2);
-        d.n_arrival_ctr = (int)(2 * (n_ctr - 3 * B - 2));  // ints: two per double of this region
-        w += n_ctr - 3 * B - 2;
-        d.ue_z = w; w += 2 * B;
-        d.ue_idx = (int*)w; w += B + 2;  // 2 B + 1 ints
-    }
-    if (n_actr) {  // (k_set_step zeroes tile_ctr[0 .. n_arrival_ctr))
-        d.tile_ctr = (int*)w;
-        d.n_arrival_ctr = (int)(2 * n_actr);
-        w += n_actr;
-    }
-    if (n_dbg) {
-        d.dbg = (unsigned long long*)w; w += n_dbg;
-    }
-    if (c->tiling_wave || c->tiling_wide) {
-        d.trow = w; w += n_trow;
-    }
-    if (c->wave_guide && c->wave2) {
-        d.wrow = w; w += (uint64_t)kW2Rows * Rr * G;  // count totals are re-summed in the kernel: no nobs
-    } else if (c->wave_guide) {
-        d.wrow = w; w += (uint64_t)kNumPart * Rr * G;
-        d.nobs = w; w += 2 * Rr * G;
-    } else if (c->surv_wave) {
-        d.wrow = w; w += (uint64_t)kW2Rows * Rr * G;
-    }
-    if (use_split) {
-        d.rrow = w; w += 3 * Rr * G;
-        if (is_mixture(*s)) {
-            d.pi_ws = w; w += 2 * Rr * G;
-            d.gpi_ws = w; w += 2 * Rr * G;
-        }
-    }
-    if (surv_mix) {
-        d.u_g = w; w += G;
-        d.eps_u = w; w += G;
-        d.gam = w; w += Rr * G;
-        d.gpart = w; w += n_gblk * (Rr + 1);
-        d.gsum = w; w += Rr + 1;
-        c->gsum_ws = d.gsum;
-    }
-    if (surv_tiling) {
-        d.u_g = w; w += G;
-        d.eps_u = w; w += G;
-    }
-    if (surv_norm) {
-        d.gam = w; w += Rr * G;
-        d.gpart = w; w += n_gblk * (Rr + 1);
-        d.gsum = w; w += Rr + 1;
-        c->gsum_ws = d.gsum;
-        d.gq = w; w += Rr * G;
-        d.sq = w; w += Rr;
-        c->sq_ws = d.sq;
-    }
-    if (n_cov) {
-        d.cov_mu = w; w += n_cov;
-        d.cov_eps = w; w += n_cov;
-        d.cov_shift = w; w += Rr;
-        d.cov_sum = w; w += Rr;
-        c->cov_sum_ws = d.cov_sum;
-    }
-    if (n_dgq) {
-        d.dgq = w; w += n_dgq;
-    }
-    if (n_dgq_t) {
-        d.dgq_t = w; w += n_dgq_t;
-    }
-    if (n_lpart) {
-        d.lpart = (long long*)w; w += 3 * n_lpart;
-        d.n_lpart = (int)n_lpart;
-    }
-    d.q0_ctr = (int*)w; w += 1;
-    static_assert(sizeof(StepCtr) == 24, "two StepCtr take 6 of the 8 spare workspace doubles");
-    d.ctrA = (StepCtr*)w; w += 3;
-    d.ctrB = (StepCtr*)w; w += 3;
+    // the library's own exchange buffers are workspace regions (null where the shape has none)
+    c->gsum_ws = d.gsum;
+    c->sq_ws = d.sq;
+    c->cov_sum_ws = d.cov_sum;
     *out = c;
     return 0;
 }
@@ -753,10 +732,10 @@ extern "C" int bean_hip_destroy(bean_hip_ctx* c) {
     if (c->async_ws) (void)hipFree(c->async_ws);
     if (c->loss_acc) (void)hipFree(c->loss_acc);
     if (c->member_ws) (void)hipFree(c->member_ws);
-    if (c->members_dev) (void)hipFree(c->members_dev);
     if (c->particle_grad) (void)hipFree(c->particle_grad);
     if (c->particle_loss) (void)hipFree(c->particle_loss);
-    if (c->particles_dev) (void)hipFree(c->particles_dev);
+    free_args(c->members);
+    free_args(c->particles);
     delete c;
     return 0;
 }
@@ -845,7 +824,7 @@ static int check_bound(bean_hip_ctx* c, bool need_grads, bool need_moments) {
     return 0;
 }
 
-static int upload_members(bean_hip_ctx* c, const uint64_t* seeds, hipStream_t stream);
+static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed);
 // private copies of everything a step writes: one per ensemble member or per particle (the two exclude each other)
 static int n_copies(const bean_hip_ctx* c) { return c->n_members > 1 ? c->n_members : c->n_particles; }
 static int alloc_workspace_copies(bean_hip_ctx* c, int n);
@@ -1033,13 +1012,15 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         // (the array is uploaded with the seeds known so far - zeros before the first run - and is then current: a
         // bean_hip_svi_run_ensemble with those seeds does not upload it again)
         const int K = c->n_members;
-        if ((int)c->member_seeds.size() != K) c->member_seeds.assign((size_t)K, 0);
-        if (upload_members(c, c->member_seeds.data(), stream)) return -1;
-        c->members_dirty = false;
+        std::vector<uint64_t> seeds = c->members.seeds;
+        if ((int)seeds.size() != K) seeds.assign((size_t)K, 0);
+        c->members.dirty = true;  // (this prepare has changed what member_args reads: tsum, tile_targets)
+        if (refresh_args(c->members, K, seeds.data(), stream, [&](int k, uint64_t seed) { return member_args(c, k, seed); }))
+            return -1;
         for (int k = 0; k < K; ++k)
-            HIP_OK(hipMemsetAsync(c->members_host[(size_t)k].const_acc, 0, kLossWords * sizeof(long long), stream));
+            HIP_OK(hipMemsetAsync(c->members.host[(size_t)k].const_acc, 0, kLossWords * sizeof(long long), stream));
         hipLaunchKernelGGL(k_prepare_ens, dim3((unsigned)((n + 255) / 256), (unsigned)K), dim3(256), 0, stream,
-                           (const DevArgs*)c->members_dev);
+                           (const DevArgs*)c->members.dev);
         HIP_OK(hipGetLastError());
         HIP_OK(hipStreamSynchronize(stream));
     }
@@ -1563,6 +1544,20 @@ static int replay_pairs(bean_hip_ctx* c, const std::vector<hipGraphExec_t>& ladd
     return 0;
 }
 
+// The ladder of an ArgSet, cut like bean_hip_svi_run's pair path: graphs of 1, 2, 4, ... <= graph_chunk units of what
+// enqueue_n launches.  A ladder of another size is this set's alone to drop; so is one that could not be built.
+template <typename EnqueueN>
+static int ensure_ladder(bean_hip_ctx* c, ArgSet& a, hipStream_t stream, int32_t graph_chunk, EnqueueN&& enqueue_n) {
+    const int n_rungs = top_rung(graph_chunk, 1, 10) + 1;
+    if ((int)a.ladder.size() == n_rungs) return 0;
+    destroy_graphs(a.ladder);
+    if (build_ladder(c, a.ladder, stream, n_rungs, 1, c->alleles_fresh, enqueue_n)) {
+        destroy_graphs(a.ladder);
+        return -1;
+    }
+    return 0;
+}
+
 #ifdef BEAN_AB_KERNELS
 
 // ---- one launch per call: bean_tile_svi.hpp
@@ -1855,40 +1850,33 @@ extern "C" int bean_hip_set_members(bean_hip_ctx* c, int32_t n_members) {
         return fail("bean_hip_set_members: this handle steps " + std::to_string(c->n_particles) +
                     " particles (bean_hip_set_particles): particles inside member sets are not batched");
     static_assert(BEAN_HIP_MAX_MEMBERS == kEnsembleMaxMembers, "the header's cap is the kernels'");
-    if (c->members_dev) (void)hipFree(c->members_dev);
-    c->members_dev = nullptr;
+    free_args(c->members);
     c->n_members = 1;
     if (c->n_particles == 1 && alloc_workspace_copies(c, n_members)) return -1;
-    HIP_OK(hipMalloc((void**)&c->members_dev, (size_t)n_members * sizeof(DevArgs)));
+    if (alloc_args(c->members, n_members)) return -1;
     c->n_members = n_members;
     c->members_set = true;
     c->member_rg = nullptr;  // (sized for another K)
     c->member_smask = nullptr;
     c->member_x = nullptr;
     c->member_xbc = nullptr;
-    c->member_seeds.clear();
     c->prepared = false;
     drop_graph(c);
     return 0;
 }
 
 // What members and particles share.  m is a copy of c->d: every pointer into the workspace moves to the k-th private
-// copy of it (k >= 1), tsum and the loss accumulators to their k-th part (the one list of those fields)
+// copy of it (k >= 1) - every region of workspace_regions whose pointer lies in the workspace: sync_devargs may have put
+// a caller's buffer in the place of gsum, sq or cov_sum - and tsum and the loss accumulators, allocations of their own,
+// to their k-th part
 static void relocate_private(const bean_hip_ctx* c, DevArgs& m, int k) {
     const char* w0 = (const char*)c->workspace;
     const char* w1 = w0 + c->workspace_bytes;
     const ptrdiff_t off = (c->member_ws + (size_t)(k - 1) * c->member_ws_stride) - (char*)c->workspace;
-#define BEAN_WS(f)                                                                  \
-    do {                                                                            \
-        const char* q_ = (const char*)m.f;                                          \
-        if (q_ && q_ >= w0 && q_ < w1) m.f = (decltype(m.f))(const_cast<char*>(q_) + off); \
-    } while (0)
-    BEAN_WS(tabP); BEAN_WS(tabPmu); BEAN_WS(tabPy); BEAN_WS(P0); BEAN_WS(mu_t); BEAN_WS(y_t); BEAN_WS(eps_mu); BEAN_WS(eps_sd);
-    BEAN_WS(part); BEAN_WS(mu_a); BEAN_WS(sig_a); BEAN_WS(lpn); BEAN_WS(eps_noise); BEAN_WS(kacc); BEAN_WS(loss_const);
-    BEAN_WS(const_acc); BEAN_WS(tile_ctr); BEAN_WS(bnd_ctr); BEAN_WS(ue_z); BEAN_WS(ue_idx); BEAN_WS(dbg); BEAN_WS(wrow);
-    BEAN_WS(nobs); BEAN_WS(rrow); BEAN_WS(pi_ws); BEAN_WS(gpi_ws); BEAN_WS(trow); BEAN_WS(dgq); BEAN_WS(dgq_t); BEAN_WS(lpart);
-    BEAN_WS(q0_ctr); BEAN_WS(ctrA); BEAN_WS(ctrB);
-#undef BEAN_WS
+    workspace_regions(c, m, [&](auto& p, uint64_t) {
+        const char* q = (const char*)p;
+        if (q && q >= w0 && q < w1) p = (std::remove_reference_t<decltype(p)>)(const_cast<char*>(q) + off);
+    });
     m.loss_acc += (size_t)k * c->loss_capacity * kLossSub * kLossWords;
     if (m.tsum) m.tsum += (size_t)k * c->tsum_stride;
 }
@@ -1930,17 +1918,6 @@ static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
     return m;
 }
 
-// the members' arguments, as they are now, to the device array the `_ens` launches read
-static int upload_members(bean_hip_ctx* c, const uint64_t* seeds, hipStream_t stream) {
-    const int K = c->n_members;
-    HIP_OK(hipStreamSynchronize(stream));  // no launch in flight reads the array while it changes
-    c->members_host.resize((size_t)K);
-    for (int k = 0; k < K; ++k) c->members_host[(size_t)k] = member_args(c, k, seeds[k]);
-    HIP_OK(hipMemcpyAsync(c->members_dev, c->members_host.data(), (size_t)K * sizeof(DevArgs), hipMemcpyHostToDevice, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    return 0;
-}
-
 extern "C" int bean_hip_bind_member_masks(bean_hip_ctx* c, const void* repguide, uint64_t repguide_bytes,
                                           const void* sample_mask, uint64_t sample_mask_bytes) {
     if (!c) return fail("bean_hip_bind_member_masks: null handle");
@@ -1962,7 +1939,7 @@ extern "C" int bean_hip_bind_member_masks(bean_hip_ctx* c, const void* repguide,
     }
     c->member_rg = (const uint8_t*)repguide;
     c->member_smask = (const double*)sample_mask;
-    drop_graph(c);        // (members_dev is older than the masks now)
+    drop_graph(c);        // (the members' arguments are older than the masks now)
     c->prepared = false;  // the data-only constants are stale: bean_hip_prepare comes next
     return 0;
 }
@@ -1993,7 +1970,7 @@ extern "C" int bean_hip_bind_member_counts(bean_hip_ctx* c, const void* x, uint6
     }
     c->member_x = (const float*)x;
     c->member_xbc = (const float*)x_bcmatch;
-    drop_graph(c);        // (members_dev is older than the counts now)
+    drop_graph(c);        // (the members' arguments are older than the counts now)
     c->prepared = false;  // the loss constant holds the counts' log-factorials: bean_hip_prepare comes next
     return 0;
 }
@@ -2026,8 +2003,8 @@ static void launch_guide_ens(bean_hip_ctx* c, hipStream_t stream, const DevArgs*
 
 static void enqueue_pairs_ens(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
     for (uint64_t i = 0; i < n; ++i) {
-        launch_param_ens<true, true, true>(c, stream, c->members_dev, c->n_members);
-        launch_guide_ens(c, stream, c->members_dev, c->n_members);
+        launch_param_ens<true, true, true>(c, stream, c->members.dev, c->n_members);
+        launch_guide_ens(c, stream, c->members.dev, c->n_members);
     }
 }
 
@@ -2045,58 +2022,53 @@ static void launch_finalize_ens(hipStream_t stream, const DevArgs* mem, int K, u
                        stream, mem, (unsigned long long)first_step, (unsigned long long)n_steps, 0);
 }
 
-extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
-                                         uint64_t n_steps, int32_t graph_chunk, void* stream_) {
-    if (!c) return fail("bean_hip_svi_run_ensemble: null handle");
-    if (!seeds) return fail("bean_hip_svi_run_ensemble: null seeds");
-    if (n_seeds != c->n_members)
-        return fail("bean_hip_svi_run_ensemble: " + std::to_string(n_seeds) + " seeds for " + std::to_string(c->n_members) +
-                    " member(s) (bean_hip_set_members)");
-    if (!ensemble_shape_ok(c))
-        return fail("bean_hip_svi_run_ensemble: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
-    // (a handle that never heard of members is an ensemble of one)
-    if (!c->members_dev) HIP_OK(hipMalloc((void**)&c->members_dev, (size_t)c->n_members * sizeof(DevArgs)));
+// The checks bean_hip_svi_run_ensemble and bean_hip_svi_run_particles open with, in the order they have always had;
+// `who` prefixes the messages.  Returns as begin_steps does.
+static int begin_copies(bean_hip_ctx* c, const char* who_, bool particles, const uint64_t* seeds, int32_t n_seeds,
+                        uint64_t first_step, uint64_t n_steps) {
+    const std::string who = who_;
+    if (!c) return fail(who + ": null handle");
+    if (!seeds) return fail(who + ": null seeds");
+    if (particles && !c->particles_set) return fail(who + ": call bean_hip_set_particles first");
+    const int n = particles ? c->n_particles : c->n_members;
+    if (n_seeds != n)
+        return fail(who + ": " + std::to_string(n_seeds) + " seeds for " + std::to_string(n) +
+                    (particles ? " particle(s) (bean_hip_set_particles)" : " member(s) (bean_hip_set_members)"));
+    if (!ensemble_shape_ok(c)) return fail(who + ": the batched kernels do not take this shape (bean_hip_ensemble_supported)");
     // (pi_out without kDumpPi refuses here and nowhere else: inherited, not reviewed here)
     if (per_step_noise(c->d) || c->d.pi_out)
-        return fail("bean_hip_svi_run_ensemble: injected or dumped noise belongs to single fits");
-    const int go = begin_steps(c, "bean_hip_svi_run_ensemble", first_step, n_steps);
+        return fail(who + ": injected or dumped noise belongs to single " + (particles ? "evaluations" : "fits"));
+    if (particles && check_bound(c, true, true)) return -1;  // (the mean gradient goes to the bound gradient buffers)
+    return begin_steps(c, who_, first_step, n_steps);
+}
+
+extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
+                                         uint64_t n_steps, int32_t graph_chunk, void* stream_) {
+    const int go = begin_copies(c, "bean_hip_svi_run_ensemble", false, seeds, n_seeds, first_step, n_steps);
     if (go <= 0) return go;
     hipStream_t stream = (hipStream_t)stream_;
     c->resume_ok = false;
     const int K = c->n_members;
-    bool same = !c->members_dirty && (int)c->member_seeds.size() == K;
-    for (int k = 0; same && k < K; ++k) same = c->member_seeds[(size_t)k] == seeds[k];
-    if (!same) {
-        // (the launches - captured ones too - hold the ADDRESS of this array: new seeds need no new graphs)
-        if (upload_members(c, seeds, stream)) return -1;
-        c->member_seeds.assign(seeds, seeds + K);
-        c->members_dirty = false;
-    }
+    ArgSet& a = c->members;
+    if (!a.dev && alloc_args(a, K)) return -1;  // (a handle that never heard of members is an ensemble of one)
+    if (refresh_args(a, K, seeds, stream, [&](int k, uint64_t seed) { return member_args(c, k, seed); })) return -1;
     const bool use_graph = graph_chunk > 0 && stream != nullptr;
     auto pairs_n = [&](uint64_t n) {
         enqueue_pairs_ens(c, stream, n);
         return 0;
     };
-    if (use_graph) {  // the ladder of bean_hip_svi_run's pair path, of {k_param_ens, k_guide_wave2_ens} pairs
-        const int n_rungs = top_rung(graph_chunk, 1, 10) + 1;
-        if ((int)c->graphs_ens.size() != n_rungs) {
-            destroy_graphs(c->graphs_ens);
-            if (build_ladder(c, c->graphs_ens, stream, n_rungs, 1, c->alleles_fresh, pairs_n)) {
-                destroy_graphs(c->graphs_ens);
-                return -1;
-            }
-        }
-    }
-    launch_set_step_ens(stream, c->members_dev, K, first_step, n_steps);
-    launch_param_ens<false, false, true>(c, stream, c->members_dev, K);
-    launch_guide_ens(c, stream, c->members_dev, K);
+    // the ladder of bean_hip_svi_run's pair path, of {k_param_ens, k_guide_wave2_ens} pairs
+    if (use_graph && ensure_ladder(c, a, stream, graph_chunk, pairs_n)) return -1;
+    launch_set_step_ens(stream, a.dev, K, first_step, n_steps);
+    launch_param_ens<false, false, true>(c, stream, a.dev, K);
+    launch_guide_ens(c, stream, a.dev, K);
     if (use_graph) {
-        if (replay_pairs(c, c->graphs_ens, stream, n_steps - 1, pairs_n)) return -1;
+        if (replay_pairs(c, a.ladder, stream, n_steps - 1, pairs_n)) return -1;
     } else {
         enqueue_pairs_ens(c, stream, n_steps - 1);
     }
-    launch_param_ens<true, true, false>(c, stream, c->members_dev, K);
-    launch_finalize_ens(stream, c->members_dev, K, first_step, n_steps);
+    launch_param_ens<true, true, false>(c, stream, a.dev, K);
+    launch_finalize_ens(stream, a.dev, K, first_step, n_steps);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -2115,8 +2087,7 @@ extern "C" int bean_hip_set_particles(bean_hip_ctx* c, int32_t n_particles) {
                     " members (bean_hip_set_members): particles inside member sets are not batched");
     if (c->particle_grad) (void)hipFree(c->particle_grad);
     c->particle_grad = nullptr;
-    if (c->particles_dev) (void)hipFree(c->particles_dev);
-    c->particles_dev = nullptr;
+    free_args(c->particles);
     c->n_particles = 1;
     c->particles_set = false;
     if (alloc_workspace_copies(c, n_particles)) return -1;
@@ -2124,10 +2095,9 @@ extern "C" int bean_hip_set_particles(bean_hip_ctx* c, int32_t n_particles) {
     for (int i = 0; i < 8; ++i) n_all += expected_bytes(c->shape, BEAN_BUF_P_MU_LOC + i) / 4;
     HIP_OK(hipMalloc((void**)&c->particle_grad, (size_t)n_all * (size_t)n_particles * sizeof(float)));
     HIP_OK(hipMemset(c->particle_grad, 0, (size_t)n_all * (size_t)n_particles * sizeof(float)));
-    HIP_OK(hipMalloc((void**)&c->particles_dev, (size_t)n_particles * sizeof(DevArgs)));
+    if (alloc_args(c->particles, n_particles)) return -1;
     c->n_particles = n_particles;
     c->particles_set = true;
-    c->particle_seeds.clear();
     c->prepared = false;
     drop_graph(c);
     return 0;
@@ -2165,19 +2135,9 @@ static DevArgs particle_args(const bean_hip_ctx* c, int q, uint64_t seed) {
     return m;
 }
 
-static int upload_particles(bean_hip_ctx* c, const uint64_t* seeds, hipStream_t stream) {
-    const int P = c->n_particles;
-    HIP_OK(hipStreamSynchronize(stream));  // no launch in flight reads the array while it changes
-    c->particles_host.resize((size_t)P);
-    for (int q = 0; q < P; ++q) c->particles_host[(size_t)q] = particle_args(c, q, seeds[q]);
-    HIP_OK(hipMemcpyAsync(c->particles_dev, c->particles_host.data(), (size_t)P * sizeof(DevArgs), hipMemcpyHostToDevice, stream));
-    HIP_OK(hipStreamSynchronize(stream));
-    return 0;
-}
-
 // n particle steps, four launches each; every one begins at the step counters the one before has left
 static void enqueue_particle_steps(bean_hip_ctx* c, hipStream_t stream, uint64_t n) {
-    const DevArgs* mem = c->particles_dev;
+    const DevArgs* mem = c->particles.dev;
     const int P = c->n_particles;
     const ParticleArrays a = particle_arrays(c);
     const unsigned blocks = (unsigned)((a.start[8] + 255) / 256);
@@ -2191,54 +2151,29 @@ static void enqueue_particle_steps(bean_hip_ctx* c, hipStream_t stream, uint64_t
 
 extern "C" int bean_hip_svi_run_particles(bean_hip_ctx* c, const uint64_t* seeds, int32_t n_seeds, uint64_t first_step,
                                           uint64_t n_steps, int32_t graph_chunk, void* stream_) {
-    if (!c) return fail("bean_hip_svi_run_particles: null handle");
-    if (!seeds) return fail("bean_hip_svi_run_particles: null seeds");
-    if (!c->particles_set) return fail("bean_hip_svi_run_particles: call bean_hip_set_particles first");
-    if (n_seeds != c->n_particles)
-        return fail("bean_hip_svi_run_particles: " + std::to_string(n_seeds) + " seeds for " + std::to_string(c->n_particles) +
-                    " particle(s) (bean_hip_set_particles)");
-    if (!ensemble_shape_ok(c))
-        return fail("bean_hip_svi_run_particles: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
-    if (per_step_noise(c->d) || c->d.pi_out)
-        return fail("bean_hip_svi_run_particles: injected or dumped noise belongs to single evaluations");
-    if (check_bound(c, true, true)) return -1;  // (the mean gradient goes to the bound gradient buffers)
-    const int go = begin_steps(c, "bean_hip_svi_run_particles", first_step, n_steps);
+    const int go = begin_copies(c, "bean_hip_svi_run_particles", true, seeds, n_seeds, first_step, n_steps);
     if (go <= 0) return go;
     hipStream_t stream = (hipStream_t)stream_;
     c->resume_ok = false;
     const int P = c->n_particles;
-    bool same = !c->particles_dirty && (int)c->particle_seeds.size() == P;
-    for (int q = 0; same && q < P; ++q) same = c->particle_seeds[(size_t)q] == seeds[q];
-    if (!same) {
-        // (the launches - captured ones too - hold the ADDRESS of this array: new seeds need no new graphs)
-        if (upload_particles(c, seeds, stream)) return -1;
-        c->particle_seeds.assign(seeds, seeds + P);
-        c->particles_dirty = false;
-    }
+    ArgSet& a = c->particles;
+    if (refresh_args(a, P, seeds, stream, [&](int q, uint64_t seed) { return particle_args(c, q, seed); })) return -1;
     const bool use_graph = graph_chunk > 0 && stream != nullptr;
     auto steps_n = [&](uint64_t n) {
         enqueue_particle_steps(c, stream, n);
         return 0;
     };
-    if (use_graph) {  // a ladder of its own, cut like the pair paths': graphs of 1, 2, 4, ... <= graph_chunk steps
-        const int n_rungs = top_rung(graph_chunk, 1, 10) + 1;
-        if ((int)c->graphs_part.size() != n_rungs) {
-            destroy_graphs(c->graphs_part);
-            if (build_ladder(c, c->graphs_part, stream, n_rungs, 1, c->alleles_fresh, steps_n)) {
-                destroy_graphs(c->graphs_part);
-                return -1;
-            }
-        }
-    }
-    launch_set_step_ens(stream, c->particles_dev, P, first_step, n_steps);
+    // a ladder of its own, of particle steps
+    if (use_graph && ensure_ladder(c, a, stream, graph_chunk, steps_n)) return -1;
+    launch_set_step_ens(stream, a.dev, P, first_step, n_steps);
     if (use_graph) {
-        if (replay_pairs(c, c->graphs_part, stream, n_steps, steps_n)) return -1;
+        if (replay_pairs(c, a.ladder, stream, n_steps, steps_n)) return -1;
     } else {
         enqueue_particle_steps(c, stream, n_steps);
     }
-    launch_finalize_ens(stream, c->particles_dev, P, first_step, n_steps);
+    launch_finalize_ens(stream, a.dev, P, first_step, n_steps);
     hipLaunchKernelGGL(k_particle_loss, dim3((unsigned)((n_steps + 255) / 256)), dim3(256), 0, stream,
-                       (const DevArgs*)c->particles_dev, P, c->d.loss_hist, (unsigned long long)first_step,
+                       (const DevArgs*)a.dev, P, c->d.loss_hist, (unsigned long long)first_step,
                        (unsigned long long)n_steps);
     HIP_OK(hipGetLastError());
     return 0;

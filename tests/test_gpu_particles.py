@@ -193,6 +193,51 @@ def test_windows_are_one_call_and_the_slot_behind_stays():
     eng.close()
 
 
+def test_particles_members_and_single_fit_share_one_handle():
+    """The particles' arguments and the members' are both live on a particle handle: run_ensemble takes it as an ensemble
+    of one, run as the single fit.  Five calls on ONE engine, each from step 0 and from the initial parameters and
+    moments, each a ladder of its own (graph_chunk 4, 23 steps): every call gives the bits a fresh engine gives that
+    makes that call alone, and the ensemble of one and the run are the single fit of their seed."""
+    from bean_amd import engine
+
+    data = make_sorting_variant_screen(130, 2, guides_per_target=7, seed=3).to(DEV)
+    n, chunk = 23, 4
+    calls = [
+        ("particles", None, lambda e: e.run_particles(n, SEED, graph_chunk=chunk, first_step=0)),
+        ("ensemble of one", SEED, lambda e: e.run_ensemble(n, [SEED], graph_chunk=chunk, first_step=0)),
+        ("run", SEED, lambda e: e.run(n, seed=SEED, graph_chunk=chunk, first_step=0)),
+        ("particles again", None, lambda e: e.run_particles(n, SEED, graph_chunk=chunk, first_step=0)),
+        ("ensemble of one, another seed", 7, lambda e: e.run_ensemble(n, [7], graph_chunk=chunk, first_step=0)),
+    ]
+
+    def alone(call, **kw):
+        eng = engine.HipSVI("MixtureNormal", data, num_steps=STEPS, **kw)
+        call(eng)
+        out = _state(eng, 0, n, grads=False)
+        eng.close()
+        assert all(torch.isfinite(v).all() for v in out.values())
+        return out
+
+    fresh = [alone(call, n_particles=3) for _, _, call in calls]
+    single = {seed: alone(lambda e, s=seed: e.run(n, seed=s, graph_chunk=chunk, first_step=0)) for seed in (SEED, 7)}
+
+    eng = engine.HipSVI("MixtureNormal", data, num_steps=STEPS, n_particles=3)
+    assert eng._particles_native
+    start = _state(eng, 0, 0, grads=False)
+    got = []
+    for what, seed, call in calls:
+        _load(eng, start)
+        call(eng)
+        got.append(_state(eng, 0, n, grads=False))
+        _assert_same(got[-1], fresh[len(got) - 1], f"{what}: on the shared handle against a fresh engine")
+        if seed is not None:
+            _assert_same(got[-1], single[seed], f"{what}: against the single fit of seed {seed}")
+    eng.close()
+    _assert_same(got[3], got[0], "the particles after the members' calls")
+    assert not torch.equal(got[4]["p.mu_loc"], got[1]["p.mu_loc"]) and not torch.equal(got[4]["loss"], got[1]["loss"])
+    assert not torch.equal(got[0]["p.mu_loc"], got[2]["p.mu_loc"])  # (three particles are not the single fit)
+
+
 # ------------------------------------------------------------------ 4. started late in the schedule
 def test_late_first_step_equals_the_defining_loop():
     """6 steps from first_step = 1500 of a 2000-step schedule, from the state a 5-step run leaves: the step size of
