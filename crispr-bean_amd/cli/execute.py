@@ -22,6 +22,27 @@ def _non_negative_int(text: str) -> int:
     return value
 
 
+def parse_depths(text):
+    """``--design-depths``: a comma-separated list of positive floats, in the order given (``argparse`` type: a bad
+    entry, a factor that is not > 0 and a factor given twice are refused with their sentence)."""
+    import math
+
+    entries = [e.strip() for e in str(text).split(",")]
+    out = []
+    for entry in entries:
+        try:
+            f = float(entry)
+        except (TypeError, ValueError):
+            raise argparse.ArgumentTypeError(f"{entry!r} is not a number: a comma-separated list of depth factors such as "
+                                             "0.25,0.5,2,4 is expected") from None
+        if not (math.isfinite(f) and f > 0):
+            raise argparse.ArgumentTypeError(f"a depth factor must be a finite number > 0, got {entry}")
+        if f in out:
+            raise argparse.ArgumentTypeError(f"depth factor {f:g} is given more than once")
+        out.append(f)
+    return out
+
+
 def get_parser():
     parser = argparse.ArgumentParser(prog="bean")
     sub = parser.add_subparsers(dest="subcommand", help="bean subcommands")
@@ -87,6 +108,21 @@ def get_parser():
                           "--jackknife-* flag, --num-particles > 1 or --load-existing.  Default 0: off.")
     own.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=101,
                      help="Seed of the simulated screens of --bootstrap (default 101).")
+    own.add_argument("--design-depths", dest="design_depths", type=parse_depths, default=None, metavar="F,F,...",
+                     help="Depth study: after the fit of the screen, draw --design-screens screens from the fitted model "
+                          "on the GPU at each of these read depths - a comma-separated list of factors > 0 such as "
+                          "0.25,0.5,2,4; at factor f every (replicate, guide) draws round(f x its observed reads), "
+                          "everything else (masks, size factors, a0, pi_a0) as observed: the same cells, other read "
+                          "counts - refit each with the same seed and report how the spread of mu over the refits "
+                          "changes with the depth: one row per depth in bean_design.<model>.csv (depth, n_screens, "
+                          "median_total, median_mu_design_se, se_ratio against depth 1, recovery of the screen's hits, "
+                          "n_hits) and the columns mu_design_se_x<f> in the element table, on the scale of the column "
+                          "mu.  Depth 1 is added where absent.  Sorting variant screens only; not combined with "
+                          "--bootstrap, --n-seeds > 1, any --jackknife-* flag, --num-particles > 1 or --load-existing.")
+    own.add_argument("--design-screens", dest="design_screens", type=_positive_int, default=8, metavar="K",
+                     help="Screens drawn and refitted per depth of --design-depths (default 8, at least 2).")
+    own.add_argument("--design-seed", dest="design_seed", type=int, default=101,
+                     help="Seed of the simulated screens of --design-depths (default 101).")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))

@@ -64,7 +64,7 @@ _SAME_SEED = "{flag} fits every member with the same seed and does not combine w
 _TWO_RUNS = "{flag} and {other} are two runs: they do not combine in one."
 _NEEDS_FITS = "{{flag}} needs the leave-one-{}out fits and does not combine with --load-existing."
 _SAMPLE_RULES = (("jackknife_replicates", _TWO_RUNS), ("jackknife_guides", _TWO_RUNS), ("n_seeds", _SAME_SEED),
-                 ("load_existing", _NEEDS_FITS.format("")), ("bootstrap", _TWO_RUNS))
+                 ("load_existing", _NEEDS_FITS.format("")), ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))
 _BOOTSTRAP_FAMILY = ("{{flag}} simulates the counts of the sorting variant models (Normal, MixtureNormal) and is not "
                      "available for {}.")
 # the flags that ask for a member set, in the order their refusals are reported:
@@ -72,11 +72,11 @@ _BOOTSTRAP_FAMILY = ("{{flag}} simulates the counts of the sorting variant model
 MEMBER_FLAGS = (
     ("jackknife_replicates", "replicates", (("n_seeds", _SAME_SEED),
                                             ("load_existing", _NEEDS_FITS.format("replicate-")),
-                                            ("bootstrap", _TWO_RUNS))),
+                                            ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))),
     ("jackknife_guides", "guides", (("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS),
                                     ("load_existing", _NEEDS_FITS.format("guide-")),
                                     ("tiling", "{flag} needs targets that own their guides and does not combine with tiling."),
-                                    ("bootstrap", _TWO_RUNS))),
+                                    ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))),
     ("jackknife_samples", "sample", (("jackknife_conditions", _TWO_RUNS),) + _SAMPLE_RULES),
     ("jackknife_conditions", "condition", (("jackknife_samples", _TWO_RUNS),) + _SAMPLE_RULES),
     ("bootstrap", "bootstrap", (("bootstrap_one", "{flag} needs at least 2 screens."),
@@ -86,11 +86,22 @@ MEMBER_FLAGS = (
                                 ("jackknife_guides", _TWO_RUNS), ("jackknife_samples", _TWO_RUNS),
                                 ("jackknife_conditions", _TWO_RUNS),
                                 ("load_existing", "{flag} needs the refits of its simulated screens and does not combine "
-                                                  "with --load-existing."))),
+                                                  "with --load-existing."),
+                                ("design_depths", _TWO_RUNS))),
+    ("design_depths", "design", (("design_one", "{flag} needs at least 2 screens per depth (--design-screens)."),
+                                 ("tiling", _BOOTSTRAP_FAMILY.format("tiling screens (MultiMixtureNormal)")),
+                                 ("survival", _BOOTSTRAP_FAMILY.format("survival screens")),
+                                 ("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS),
+                                 ("jackknife_guides", _TWO_RUNS), ("jackknife_samples", _TWO_RUNS),
+                                 ("jackknife_conditions", _TWO_RUNS),
+                                 ("load_existing", "{flag} needs the refits of its simulated screens and does not combine "
+                                                   "with --load-existing."),
+                                 ("bootstrap", _TWO_RUNS))),
 )
 _IS_SET = {"n_seeds": lambda args: int(getattr(args, "n_seeds", 1) or 1) > 1,
            "bootstrap": lambda args: int(getattr(args, "bootstrap", 0) or 0) > 0,
            "bootstrap_one": lambda args: int(getattr(args, "bootstrap", 0) or 0) == 1,
+           "design_one": lambda args: int(getattr(args, "design_screens", 8) or 0) < 2,
            "survival": lambda args: getattr(args, "selection", None) == "survival",
            "tiling": lambda args: getattr(args, "library_design", None) == "tiling",
            "guides_max": lambda args: int(getattr(args, "jackknife_guides_max", 63)) > 63}
@@ -101,8 +112,8 @@ def _refuse(message):
 
 
 def member_mode(args, fail=_refuse, only=None, parser_rules=None):
-    """The member set this run fits next to the screen: None, "seeds", "replicates", "guides", "sample", "condition" or
-    "bootstrap".
+    """The member set this run fits next to the screen: None, "seeds", "replicates", "guides", "sample", "condition",
+    "bootstrap" or "design".
     A combination that is refused goes to ``fail(sentence)`` (the parser's ``error``; here, raising ``ValueError``).
     ``only``: the flags whose rules are looked at (default: all); ``parser_rules``: further rules per flag, after its own."""
     is_set = lambda attr: _IS_SET.get(attr, lambda a: bool(getattr(a, attr, False)))(args)  # noqa: E731
@@ -236,11 +247,21 @@ def _bootstrap_members(fit, ndata, args, guide_names):
             {"bootstrap": jk.bootstrap_summary(full, boots)})
 
 
+def _design_members(fit, ndata, args, guide_names):
+    depths = model_run.design_depths(args.design_depths)
+    full, fits = fit(model_run.run_inference_design, depths=depths, n_screens=int(getattr(args, "design_screens", 8)),
+                     design_seed=int(getattr(args, "design_seed", model_run.SEED)))
+    heads = [{"depth": f, "screen": j} for f in depths for j in range(len(fits[0]))]
+    return (full, _entries(heads, [r for row in fits for r in row]),
+            {"design": jk.design_summary(full, fits, depths, data=ndata)})
+
+
 # mode -> (what fits its members and returns (the fit the tables come from, the members' entry of the --save-raw
 #          pickle, write_result_table's keywords for their summary), the key of that entry)
 MEMBER_RUNS = {"seeds": (_seed_members, "ensemble"), "replicates": (_replicate_members, "jackknife"),
                "guides": (_guide_members, "guide_jackknife"), "sample": (_sample_members, "sample_jackknife"),
-               "condition": (_sample_members, "sample_jackknife"), "bootstrap": (_bootstrap_members, "bootstrap")}
+               "condition": (_sample_members, "sample_jackknife"), "bootstrap": (_bootstrap_members, "bootstrap"),
+               "design": (_design_members, "design")}
 
 
 def main(args, return_data=False):

@@ -1,5 +1,6 @@
 // k_simulate_wave2: replicate counts of the variant sorting families, drawn on the device (posterior predictive check);
-// k_simulate_members (at the end): K such screens in one launch, the member on blockIdx.y (parametric bootstrap).
+// k_simulate_members (at the end): K such screens in one launch, the member on blockIdx.y (parametric bootstrap);
+// k_simulate_design (after it): D x K screens in one launch, K draws at each of D read depths (depth study).
 //
 // For one draw d of the latent sites - the draw bean_hip_elbo_grad(seed, step = d) evaluates, prepared by the same
 // k_set_step + PREP k_param launches - every (replicate, guide) forms the Dirichlet-Multinomial concentrations of its
@@ -52,13 +53,22 @@ __host__ __device__ inline size_t simulate_wave2_lds(int B) {
     return ((size_t)4 * B + (size_t)B * 64) * sizeof(double) + (size_t)B * 64 * sizeof(float);
 }
 
-// The per-lane body of both simulators: the workgroup blockIdx.x of one screen, drawn as draw `ctr.step` into the
+// The total a pair draws at read depth `depth`: floor(depth * n_obs + 0.5) in float64, at most kSimCatWords - 1 (the
+// categorical window of a (likelihood, draw), and the largest count a float32 plane holds exactly next to its
+// neighbours).  The host refuses depths that would reach the clamp (HipSVI.simulate_design); the kernel holds it anyway.
+__device__ __forceinline__ long design_total(const double n_obs, const double depth) {
+    const double t = floor(fma(depth, n_obs, 0.5));
+    return (long)fmin(t, (double)(kSimCatWords - 1ull));
+}
+
+// The per-lane body of the simulators: the workgroup blockIdx.x of one screen, drawn as draw `ctr.step` into the
 // planes of `s`.  `dump_pi` gates the BEAN_FLAG_DUMP_PI write (one screen has one pi_out).  One function, so that a plane
 // of k_simulate_members is bit for bit the screen k_simulate_wave2 leaves for the same draw (as guide_pair_math is the
-// one body of the guide kernels).
-template <int FAM, bool ACC>
+// one body of the guide kernels).  DEPTH (k_simulate_design alone): the pair draws design_total(n_obs, depth) reads
+// instead of n_obs; nothing else of the draw - pi, concentrations, gammas, which word is which read - looks at it.
+template <int FAM, bool ACC, bool DEPTH = false>
 __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimArgs& s, const StepCtr& ctr, double* sim_lds,
-                                                   const bool dump_pi) {
+                                                   const bool dump_pi, const double depth = 1.0) {
     constexpr bool MIX = FAM == kMixture;
     const int wg = blockIdx.x;
     const int kk = wg >> 3;
@@ -214,7 +224,7 @@ __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimAr
             xs[b * 64] = 0.f;
         }
         // ---- x_rep ~ Multinomial(n, p): four categorical draws per Philox block
-        const long n_i = (long)n;
+        const long n_i = DEPTH ? design_total(n, depth) : (long)n;
         const long n_blk = (n_i + 3) >> 2;
         const unsigned long long cat_sub = ((unsigned long long)kSiteSimCat << 48) + sub;
         const unsigned long long cat_off = dl * kSimCatWords;
@@ -274,6 +284,43 @@ void k_simulate_members(DevArgs c, SimArgs s) {
     sm.xbc_out = s.xbc_out ? s.xbc_out + plane : nullptr;
     sm.alpha_out = nullptr;
     simulate_pair_body<FAM, ACC>(c, sm, ctr, sim_lds, member == 0);
+}
+
+// k_simulate_design: K replicate screens at each of D read depths in one launch (a depth study's screens).  gridDim.x
+// as k_simulate_members, gridDim.y = D * K; member m = blockIdx.y = i * K + j is depth i, draw j, and writes plane (i, j)
+// of x_out / xbc_out, (D, K, R, B, G) member-major.  The depth factors travel by value in the argument struct (D <= 64
+// doubles, read through scalar loads of the kernel arguments): no caller-owned device pointer, no copy to wait for.
+// Member (i, j) is member j of k_simulate_members in everything but its totals: the shared Normal sites, pi_in and
+// DUMP_PI (member 0 alone) as there, draw ctrB->step + j for the pi, gamma and categorical sites AT EVERY DEPTH (common
+// random numbers across depths), and design_total(n_obs, depth[i]) reads per pair.  From the counter layout:
+//   (a) depth[i] == 1: plane (i, j) is bit for bit plane j of k_simulate_members (fma(1, n, 0.5) floors to n);
+//   (b) depth[a] <= depth[b]: plane (a, j) <= plane (b, j) elementwise - categorical draw t is word t of the pair's
+//       window and p does not depend on the total, so the deeper screen is the shallower one plus further reads;
+//   (c) every (replicate, guide) of plane (i, j) sums to design_total(n_obs, depth[i]) exactly.
+// COST: as k_simulate_members, with the largest n_i of a 64-guide tile in place of its largest n_obs - a wave of depth 4
+// runs four times as long as its depth-1 twin.  LDS, scratch, atomics and stores as k_simulate_wave2.
+struct DesignArgs {
+    int K;                               // draws per depth
+    int D;                               // depths
+    double depth[kEnsembleMaxMembers];   // [D]
+};
+static_assert(sizeof(DevArgs) + sizeof(SimArgs) + sizeof(DesignArgs) <= 4096, "the kernel arguments fit their segment");
+
+template <int FAM, bool ACC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
+void k_simulate_design(DevArgs c, SimArgs s, DesignArgs dz) {
+    extern __shared__ double sim_lds[];
+    StepCtr ctr = *c.ctrB;
+    const unsigned member = blockIdx.y;
+    const unsigned i = member / (unsigned)dz.K, j = member - i * (unsigned)dz.K;
+    if (i >= (unsigned)dz.D) return;
+    ctr.step += (unsigned long long)j;
+    const size_t plane = (size_t)member * (size_t)c.R * (size_t)c.B * (size_t)c.G;
+    SimArgs sm;
+    sm.x_out = s.x_out + plane;
+    sm.xbc_out = s.xbc_out ? s.xbc_out + plane : nullptr;
+    sm.alpha_out = nullptr;
+    simulate_pair_body<FAM, ACC, true>(c, sm, ctr, sim_lds, member == 0, dz.depth[i]);
 }
 
 }  // namespace bean

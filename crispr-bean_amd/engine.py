@@ -870,6 +870,49 @@ class HipSVI:
             out["X_bcmatch"] = xbc
         return out
 
+    def simulate_design(self, first_draw: int, n_draws: int, depths, seed: int = 101) -> Dict[str, torch.Tensor]:
+        """``n_draws`` replicate screens at each of the read depths ``depths`` in one launch
+        (``bean_hip_simulate_design``): ``X`` (D, K, R, B, G) float32 and, where the fit uses the barcode-matched counts,
+        ``X_bcmatch`` - device tensors, member-major over (depth, draw).  Plane (i, j) is plane j of
+        ``simulate_members(first_draw, n_draws)`` drawn with ``floor(depths[i] * n_obs + 0.5)`` reads per (replicate,
+        guide) instead of ``n_obs``: the same pi, Dirichlet and categorical streams at every depth, so depth 1 is that
+        plane bit for bit and a deeper screen is the shallower one plus further reads.  A depth under which the largest
+        observed total would reach 2^24 reads (the categorical window, and the limit of exact float32 counts) is a
+        ``ValueError`` before any launch.  Leaves the fit alone as ``simulate`` does; the next ``run(resume=True)`` is a
+        plain run."""
+        if not self.predictive_supported:
+            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
+                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        K = int(n_draws)
+        fs = [float(f) for f in depths]
+        D = len(fs)
+        finite = [f for f in fs if f == f and f != float("inf")]
+        if finite:
+            if getattr(self, "_largest_total", None) is None:  # read back once: the bound counts do not change
+                keys = ("X", "X_BC") if self.use_bcmatch else ("X",)
+                self._largest_total = max(float(self._keep[k].double().sum(1).max()) for k in keys)
+            most = self._largest_total
+            if max(finite) * most >= float(1 << 24):
+                raise ValueError(f"simulate_design: depth {max(finite):g} times the largest observed total {most:.0f} is "
+                                 f"{max(finite) * most:.0f} reads, not below 2^24 = {1 << 24} (the categorical window of "
+                                 "a pair, and the limit of exact float32 counts)")
+        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
+        shape = (D, max(K, 0), R, B, G)
+        x = torch.empty(shape, dtype=torch.float32, device=self.device)
+        xbc = torch.empty(shape, dtype=torch.float32, device=self.device) if self.use_bcmatch else None
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
+        arr = (ctypes.c_double * max(D, 1))(*fs)
+        with self._on_stream():
+            self._check(self.lib.bean_hip_simulate_design(self._h, int(seed), int(first_draw), K, arr, D, ptr(x), nb(x),
+                                                          ptr(xbc), nb(xbc), self._sptr()), "simulate_design")
+        self.invalidate_resume()
+        out = {"X": x}
+        if xbc is not None:
+            out["X_bcmatch"] = xbc
+        return out
+
     def run_ensemble(self, n_steps: int, seeds, graph_chunk: int = 50, first_step: Optional[int] = None):
         """Enqueue ``n_steps`` SVI steps of all ``n_members`` fits, member k with ``seeds[k]`` (no host
         synchronisation).  Member k is, bit for bit, a single engine's ``run(n_steps, seed=seeds[k])``;

@@ -34,6 +34,13 @@ K screens drawn from the fitted model on the device (``HipSVI.simulate_members``
 ``bootstrap_plan``, ``bootstrap_summary``.  The members differ in their counts alone; everything derived from the observed
 screen is conditioned on.
 
+Depth study: would sequencing deeper (or shallower) change the spread of ``mu`` (``run_inference_design``, ``bean run
+--design-depths``).
+
+The bootstrap's screens drawn at other read depths (``HipSVI.simulate_design``): every (replicate, guide) draws
+``floor(f * n_obs + 0.5)`` reads, everything else as observed - the same cells, other read counts: ``design_plan``,
+``design_summary``.
+
 Each of these, and the seed ensemble, is K fits of one screen: a ``MemberPlan``, fitted by ``model/run.py::_fit_plan``.
 
 Pure torch: no GPU involved in this file.
@@ -41,7 +48,7 @@ Pure torch: no GPU involved in this file.
 from __future__ import annotations
 
 import copy
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -468,3 +475,99 @@ def bootstrap_summary(full, boots) -> Dict[str, object]:
         raise ValueError(f"bootstrap_summary needs at least two bootstrap fits, got {n}")
     m = torch.stack([_mu_loc(r) for r in boots])
     return {"mu_boot_se": m.std(0, unbiased=True), "mu_boot_bias": m.mean(0) - _mu_loc(full), "n_boot": n}
+
+
+# ---------------------------------------------------------------- depth study
+def depth_text(f) -> str:
+    """A depth factor as labels, tags and column names show it: ``{f:g}``."""
+    return f"{float(f):g}"
+
+
+def design_plan(data, seed, depths, x, x_bcmatch=None) -> MemberPlan:
+    """A depth study: member 0 is the screen, member ``1 + i * K + j`` a ``copy.copy(data)`` whose ``X_masked`` is plane
+    ``(i, j)`` of ``x`` (D, K, R, B, G) - depth ``depths[i]``, draw j, the screens ``HipSVI.simulate_design`` drew from the
+    fitted model - and, where ``x_bcmatch`` is given, whose ``X_bcmatch_masked`` is plane ``(i, j)`` of it.
+
+    Conditioned on, as in ``bootstrap_plan``: both masks, the size factors, ``a0`` / ``a0_bcmatch``, ``pi_a0`` and the
+    control allele counts are the observed screen's, shared with ``data`` - the same cells, other read counts.  Every
+    member gets ``seed``; an engine run holds the screen and at most 63 of the screens.  ``data`` is not modified."""
+    seed = int(seed)
+    depths = [float(f) for f in depths]
+    if x.dim() != 5 or int(x.shape[0]) != len(depths):
+        raise ValueError(f"x has shape {tuple(x.shape)}: (D, K, R, B, G) with D = {len(depths)} depths is needed")
+    if x_bcmatch is not None and tuple(x_bcmatch.shape) != tuple(x.shape):
+        raise ValueError(f"x_bcmatch has shape {tuple(x_bcmatch.shape)}, x {tuple(x.shape)}")
+    K = int(x.shape[1])
+
+    def screen(data, ij):
+        i, j = ij
+        out = copy.copy(data)
+        out.X_masked = x[i, j]
+        if x_bcmatch is not None:
+            out.X_bcmatch_masked = x_bcmatch[i, j]
+        return out
+
+    items = [(i, j) for i in range(len(depths)) for j in range(K)]
+    plan = _leave_one_out_plan(data, seed, items, label=lambda ij: f"depth {depth_text(depths[ij[0]])} screen {ij[1]}",
+                               tag=lambda ij: f"depth{depth_text(depths[ij[0]])}_{ij[1]}", key="depth",
+                               value=lambda ij: depths[ij[0]], leave=screen, differ_in=("masks", "counts"),
+                               per_run=MAX_GUIDE_POSITIONS, label_halts=True)
+    extra = [{"depth": e["depth"], "screen": None if k == 0 else items[k - 1][1], "seed": seed}
+             for k, e in enumerate(plan.dump_extra)]
+    return replace(plan, dump_extra=extra)
+
+
+def design_totals(n_obs, depth):
+    """``floor(depth * n_obs + 0.5)`` in float64: the reads a pair of ``n_obs`` observed reads draws at ``depth``."""
+    return torch.floor(torch.as_tensor(n_obs, dtype=torch.float64) * float(depth) + 0.5)
+
+
+def design_summary(full, fits, depths, z_hit: float = 1.96, data=None) -> Dict[str, object]:
+    """Depth-study summary (float64).  ``fits[i][j]`` is the refit of draw j at depth ``depths[i]``, ``m_ij`` / ``s_ij``
+    its ``mu_loc`` / ``mu_scale``; ``depths`` holds the baseline depth 1.
+
+    * ``mu_design_se`` (D, T): the standard deviation of ``m_ij`` over j, unbiased (K - 1);
+    * ``mu_design_sd`` (D, T): the mean of ``s_ij`` over j;
+    * ``se_ratio`` (D,): the median over targets of ``mu_design_se[i] / mu_design_se[depth 1]``; targets whose
+      denominator is zero or not finite are left out, ``n_left_out`` counts them (all left out: NaN);
+    * ``hits``: the targets (sorted indices) with ``|mu_loc_full| / mu_scale_full >= z_hit``; ``n_hits``;
+    * ``recovery`` (D,): the share of (hit, j) with ``sign(m_ij) == sign(mu_loc_full)`` and ``|m_ij| / s_ij >= z_hit``;
+      NaN where there is no hit;
+    * ``n_screens`` = K, ``depths``, and ``median_total`` (D,): the median of ``floor(depth * n_obs + 0.5)`` over the
+      (replicate, guide) pairs of ``data`` that ``repguide_mask`` keeps (NaN without ``data``).
+
+    Fewer than two screens at a depth, depths and fits of different lengths, or no depth 1 are a ``ValueError``."""
+    depths = [float(f) for f in depths]
+    D = len(depths)
+    if D < 1 or D != len(fits):
+        raise ValueError(f"design_summary needs one list of fits per depth, got {len(fits)} for {D} depths")
+    K = len(fits[0])
+    if K < 2 or any(len(row) != K for row in fits):
+        raise ValueError(f"design_summary needs at least two screens at every depth, the same number at each, got "
+                         f"{[len(row) for row in fits]}")
+    if 1.0 not in depths:
+        raise ValueError(f"design_summary needs depth 1, the baseline of every ratio, among {depths}")
+    base = depths.index(1.0)
+    m = torch.stack([torch.stack([_mu_loc(r).reshape(-1) for r in row]) for row in fits])  # (D, K, T)
+    s = torch.stack([torch.stack([_param(r, "mu_scale").reshape(-1) for r in row]) for row in fits])
+    centre, scale = _mu_loc(full).reshape(-1), _param(full, "mu_scale").reshape(-1)
+    se = m.std(1, unbiased=True)
+    den = se[base]
+    ok = torch.isfinite(den) & (den != 0)
+    nan = float("nan")
+    ratio = torch.stack([torch.quantile(se[i][ok] / den[ok], 0.5) if bool(ok.any()) else torch.tensor(nan, dtype=torch.float64)
+                         for i in range(D)])
+    hit = (centre.abs() / scale) >= float(z_hit)
+    found = (torch.sign(m) == torch.sign(centre)) & ((m.abs() / s) >= float(z_hit))  # (D, K, T)
+    n_hits = int(hit.sum())
+    recovery = (found[:, :, hit].to(torch.float64).mean((1, 2)) if n_hits
+                else torch.full((D,), nan, dtype=torch.float64))
+    median_total = torch.full((D,), nan, dtype=torch.float64)
+    if data is not None:
+        n_obs = data.X_masked.detach().cpu().to(torch.float64).sum(1)  # (R, G)
+        kept = n_obs[data.repguide_mask.detach().cpu() != 0]
+        if kept.numel():
+            median_total = torch.stack([torch.quantile(design_totals(kept, f), 0.5) for f in depths])
+    return {"mu_design_se": se, "mu_design_sd": s.mean(1), "se_ratio": ratio, "n_left_out": int((~ok).sum()),
+            "hits": torch.nonzero(hit).reshape(-1).tolist(), "n_hits": n_hits, "recovery": recovery, "n_screens": K,
+            "median_total": median_total, "depths": depths}

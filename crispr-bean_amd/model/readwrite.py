@@ -188,6 +188,7 @@ def write_result_table(
     guide_jackknife: Optional[dict] = None,
     sample_jackknife: Optional[dict] = None,
     bootstrap: Optional[dict] = None,
+    design: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -217,7 +218,13 @@ def write_result_table(
 
     ``bootstrap`` (a parametric bootstrap, ``model/jackknife.py::bootstrap_summary``): the element table gets exactly
     the columns ``mu_boot_se``, ``mu_boot_bias`` and ``n_boot`` (on the scale of ``mu``, not rescaled); every other
-    column and the sgRNA table are those of the run without it."""
+    column and the sgRNA table are those of the run without it.
+
+    ``design`` (a depth study, ``model/jackknife.py::design_summary``): the element table gets exactly the columns
+    ``mu_design_se_x{f:g}``, one per depth in the summary's order (on the scale of ``mu``, not rescaled), and the
+    summary's table - one row per depth: ``depth, n_screens, median_total, median_mu_design_se, se_ratio, recovery,
+    n_hits`` - is written next to the element table as ``bean_design.<model_label><suffix>.csv``, also with
+    ``return_result``.  With ``None`` every file is byte for byte what it was and no further one is written."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -244,6 +251,13 @@ def write_result_table(
                              "mu_sjk_max_shift_sample", "n_sjk")
     if bootstrap is not None:
         _add_summary_columns(element, bootstrap, "the bootstrap summary", ("mu_boot_se", "mu_boot_bias"), None, "n_boot")
+    if design is not None:
+        spread = np.asarray(design["mu_design_se"], dtype=np.float64)
+        if spread.ndim != 2 or spread.shape != (len(design["depths"]), len(element)):
+            raise ValueError(f"the depth study summary has shape {spread.shape} for {len(design['depths'])} depths and "
+                             f"{len(element)} targets")
+        for f, column in zip(design["depths"], spread):
+            element[f"mu_design_se_x{float(f):g}"] = column
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always
@@ -259,6 +273,12 @@ def write_result_table(
     if sample_jackknife is not None:
         pd.DataFrame(sample_jackknife["influence"]).to_csv(f"{prefix}bean_sample_influence.{model_label}{suffix}.csv",
                                                            index=False)
+    if design is not None:
+        pd.DataFrame({"depth": [float(f) for f in design["depths"]], "n_screens": int(design["n_screens"]),
+                      "median_total": _flat(design["median_total"]),
+                      "median_mu_design_se": np.median(spread, axis=1) if spread.shape[1] else np.full(len(spread), np.nan),
+                      "se_ratio": _flat(design["se_ratio"]), "recovery": _flat(design["recovery"]),
+                      "n_hits": int(design["n_hits"])}).to_csv(f"{prefix}bean_design.{model_label}{suffix}.csv", index=False)
     if return_result:
         return element
     element.to_csv(f"{prefix}bean_element_result.{model_label}{suffix}.csv")

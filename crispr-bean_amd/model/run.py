@@ -18,8 +18,8 @@ import torch
 
 from ..engine import HipSVI
 from . import model as sorting_model
-from .jackknife import (bootstrap_plan, guide_plan, particle_seeds, replicate_plan, sample_plan, seed_plan,  # noqa: F401
-                        stack_counts, stack_masks)
+from .jackknife import (bootstrap_plan, design_plan, guide_plan, particle_seeds, replicate_plan, sample_plan,  # noqa: F401
+                        seed_plan, stack_counts, stack_masks)
 from .model import ModelSpec
 
 logger = logging.getLogger(__name__)
@@ -554,6 +554,105 @@ def run_inference_bootstrap(model, guide, data, n_boot: int = 32, seed: int = SE
     plan = dataclasses.replace(plan, per_run=per_run)
     results = _fit_plan(model, guide, data, plan, common, report_every, verbose)
     return results[0], results[1:]
+
+
+def design_depths(depths):
+    """The depth factors of a depth study as floats, depth 1 - the baseline of every ratio - put in front where it is
+    absent.  An empty list, a factor that is not a finite number > 0 and a factor given twice are each a ``ValueError``."""
+    import math
+
+    out = [float(f) for f in depths]
+    if not out:
+        raise ValueError("a depth study needs at least one depth factor")
+    for f in out:
+        if not (math.isfinite(f) and f > 0):
+            raise ValueError(f"a depth factor must be a finite number > 0, got {f:g}")
+    twice = sorted({f for f in out if out.count(f) > 1})
+    if twice:
+        raise ValueError(f"depth factor {twice[0]:g} is given more than once")
+    return out if 1.0 in out else [1.0] + out
+
+
+def design_screens(eng: HipSVI, depths, n_screens: int, design_seed: int = SEED):
+    """``(X (D, K, R, B, G), X_bcmatch or None)``, device tensors: screen (i, j) is depth ``depths[i]``, draw j of
+    ``eng.simulate_design(..., seed=design_seed)`` whatever the batching - calls of at most ``MAX_MEMBERS`` screens,
+    chunked over the depths (``D_c * K <= MAX_MEMBERS``) and, where ``K > MAX_MEMBERS``, over j with ``first_draw``
+    advancing as ``bootstrap_screens`` advances it."""
+    from .._lib import MAX_MEMBERS
+
+    depths = [float(f) for f in depths]
+    K = int(n_screens)
+    rows_x, rows_bc = [], []
+    for j0 in range(0, K, MAX_MEMBERS):
+        k = min(MAX_MEMBERS, K - j0)
+        per_call = max(MAX_MEMBERS // k, 1)
+        xs, xbcs = [], []
+        for i0 in range(0, len(depths), per_call):
+            sim = eng.simulate_design(j0, k, depths[i0:i0 + per_call], seed=design_seed)
+            xs.append(sim["X"])
+            if "X_bcmatch" in sim:
+                xbcs.append(sim["X_bcmatch"])
+        rows_x.append(torch.cat(xs))
+        if xbcs:
+            rows_bc.append(torch.cat(xbcs))
+    return torch.cat(rows_x, 1), (torch.cat(rows_bc, 1) if rows_bc else None)
+
+
+def run_inference_design(model, guide, data, depths, n_screens: int = 8, seed: int = SEED, design_seed: int = SEED,
+                         initial_lr=0.01, gamma=0.1, num_steps=2000, report_every: int = 100, verbose: bool = True,
+                         max_per_run: int = 63):
+    """Depth study: fit the screen, draw ``n_screens`` screens from the fitted model at each read depth of ``depths`` on
+    the device, and refit every one of them with the same ``seed`` (``model/jackknife.py::design_plan``) - would
+    sequencing deeper tighten ``mu``, or is its spread set by the dispersion ``a0`` and not by the read count.
+
+    The screens are the parametric bootstrap's (``bootstrap_engine``: the plug-in, zero noise in every Normal site) with
+    one change: at depth f every (replicate, guide) draws ``floor(f * n_obs + 0.5)`` reads.  Screen (i, j) uses the pi,
+    Dirichlet and categorical streams of draw j of ``design_seed`` at every depth (common random numbers across depths).
+    Masks, size factors, ``a0``, ``pi_a0`` and the control allele counts are the observed screen's: the same cells, other
+    read counts.  Depth 1 is added in front of ``depths`` where absent (``design_depths``).
+
+    Returns ``(full, fits)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns, ``fits[i][j]`` exactly
+    what it returns for the screen with the counts of depth i, draw j - bit for bit; ``fits`` follows
+    ``design_depths(depths)``, and its depth-1 row is the ``boots`` of ``run_inference_bootstrap(n_boot=n_screens,
+    boot_seed=design_seed)``.  The refits are members of one engine next to the screen, at most ``max_per_run``
+    (1 ... 63) per engine run, where the batched kernels take the shape; else one after the other (``_fit_plan``).
+    Raises ``PredictiveUnsupported`` - the message names the family - as ``run_inference_bootstrap`` does;
+    ``n_screens < 2``, no depth, a depth given twice and a depth that is not > 0 are each a ``ValueError``.  A halt's
+    message and dump file (``tmp_result.depth<f>_<j>.pkl``, with ``"depth": f, "screen": j``) name the screen."""
+    import dataclasses
+
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+    from .jackknife import MAX_GUIDE_POSITIONS
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _predictive_refusal(spec, data, world)
+    if why is not None:
+        raise PredictiveUnsupported(f"a depth study is not available for {why}: the count simulator serves the sorting "
+                                    "variant Normal and MixtureNormal models on one GPU")
+    n_screens, per_run = int(n_screens), int(max_per_run)
+    if n_screens < 2:
+        raise ValueError(f"a depth study needs at least 2 screens per depth, got {n_screens}")
+    depths = design_depths(depths)
+    if not 1 <= per_run <= MAX_GUIDE_POSITIONS:
+        raise ValueError(f"max_per_run must be in [1, {MAX_GUIDE_POSITIONS}] (the screen is member 0 of every run), "
+                         f"got {per_run}")
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+    first = run_inference(model, guide, data, seed=seed, report_every=report_every, verbose=verbose, **common)
+    eng = bootstrap_engine(model, guide, data, first[0])
+    try:
+        x, x_bc = design_screens(eng, depths, n_screens, design_seed)
+        torch.cuda.synchronize(eng.device)
+    finally:
+        eng.close()
+    home = lambda t, like: None if t is None else t.to(like.device, like.dtype)  # noqa: E731
+    plan = design_plan(data, seed, depths, home(x, data.X_masked),
+                       home(x_bc, data.X_bcmatch_masked) if x_bc is not None else None)
+    plan = dataclasses.replace(plan, per_run=per_run)
+    results = _fit_plan(model, guide, data, plan, common, report_every, verbose)
+    return results[0], [results[1 + i * n_screens:1 + (i + 1) * n_screens] for i in range(len(depths))]
 
 
 def identify_model_guide(args):

@@ -424,6 +424,47 @@ int bean_hip_simulate(bean_hip_ctx* ctx, uint64_t seed, uint64_t draw, void* x_o
 int bean_hip_simulate_members(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t n_draws, void* x_out,
                               uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes, void* stream);
 
+/* K replicate screens at each of D read depths in ONE launch: the screens of a depth study ("would sequencing deeper
+ * tighten the hits?").
+ *
+ *   bean_hip_simulate_design      takes the handles bean_hip_predictive_supported takes, any size, n_depths = D >= 1,
+ *                                 n_draws = K >= 1 and D * K <= BEAN_HIP_MAX_MEMBERS.  depths: D factors in HOST memory,
+ *                                 each finite and > 0; they are copied into the launch's arguments before the call
+ *                                 returns (no device pointer of the caller, no host synchronisation).  x_out:
+ *                                 (D, K, R, B, G) float32, member-major with member m = i * K + j depth i, draw j -
+ *                                 D * K members of bean_hip_bind_member_counts; xbc_out: the same shape, required
+ *                                 exactly when the handle has BEAN_FLAG_USE_BCMATCH and null (0 bytes) otherwise.
+ *                                 Launches: those of bean_hip_simulate_members - one k_set_step(first_draw, slot 0,
+ *                                 n = 0), one PREP k_param - then one k_simulate_design with the member on blockIdx.y.
+ *                                 Which draw is whose: member (i, j) is member j of bean_hip_simulate_members(seed,
+ *                                 first_draw, K) - the shared Normal sites of draw first_draw (or the injected *_IN
+ *                                 values), draw index first_draw + j for its pi, Dirichlet and categorical sites AT
+ *                                 EVERY DEPTH (common random numbers across depths), BEAN_BUF_PI_IN and
+ *                                 BEAN_FLAG_DUMP_PI as there - except that every (replicate, guide) draws
+ *                                     n_i = floor(depths[i] * n_obs + 0.5)   (float64)
+ *                                 reads instead of its observed total n_obs.  Concentrations, a0, masks and size
+ *                                 factors are the observed ones: nothing else of the draw depends on the depth.  So
+ *                                   (a) with depths[i] == 1 plane (i, j) is bit for bit plane j of
+ *                                       bean_hip_simulate_members(seed, first_draw, K);
+ *                                   (b) for depths[a] <= depths[b], plane (a, j) <= plane (b, j) elementwise: read t of
+ *                                       a pair is word t of its stream and p does not depend on n;
+ *                                   (c) every (replicate, guide) of plane (i, j) sums to n_i exactly.
+ *                                 n_i is clamped to 2^24 - 1: the words a (likelihood, draw) owns in the categorical
+ *                                 stream, and the limit of exact float32 integers.  Callers keep max(depths) * max n_obs
+ *                                 below 2^24 (HipSVI.simulate_design refuses otherwise).  Cost: the time follows the
+ *                                 LARGEST n_i of each 64-guide tile, so a depth-4 member takes four times its depth-1
+ *                                 twin.  State: as bean_hip_simulate_members - nothing of the fit is written, and a
+ *                                 following bean_hip_svi_resume does not continue an earlier window.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched, the handle stays usable): a null handle; a
+ * handle that is not supported (the message names bean_hip_predictive_supported) or not prepared; null depths; D < 1,
+ * K < 1 or D * K > BEAN_HIP_MAX_MEMBERS (the message states the product and the limit); a depth that is not finite or
+ * not > 0 (the message states its index and value); byte counts other than 4 D K R B G (the message states D and K);
+ * xbc_out on a handle without BEAN_FLAG_USE_BCMATCH or without it on a handle with the flag. */
+int bean_hip_simulate_design(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t n_draws, const double* depths,
+                             int32_t n_depths, void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes,
+                             void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
