@@ -43,6 +43,34 @@ def parse_depths(text):
     return out
 
 
+def parse_effects(text):
+    """``--power-effects``: a comma-separated list of finite floats, negatives allowed, in the order given (``argparse``
+    type: a bad entry, an effect that is not finite and an effect given twice are refused with their sentence)."""
+    import math
+
+    entries = [e.strip() for e in str(text).split(",")]
+    out = []
+    for entry in entries:
+        try:
+            f = float(entry)
+        except (TypeError, ValueError):
+            raise argparse.ArgumentTypeError(f"{entry!r} is not a number: a comma-separated list of effects such as "
+                                             "0.1,0.2,0.4 is expected") from None
+        if not math.isfinite(f):
+            raise argparse.ArgumentTypeError(f"a planted effect must be a finite number, got {entry}")
+        if f in out:
+            raise argparse.ArgumentTypeError(f"effect {f:g} is given more than once")
+        out.append(f)
+    return out
+
+
+def _open_unit_interval(text: str) -> float:
+    value = float(text)
+    if not 0.0 < value < 1.0:
+        raise argparse.ArgumentTypeError(f"must be in (0, 1), got {text}")
+    return value
+
+
 def get_parser():
     parser = argparse.ArgumentParser(prog="bean")
     sub = parser.add_subparsers(dest="subcommand", help="bean subcommands")
@@ -123,6 +151,25 @@ def get_parser():
                      help="Screens drawn and refitted per depth of --design-depths (default 8, at least 2).")
     own.add_argument("--design-seed", dest="design_seed", type=int, default=101,
                      help="Seed of the simulated screens of --design-depths (default 101).")
+    own.add_argument("--power-effects", dest="power_effects", type=parse_effects, default=None, metavar="E,E,...",
+                     help="Power study: after the fit of the screen, draw --power-screens screens from the fitted model on "
+                          "the GPU with each of these effects planted - a comma-separated list such as 0.1,0.2,0.4, "
+                          "negatives allowed (--power-effects=-0.5,0.5); with effect e every target's mu is e, the value "
+                          "itself, everything else (sd, editing rates, masks, size factors, a0, pi_a0, totals) as fitted "
+                          "and observed - refit each with the same seed and report how often a target is called (|z| >= "
+                          "1.96 with the effect's sign): one row per effect in bean_power.<model>.csv (effect, n_screens, "
+                          "n_planted, power_mean, power_median, shrinkage, median_mu_power_se) and the columns "
+                          "power_x<e> and mde<100 level> (mde<100 level>_neg with negative effects) in the element "
+                          "table.  Effect 0, whose rate is the false-positive rate, is added where absent.  Sorting "
+                          "variant screens only; not combined with --bootstrap, --design-depths, --n-seeds > 1, any "
+                          "--jackknife-* flag, --num-particles > 1 or --load-existing.")
+    own.add_argument("--power-screens", dest="power_screens", type=_positive_int, default=8, metavar="K",
+                     help="Screens drawn and refitted per effect of --power-effects (default 8, at least 2).")
+    own.add_argument("--power-seed", dest="power_seed", type=int, default=101,
+                     help="Seed of the simulated screens of --power-effects (default 101).")
+    own.add_argument("--power-level", dest="power_level", type=_open_unit_interval, default=0.8, metavar="P",
+                     help="The power the minimal detectable effect of --power-effects is read at, in (0, 1) (default 0.8: "
+                          "the column mde80).")
     from .build_prior import attach_args as attach_prior_args
 
     attach_prior_args(sub.add_parser("build-prior", help="obtain prior_params.pkl for batched runs"))

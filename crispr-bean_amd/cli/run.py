@@ -64,7 +64,8 @@ _SAME_SEED = "{flag} fits every member with the same seed and does not combine w
 _TWO_RUNS = "{flag} and {other} are two runs: they do not combine in one."
 _NEEDS_FITS = "{{flag}} needs the leave-one-{}out fits and does not combine with --load-existing."
 _SAMPLE_RULES = (("jackknife_replicates", _TWO_RUNS), ("jackknife_guides", _TWO_RUNS), ("n_seeds", _SAME_SEED),
-                 ("load_existing", _NEEDS_FITS.format("")), ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))
+                 ("load_existing", _NEEDS_FITS.format("")), ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS),
+                 ("power_effects", _TWO_RUNS))
 _BOOTSTRAP_FAMILY = ("{{flag}} simulates the counts of the sorting variant models (Normal, MixtureNormal) and is not "
                      "available for {}.")
 # the flags that ask for a member set, in the order their refusals are reported:
@@ -72,11 +73,13 @@ _BOOTSTRAP_FAMILY = ("{{flag}} simulates the counts of the sorting variant model
 MEMBER_FLAGS = (
     ("jackknife_replicates", "replicates", (("n_seeds", _SAME_SEED),
                                             ("load_existing", _NEEDS_FITS.format("replicate-")),
-                                            ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))),
+                                            ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS),
+                                            ("power_effects", _TWO_RUNS))),
     ("jackknife_guides", "guides", (("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS),
                                     ("load_existing", _NEEDS_FITS.format("guide-")),
                                     ("tiling", "{flag} needs targets that own their guides and does not combine with tiling."),
-                                    ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))),
+                                    ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS),
+                                    ("power_effects", _TWO_RUNS))),
     ("jackknife_samples", "sample", (("jackknife_conditions", _TWO_RUNS),) + _SAMPLE_RULES),
     ("jackknife_conditions", "condition", (("jackknife_samples", _TWO_RUNS),) + _SAMPLE_RULES),
     ("bootstrap", "bootstrap", (("bootstrap_one", "{flag} needs at least 2 screens."),
@@ -87,7 +90,7 @@ MEMBER_FLAGS = (
                                 ("jackknife_conditions", _TWO_RUNS),
                                 ("load_existing", "{flag} needs the refits of its simulated screens and does not combine "
                                                   "with --load-existing."),
-                                ("design_depths", _TWO_RUNS))),
+                                ("design_depths", _TWO_RUNS), ("power_effects", _TWO_RUNS))),
     ("design_depths", "design", (("design_one", "{flag} needs at least 2 screens per depth (--design-screens)."),
                                  ("tiling", _BOOTSTRAP_FAMILY.format("tiling screens (MultiMixtureNormal)")),
                                  ("survival", _BOOTSTRAP_FAMILY.format("survival screens")),
@@ -96,12 +99,22 @@ MEMBER_FLAGS = (
                                  ("jackknife_conditions", _TWO_RUNS),
                                  ("load_existing", "{flag} needs the refits of its simulated screens and does not combine "
                                                    "with --load-existing."),
-                                 ("bootstrap", _TWO_RUNS))),
+                                 ("bootstrap", _TWO_RUNS), ("power_effects", _TWO_RUNS))),
+    ("power_effects", "power", (("power_one", "{flag} needs at least 2 screens per effect (--power-screens)."),
+                                ("tiling", _BOOTSTRAP_FAMILY.format("tiling screens (MultiMixtureNormal)")),
+                                ("survival", _BOOTSTRAP_FAMILY.format("survival screens")),
+                                ("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS),
+                                ("jackknife_guides", _TWO_RUNS), ("jackknife_samples", _TWO_RUNS),
+                                ("jackknife_conditions", _TWO_RUNS),
+                                ("load_existing", "{flag} needs the refits of its simulated screens and does not combine "
+                                                  "with --load-existing."),
+                                ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))),
 )
 _IS_SET = {"n_seeds": lambda args: int(getattr(args, "n_seeds", 1) or 1) > 1,
            "bootstrap": lambda args: int(getattr(args, "bootstrap", 0) or 0) > 0,
            "bootstrap_one": lambda args: int(getattr(args, "bootstrap", 0) or 0) == 1,
            "design_one": lambda args: int(getattr(args, "design_screens", 8) or 0) < 2,
+           "power_one": lambda args: int(getattr(args, "power_screens", 8) or 0) < 2,
            "survival": lambda args: getattr(args, "selection", None) == "survival",
            "tiling": lambda args: getattr(args, "library_design", None) == "tiling",
            "guides_max": lambda args: int(getattr(args, "jackknife_guides_max", 63)) > 63}
@@ -113,7 +126,7 @@ def _refuse(message):
 
 def member_mode(args, fail=_refuse, only=None, parser_rules=None):
     """The member set this run fits next to the screen: None, "seeds", "replicates", "guides", "sample", "condition",
-    "bootstrap" or "design".
+    "bootstrap", "design" or "power".
     A combination that is refused goes to ``fail(sentence)`` (the parser's ``error``; here, raising ``ValueError``).
     ``only``: the flags whose rules are looked at (default: all); ``parser_rules``: further rules per flag, after its own."""
     is_set = lambda attr: _IS_SET.get(attr, lambda a: bool(getattr(a, attr, False)))(args)  # noqa: E731
@@ -256,12 +269,21 @@ def _design_members(fit, ndata, args, guide_names):
             {"design": jk.design_summary(full, fits, depths, data=ndata)})
 
 
+def _power_members(fit, ndata, args, guide_names):
+    effects = model_run.power_effects(args.power_effects)
+    full, fits = fit(model_run.run_inference_power, effects=effects, n_screens=int(getattr(args, "power_screens", 8)),
+                     power_seed=int(getattr(args, "power_seed", model_run.SEED)))
+    heads = [{"effect": e, "screen": j} for e in effects for j in range(len(fits[0]))]
+    return (full, _entries(heads, [r for row in fits for r in row]),
+            {"power": jk.power_summary(full, fits, effects, level=float(getattr(args, "power_level", 0.8)))})
+
+
 # mode -> (what fits its members and returns (the fit the tables come from, the members' entry of the --save-raw
 #          pickle, write_result_table's keywords for their summary), the key of that entry)
 MEMBER_RUNS = {"seeds": (_seed_members, "ensemble"), "replicates": (_replicate_members, "jackknife"),
                "guides": (_guide_members, "guide_jackknife"), "sample": (_sample_members, "sample_jackknife"),
                "condition": (_sample_members, "sample_jackknife"), "bootstrap": (_bootstrap_members, "bootstrap"),
-               "design": (_design_members, "design")}
+               "design": (_design_members, "design"), "power": (_power_members, "power")}
 
 
 def main(args, return_data=False):

@@ -2798,3 +2798,61 @@ extern "C" int bean_hip_simulate_design(bean_hip_ctx* c, uint64_t seed, uint64_t
     HIP_OK(hipGetLastError());
     return 0;
 }
+
+// K replicate screens at each of D planted effects in one launch (k_simulate_power: a power study's screens, (D, K)
+// member-major - D * K members of bean_hip_bind_member_counts).  Everything of member (i, j) is member j of
+// bean_hip_simulate_members(seed, first_draw, K) but the table entries of the planted targets, which its lanes form at
+// mu = effects[i].  The effects are copied into the launch's argument struct here: the caller's array is not read after
+// the call returns; `plant` is the caller's device array and is read by the kernel.
+extern "C" int bean_hip_simulate_power(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                       const double* effects, int32_t n_effects, const void* plant, void* x_out,
+                                       uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes, void* stream_) {
+    if (!c) return fail("bean_hip_simulate_power: null handle");
+    if (!predictive_shape_ok(c))
+        return fail("bean_hip_simulate_power: the count simulator does not take this handle "
+                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
+                    "covariates, one member, one particle");
+    if (!c->prepared) return fail("bean_hip_simulate_power: call bean_hip_prepare first");
+    if (!effects) return fail("bean_hip_simulate_power: effects is null");
+    if (n_effects < 1 || n_draws < 1 || (int64_t)n_effects * n_draws > BEAN_HIP_MAX_MEMBERS)
+        return fail("bean_hip_simulate_power: n_effects >= 1, n_draws >= 1 and n_effects * n_draws <= " +
+                    std::to_string(BEAN_HIP_MAX_MEMBERS) + ", got " + std::to_string(n_effects) + " x " +
+                    std::to_string(n_draws) + " = " + std::to_string((int64_t)n_effects * n_draws));
+    for (int i = 0; i < n_effects; ++i)
+        if (!(effects[i] >= -1.7976931348623157e308 && effects[i] <= 1.7976931348623157e308))
+            return fail("bean_hip_simulate_power: effects[" + std::to_string(i) + "] = " + std::to_string(effects[i]) +
+                        " is not a finite number");
+    if (check_bound(c, false, false)) return -1;
+    const DevArgs& d0 = c->d;
+    const uint64_t n = (uint64_t)n_effects * n_draws * d0.R * d0.B * d0.G;
+    const bool use_bc = (d0.flags & kUseBc) != 0;
+    const std::string shape = "(D, K, R, B, G) float32 with D = " + std::to_string(n_effects) + ", K = " +
+                              std::to_string(n_draws) + ", " + std::to_string(4 * n) + " bytes";
+    if (!x_out || x_bytes != 4 * n) return fail("bean_hip_simulate_power: x_out must hold " + shape);
+    if (use_bc && (!xbc_out || xbc_bytes != 4 * n))
+        return fail("bean_hip_simulate_power: this handle uses the barcode-matched counts: xbc_out must hold " + shape);
+    if (!use_bc && (xbc_out || xbc_bytes))
+        return fail("bean_hip_simulate_power: xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
+    hipStream_t stream = (hipStream_t)stream_;
+    c->d.seed = seed;
+    c->resume_ok = false;  // the workspace now holds draw first_draw and its tables
+    launch_set_step(c, stream, first_draw, 0, 0);
+    launch_param<false, false, true>(c, stream);
+    const DevArgs& d = c->d;
+    SimArgs sa;
+    sa.x_out = (float*)x_out;
+    sa.xbc_out = (float*)xbc_out;
+    sa.alpha_out = nullptr;
+    PowerArgs pw;
+    pw.K = n_draws;
+    pw.D = n_effects;
+    pw.plant = (const uint8_t*)plant;
+    for (int i = 0; i < kEnsembleMaxMembers; ++i) pw.effect[i] = i < n_effects ? effects[i] : 0.0;
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)(n_effects * n_draws)), block(64);
+    const size_t lds = simulate_wave2_lds(d.B);
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_simulate_power<fam(), acc()>), grid, block, lds, stream, d, sa, pw);
+    });
+    HIP_OK(hipGetLastError());
+    return 0;
+}

@@ -760,6 +760,22 @@ __device__ __forceinline__ void write_phi_entry(const DevArgs& c, int t, int b, 
     c.tabPy[o] = -(ufh - ufl) * inv * dsig_dy;
 }
 
+// One table value alone, for a lane that forms the entry of its own target (k_simulate_power's planted targets):
+// write_phi_entry's operations on the same operands - the same bits as the table of a PREP launch that drew (mu, y).
+// phi_inv_sigma: 1 / sigma of the draw y; planted_phi_entry: Phi(u_hi) - Phi(u_lo) of bin b at mean mu.
+__device__ __forceinline__ double phi_inv_sigma(const DevArgs& c, double y) {
+    const double sigma = c.family == kNormal ? exp(0.5 * y) : exp(y);
+    return 1.0 / sigma;
+}
+__device__ __forceinline__ double planted_phi_entry(const DevArgs& c, int b, double mu, double inv) {
+#pragma clang fp contract(off)
+    const double zh = c.z_hi[b], zl = c.z_lo[b];
+    double ch = 1.0, cl = 0.0;
+    if (!isinf(zh)) ch = norm_cdf((zh - mu) * inv);
+    if (!isinf(zl)) cl = norm_cdf((zl - mu) * inv);
+    return ch - cl;
+}
+
 // Thin mode (the usual one): a target block of kParamBlock threads holds kParamBlock / DevArgs::lpt targets
 // and works in three phases with two thread -> work maps:
 //   A  sums      lpt lanes per target (group map): the target's (guide, replicate) rows

@@ -1,6 +1,7 @@
 // k_simulate_wave2: replicate counts of the variant sorting families, drawn on the device (posterior predictive check);
 // k_simulate_members (at the end): K such screens in one launch, the member on blockIdx.y (parametric bootstrap);
-// k_simulate_design (after it): D x K screens in one launch, K draws at each of D read depths (depth study).
+// k_simulate_design (after it): D x K screens in one launch, K draws at each of D read depths (depth study);
+// k_simulate_power (last): D x K screens in one launch, K draws at each of D planted effects (power study).
 //
 // For one draw d of the latent sites - the draw bean_hip_elbo_grad(seed, step = d) evaluates, prepared by the same
 // k_set_step + PREP k_param launches - every (replicate, guide) forms the Dirichlet-Multinomial concentrations of its
@@ -66,9 +67,13 @@ __device__ __forceinline__ long design_total(const double n_obs, const double de
 // of k_simulate_members is bit for bit the screen k_simulate_wave2 leaves for the same draw (as guide_pair_math is the
 // one body of the guide kernels).  DEPTH (k_simulate_design alone): the pair draws design_total(n_obs, depth) reads
 // instead of n_obs; nothing else of the draw - pi, concentrations, gammas, which word is which read - looks at it.
-template <int FAM, bool ACC, bool DEPTH = false>
+// PLANT (k_simulate_power alone): a lane whose target is planted (`plant` null, or plant[target] != 0) takes
+// planted_phi_entry at mu = `effect` and the target's drawn y_t wherever the body reads the table - pass 1 and the
+// concentrations the log branch forms again; every other lane, and everything else of the draw, is untouched.
+template <int FAM, bool ACC, bool DEPTH = false, bool PLANT = false>
 __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimArgs& s, const StepCtr& ctr, double* sim_lds,
-                                                   const bool dump_pi, const double depth = 1.0) {
+                                                   const bool dump_pi, const double depth = 1.0, const double effect = 0.0,
+                                                   const uint8_t* plant = nullptr) {
     constexpr bool MIX = FAM == kMixture;
     const int wg = blockIdx.x;
     const int kk = wg >> 3;
@@ -131,6 +136,13 @@ __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimAr
     const double w1 = MIX ? (ACC ? pe1 : pi1) : 1.0;        // weight of the edited component
     const double epsB = kEps / (double)B;
     const long tcol = c.g2t[g];
+    // the table value of bin b: the shared table's, or - PLANT, a planted target - this lane's own entry at the effect
+    const bool planted = PLANT && (!plant || plant[tcol] != 0);
+    const double plant_inv = planted ? phi_inv_sigma(c, c.y_t[tcol]) : 0.0;
+    const auto tab = [&](int b) {
+        if (PLANT && planted) return planted_phi_entry(c, b, effect, plant_inv);
+        return c.tabP[(long)b * c.T + tcol];
+    };
 
 #pragma unroll 1
     for (int lik = 0; lik < 2; ++lik) {
@@ -143,7 +155,7 @@ __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimAr
         double S = 0.0, n = 0.0;
 #pragma unroll 1
         for (int b = 0; b < B; ++b) {
-            const double p1 = c.tabP[(long)b * c.T + tcol];
+            const double p1 = tab(b);
             const double e = fma(w0, MIX ? c_p0[b] : 0.0, w1 * p1);
             S += e * sf[b];
             n += (double)X[((long)r * B + b) * G + g];
@@ -184,8 +196,7 @@ __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimAr
             // + log U / alpha, from the same counters (the boost's block first, then the rounds), less their maximum.
             // The column holds the gammas by now, so the concentrations are formed again: same operands, same bits.
             const auto conc = [&](int b) {
-                const double ar = alpha_raw(w0, MIX ? c_p0[b] : 0.0, w1, c.tabP[(long)b * c.T + tcol], sf[b], epsB,
-                                            ai * c_sm[b]);
+                const double ar = alpha_raw(w0, MIX ? c_p0[b] : 0.0, w1, tab(b), sf[b], epsB, ai * c_sm[b]);
                 return ar < kEps ? kEps : ar;
             };
             double mx = -INFINITY;
@@ -321,6 +332,49 @@ void k_simulate_design(DevArgs c, SimArgs s, DesignArgs dz) {
     sm.xbc_out = s.xbc_out ? s.xbc_out + plane : nullptr;
     sm.alpha_out = nullptr;
     simulate_pair_body<FAM, ACC, true>(c, sm, ctr, sim_lds, member == 0, dz.depth[i]);
+}
+
+// k_simulate_power: K replicate screens at each of D planted effects in one launch (a power study's screens).  gridDim.x
+// as k_simulate_members, gridDim.y = D * K; member m = blockIdx.y = i * K + j is effect i, draw j, and writes plane (i, j)
+// of x_out / xbc_out, (D, K, R, B, G) member-major.  The effects travel by value in the argument struct (D <= 64 doubles,
+// read through scalar loads of the kernel arguments, indexed by the uniform blockIdx.y / K); `plant` is a device array of
+// T bytes (non-zero: planted) or null (every target planted).  Member (i, j) is member j of k_simulate_members in
+// everything but the table entries of its planted targets: the shared Normal sites (y_t among them), pi_in and DUMP_PI
+// (member 0 alone) as there, draw ctrB->step + j for the pi, gamma and categorical sites AT EVERY EFFECT (common random
+// numbers across effects).  A (replicate, guide) lane of a planted target forms Phi(u_hi) - Phi(u_lo) at mu = effect[i] -
+// the value itself, not a shift of the fitted mu - and the target's drawn y_t, with write_phi_entry's operations, in
+// pass 1 and again in the log branch; 2 B normal CDFs per likelihood next to ceil(n_obs / 4) categorical trips.  So
+//   (a) with nothing planted, plane (i, j) is bit for bit plane j of k_simulate_members;
+//   (b) plane (i, j) is bit for bit plane j of k_simulate_members on a handle whose PREP launch drew mu_t = effect[i]
+//       on the planted targets (mu_loc = float32(effect[i]), eps_mu = 0) and is equal in everything else;
+//   (c) every (replicate, guide) sums to n_obs exactly;
+//   (d) the lanes of unplanted targets are those of k_simulate_members in every plane.
+// The variant families share no parameter between targets and S = sum_b e_b sf_b normalises per guide, so planting every
+// target at once leaves each target's counts what they are with it alone planted.  LDS, scratch, atomics and stores as
+// k_simulate_wave2.
+struct PowerArgs {
+    int K;                               // draws per effect
+    int D;                               // effects
+    const uint8_t* plant;                // [T] or null: every target
+    double effect[kEnsembleMaxMembers];  // [D]
+};
+static_assert(sizeof(DevArgs) + sizeof(SimArgs) + sizeof(PowerArgs) <= 4096, "the kernel arguments fit their segment");
+
+template <int FAM, bool ACC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
+void k_simulate_power(DevArgs c, SimArgs s, PowerArgs pw) {
+    extern __shared__ double sim_lds[];
+    StepCtr ctr = *c.ctrB;
+    const unsigned member = blockIdx.y;
+    const unsigned i = member / (unsigned)pw.K, j = member - i * (unsigned)pw.K;
+    if (i >= (unsigned)pw.D) return;
+    ctr.step += (unsigned long long)j;
+    const size_t plane = (size_t)member * (size_t)c.R * (size_t)c.B * (size_t)c.G;
+    SimArgs sm;
+    sm.x_out = s.x_out + plane;
+    sm.xbc_out = s.xbc_out ? s.xbc_out + plane : nullptr;
+    sm.alpha_out = nullptr;
+    simulate_pair_body<FAM, ACC, false, true>(c, sm, ctr, sim_lds, member == 0, 1.0, pw.effect[i], pw.plant);
 }
 
 }  // namespace bean

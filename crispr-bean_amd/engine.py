@@ -679,6 +679,7 @@ class HipSVI:
                 self._native_comm = False
             self.lib.bean_hip_destroy(self._h)
             self._h = None
+            self._plant = None  # (simulate_power's mask: nothing reads it after the synchronisation above)
 
     def __del__(self):
         try:
@@ -907,6 +908,50 @@ class HipSVI:
         with self._on_stream():
             self._check(self.lib.bean_hip_simulate_design(self._h, int(seed), int(first_draw), K, arr, D, ptr(x), nb(x),
                                                           ptr(xbc), nb(xbc), self._sptr()), "simulate_design")
+        self.invalidate_resume()
+        out = {"X": x}
+        if xbc is not None:
+            out["X_bcmatch"] = xbc
+        return out
+
+    def simulate_power(self, first_draw: int, n_draws: int, effects, plant=None, seed: int = 101) -> Dict[str, torch.Tensor]:
+        """``n_draws`` replicate screens at each of the planted effects ``effects`` in one launch
+        (``bean_hip_simulate_power``): ``X`` (D, K, R, B, G) float32 and, where the fit uses the barcode-matched counts,
+        ``X_bcmatch`` - device tensors, member-major over (effect, draw).  Plane (i, j) is plane j of
+        ``simulate_members(first_draw, n_draws)`` with ``mu_t = effects[i]`` - the value itself, not a shift of the fitted
+        mean - on every planted target: the same pi, Dirichlet and categorical streams at every effect, the drawn ``sd``
+        and every guide-level quantity as they are.  ``plant``: ``None`` (every target) or T booleans / uint8 (tensor or
+        array; non-zero: planted), moved to the device as uint8 and held by the engine until the next call or ``close()``;
+        any other length is a ``ValueError``.  With nothing planted the planes are those of ``simulate_members`` bit for
+        bit, and the guides of unplanted targets are in every plane.  Leaves the fit alone as ``simulate`` does; the next
+        ``run(resume=True)`` is a plain run."""
+        if not self.predictive_supported:
+            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
+                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        K = int(n_draws)
+        es = [float(e) for e in effects]
+        D = len(es)
+        T = int(self.T)
+        mask = None
+        if plant is not None:
+            mask = torch.as_tensor(plant)
+            if mask.dim() != 1 or int(mask.numel()) != T or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f"simulate_power: plant must be None or {T} booleans / uint8 (one per target), got "
+                                 f"{mask.dtype} of shape {tuple(mask.shape)}")
+        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
+        shape = (D, max(K, 0), R, B, G)
+        x = torch.empty(shape, dtype=torch.float32, device=self.device)
+        xbc = torch.empty(shape, dtype=torch.float32, device=self.device) if self.use_bcmatch else None
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
+        arr = (ctypes.c_double * max(D, 1))(*es)
+        with self._on_stream():
+            if mask is not None:
+                mask = mask.to(self.device).to(torch.uint8).contiguous()
+            self._plant = mask  # the launch reads it: kept alive until the next call or close()
+            self._check(self.lib.bean_hip_simulate_power(self._h, int(seed), int(first_draw), K, arr, D, ptr(mask), ptr(x),
+                                                         nb(x), ptr(xbc), nb(xbc), self._sptr()), "simulate_power")
         self.invalidate_resume()
         out = {"X": x}
         if xbc is not None:

@@ -41,6 +41,12 @@ The bootstrap's screens drawn at other read depths (``HipSVI.simulate_design``):
 ``floor(f * n_obs + 0.5)`` reads, everything else as observed - the same cells, other read counts: ``design_plan``,
 ``design_summary``.
 
+Power study: how large must a variant's effect be for this screen to have called it, and how often does a variant with no
+effect cross the threshold (``run_inference_power``, ``bean run --power-effects``).
+
+The bootstrap's screens drawn with an effect planted (``HipSVI.simulate_power``): the guides of every planted target sort
+with ``mu_t = effect``, the value itself, everything else as fitted and observed: ``power_plan``, ``power_summary``.
+
 Each of these, and the seed ensemble, is K fits of one screen: a ``MemberPlan``, fitted by ``model/run.py::_fit_plan``.
 
 Pure torch: no GPU involved in this file.
@@ -571,3 +577,136 @@ def design_summary(full, fits, depths, z_hit: float = 1.96, data=None) -> Dict[s
     return {"mu_design_se": se, "mu_design_sd": s.mean(1), "se_ratio": ratio, "n_left_out": int((~ok).sum()),
             "hits": torch.nonzero(hit).reshape(-1).tolist(), "n_hits": n_hits, "recovery": recovery, "n_screens": K,
             "median_total": median_total, "depths": depths}
+
+
+# ---------------------------------------------------------------- power study
+def effect_text(e) -> str:
+    """A planted effect as labels, tags and column names show it: ``{e:g}``."""
+    return f"{float(e):g}"
+
+
+def power_plan(data, seed, effects, x, x_bcmatch=None) -> MemberPlan:
+    """A power study: member 0 is the screen, member ``1 + i * K + j`` a ``copy.copy(data)`` whose ``X_masked`` is plane
+    ``(i, j)`` of ``x`` (D, K, R, B, G) - planted effect ``effects[i]``, draw j, the screens ``HipSVI.simulate_power`` drew
+    from the fitted model - and, where ``x_bcmatch`` is given, whose ``X_bcmatch_masked`` is plane ``(i, j)`` of it.
+
+    Conditioned on, as in ``bootstrap_plan``: both masks, the size factors, ``a0`` / ``a0_bcmatch``, ``pi_a0`` and the
+    control allele counts are the observed screen's, shared with ``data``.  Every member gets ``seed``; an engine run holds
+    the screen and at most 63 of the screens.  ``data`` is not modified."""
+    seed = int(seed)
+    effects = [float(e) for e in effects]
+    if x.dim() != 5 or int(x.shape[0]) != len(effects):
+        raise ValueError(f"x has shape {tuple(x.shape)}: (D, K, R, B, G) with D = {len(effects)} effects is needed")
+    if x_bcmatch is not None and tuple(x_bcmatch.shape) != tuple(x.shape):
+        raise ValueError(f"x_bcmatch has shape {tuple(x_bcmatch.shape)}, x {tuple(x.shape)}")
+    K = int(x.shape[1])
+
+    def screen(data, ij):
+        i, j = ij
+        out = copy.copy(data)
+        out.X_masked = x[i, j]
+        if x_bcmatch is not None:
+            out.X_bcmatch_masked = x_bcmatch[i, j]
+        return out
+
+    items = [(i, j) for i in range(len(effects)) for j in range(K)]
+    plan = _leave_one_out_plan(data, seed, items, label=lambda ij: f"effect {effect_text(effects[ij[0]])} screen {ij[1]}",
+                               tag=lambda ij: f"effect{effect_text(effects[ij[0]])}_{ij[1]}", key="effect",
+                               value=lambda ij: effects[ij[0]], leave=screen, differ_in=("masks", "counts"),
+                               per_run=MAX_GUIDE_POSITIONS, label_halts=True)
+    extra = [{"effect": e["effect"], "screen": None if k == 0 else items[k - 1][1], "seed": seed}
+             for k, e in enumerate(plan.dump_extra)]
+    return replace(plan, dump_extra=extra)
+
+
+def _first_crossing(anchors, power, level):
+    """Per target, the smallest effect at which ``power`` (A, T) reaches ``level`` along ``anchors`` (A ascending values,
+    the first of them 0): the smallest positive anchor where the power at 0 already reaches the level; else, at the first
+    anchor k whose power reaches it, the point between anchors k - 1 and k where the straight line between their powers
+    meets the level; ``+inf`` where no anchor reaches it."""
+    A, T = power.shape
+    out = torch.full((T,), float("inf"), dtype=torch.float64)
+    if A < 2:
+        return out
+    open_ = torch.ones(T, dtype=torch.bool)
+    at0 = power[0] >= level
+    out[at0] = anchors[1]
+    open_ &= ~at0
+    for k in range(1, A):
+        here = open_ & (power[k] >= level)
+        w = (level - power[k - 1]) / (power[k] - power[k - 1])
+        out[here] = (anchors[k - 1] * (1.0 - w) + anchors[k] * w)[here]
+        open_ &= ~here
+    return out
+
+
+def power_summary(full, fits, effects, plant=None, z_hit: float = 1.96, level: float = 0.8) -> Dict[str, object]:
+    """Power-study summary (float64).  ``fits[i][j]`` is the refit of draw j with ``effects[i]`` planted, ``m_ij`` /
+    ``s_ij`` its ``mu_loc`` / ``mu_scale``; ``effects`` holds the null, effect 0; ``plant``: ``None`` (every target) or T
+    booleans, the targets that were planted.
+
+    * ``detected_ij[t]``: ``|m_ij| / s_ij >= z_hit`` and, for ``e_i != 0``, ``sign(m_ij) == sign(e_i)``;
+    * ``power`` (D, T): the mean of ``detected`` over j - at effect 0 the false-positive rate; NaN on unplanted targets;
+    * ``power_mean`` (D,): the mean over planted targets and j; ``power_median`` (D,): the median over planted targets of
+      ``power``;
+    * ``mu_power_mean`` / ``mu_power_se`` (D, T): the mean and the unbiased (K - 1) standard deviation of ``m_ij`` over j;
+    * ``shrinkage`` (D,): the median over planted targets of ``mu_power_mean[i] / e_i``; NaN at effect 0;
+    * ``mde`` (T,): the minimal detectable effect.  Over the anchors - effect 0, then the positive effects in ascending
+      order - the first crossing of ``level`` by linear interpolation of ``power`` between neighbouring anchors; the
+      smallest positive effect where the power at 0 already reaches the level; ``+inf`` where no anchor reaches it (and
+      without a positive effect); NaN on unplanted targets;
+    * ``mde_neg`` (T,): likewise over ``|e|`` of the negative effects, a positive number; absent without a negative effect;
+    * ``n_planted``, ``n_screens`` = K, ``effects``, ``level``, ``z_hit``.
+
+    Fewer than two screens per effect, rows of different lengths, a row count that is not D, no effect 0, and a ``plant``
+    that is not one entry per target are each a ``ValueError``."""
+    effects = [float(e) for e in effects]
+    D = len(effects)
+    if D < 1 or D != len(fits):
+        raise ValueError(f"power_summary needs one list of fits per effect, got {len(fits)} for {D} effects")
+    K = len(fits[0])
+    if K < 2 or any(len(row) != K for row in fits):
+        raise ValueError(f"power_summary needs at least two screens at every effect, the same number at each, got "
+                         f"{[len(row) for row in fits]}")
+    if 0.0 not in effects:
+        raise ValueError(f"power_summary needs effect 0, the null every power is read against, among {effects}")
+    z_hit, level = float(z_hit), float(level)
+    m = torch.stack([torch.stack([_mu_loc(r).reshape(-1) for r in row]) for row in fits])  # (D, K, T)
+    s = torch.stack([torch.stack([_param(r, "mu_scale").reshape(-1) for r in row]) for row in fits])
+    T = int(m.shape[2])
+    if plant is None:
+        planted = torch.ones(T, dtype=torch.bool)
+    else:
+        planted = torch.as_tensor(plant).detach().cpu().reshape(-1) != 0
+        if int(planted.numel()) != T:
+            raise ValueError(f"plant has {int(planted.numel())} entries for {T} targets")
+    e = torch.tensor(effects, dtype=torch.float64)
+    nan = float("nan")
+    detected = (m.abs() / s) >= z_hit
+    directed = e != 0
+    detected[directed] &= torch.sign(m[directed]) == torch.sign(e[directed]).reshape(-1, 1, 1)
+    power = detected.to(torch.float64).mean(1)
+    power[:, ~planted] = nan
+    n_planted = int(planted.sum())
+    none = torch.full((D,), nan, dtype=torch.float64)
+    mean = m.mean(1)
+    if n_planted:
+        power_mean = power[:, planted].mean(1)
+        power_median = torch.stack([torch.quantile(power[i][planted], 0.5) for i in range(D)])
+        shrinkage = torch.stack([torch.quantile(mean[i][planted] / e[i], 0.5) if effects[i] != 0
+                                 else torch.tensor(nan, dtype=torch.float64) for i in range(D)])
+    else:
+        power_mean, power_median, shrinkage = none, none.clone(), none.clone()
+    out = {"power": power, "power_mean": power_mean, "power_median": power_median, "mu_power_mean": mean,
+           "mu_power_se": m.std(1, unbiased=True), "shrinkage": shrinkage, "n_planted": n_planted, "n_screens": K,
+           "effects": effects, "level": level, "z_hit": z_hit}
+    null = effects.index(0.0)
+    for key, sign in (("mde", 1.0), ("mde_neg", -1.0)):
+        rows = sorted((sign * f, i) for i, f in enumerate(effects) if sign * f > 0)
+        if key == "mde_neg" and not rows:
+            continue
+        anchors = torch.tensor([0.0] + [a for a, _ in rows], dtype=torch.float64)
+        mde = _first_crossing(anchors, power[[null] + [i for _, i in rows]], level)
+        mde[~planted] = nan
+        out[key] = mde
+    return out

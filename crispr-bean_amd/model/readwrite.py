@@ -189,6 +189,7 @@ def write_result_table(
     sample_jackknife: Optional[dict] = None,
     bootstrap: Optional[dict] = None,
     design: Optional[dict] = None,
+    power: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -224,7 +225,15 @@ def write_result_table(
     ``mu_design_se_x{f:g}``, one per depth in the summary's order (on the scale of ``mu``, not rescaled), and the
     summary's table - one row per depth: ``depth, n_screens, median_total, median_mu_design_se, se_ratio, recovery,
     n_hits`` - is written next to the element table as ``bean_design.<model_label><suffix>.csv``, also with
-    ``return_result``.  With ``None`` every file is byte for byte what it was and no further one is written."""
+    ``return_result``.  With ``None`` every file is byte for byte what it was and no further one is written.
+
+    ``power`` (a power study, ``model/jackknife.py::power_summary``): the element table gets exactly the columns
+    ``power_x{e:g}``, one per effect in the summary's order (the share of the refits that call the target; at effect 0 the
+    false-positive rate), then ``mde{100 * level:g}`` (the minimal detectable effect at the summary's level: ``mde80``)
+    and, where negative effects were given, ``mde{...}_neg``; the summary's table - one row per effect: ``effect,
+    n_screens, n_planted, power_mean, power_median, shrinkage, median_mu_power_se`` - is written next to the element
+    table as ``bean_power.<model_label><suffix>.csv``, also with ``return_result``.  With ``None`` every file is byte for
+    byte what it was and no further one is written."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -258,6 +267,17 @@ def write_result_table(
                              f"{len(element)} targets")
         for f, column in zip(design["depths"], spread):
             element[f"mu_design_se_x{float(f):g}"] = column
+    if power is not None:
+        rates = np.asarray(power["power"], dtype=np.float64)
+        if rates.ndim != 2 or rates.shape != (len(power["effects"]), len(element)):
+            raise ValueError(f"the power study summary has shape {rates.shape} for {len(power['effects'])} effects and "
+                             f"{len(element)} targets")
+        for e, column in zip(power["effects"], rates):
+            element[f"power_x{float(e):g}"] = column
+        mde = f"mde{100 * float(power['level']):g}"
+        element[mde] = _flat(power["mde"])
+        if "mde_neg" in power:
+            element[mde + "_neg"] = _flat(power["mde_neg"])
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always
@@ -279,6 +299,14 @@ def write_result_table(
                       "median_mu_design_se": np.median(spread, axis=1) if spread.shape[1] else np.full(len(spread), np.nan),
                       "se_ratio": _flat(design["se_ratio"]), "recovery": _flat(design["recovery"]),
                       "n_hits": int(design["n_hits"])}).to_csv(f"{prefix}bean_design.{model_label}{suffix}.csv", index=False)
+    if power is not None:
+        planted = ~np.isnan(rates[0]) if len(rates) else np.zeros(0, dtype=bool)
+        se = np.asarray(power["mu_power_se"], dtype=np.float64)[:, planted]
+        pd.DataFrame({"effect": [float(e) for e in power["effects"]], "n_screens": int(power["n_screens"]),
+                      "n_planted": int(power["n_planted"]), "power_mean": _flat(power["power_mean"]),
+                      "power_median": _flat(power["power_median"]), "shrinkage": _flat(power["shrinkage"]),
+                      "median_mu_power_se": np.median(se, axis=1) if se.shape[1] else np.full(len(se), np.nan)}
+                     ).to_csv(f"{prefix}bean_power.{model_label}{suffix}.csv", index=False)
     if return_result:
         return element
     element.to_csv(f"{prefix}bean_element_result.{model_label}{suffix}.csv")

@@ -18,8 +18,8 @@ import torch
 
 from ..engine import HipSVI
 from . import model as sorting_model
-from .jackknife import (bootstrap_plan, design_plan, guide_plan, particle_seeds, replicate_plan, sample_plan,  # noqa: F401
-                        seed_plan, stack_counts, stack_masks)
+from .jackknife import (bootstrap_plan, design_plan, guide_plan, particle_seeds, power_plan, replicate_plan,  # noqa: F401
+                        sample_plan, seed_plan, stack_counts, stack_masks)
 from .model import ModelSpec
 
 logger = logging.getLogger(__name__)
@@ -653,6 +653,108 @@ def run_inference_design(model, guide, data, depths, n_screens: int = 8, seed: i
     plan = dataclasses.replace(plan, per_run=per_run)
     results = _fit_plan(model, guide, data, plan, common, report_every, verbose)
     return results[0], [results[1 + i * n_screens:1 + (i + 1) * n_screens] for i in range(len(depths))]
+
+
+def power_effects(effects):
+    """The planted effects of a power study as floats, effect 0 - the null, whose detection rate is the false-positive
+    rate every power is read against - put in front where it is absent.  An empty list, an effect that is not finite and
+    an effect given twice are each a ``ValueError``."""
+    import math
+
+    out = [float(e) for e in effects]
+    if not out:
+        raise ValueError("a power study needs at least one effect")
+    for e in out:
+        if not math.isfinite(e):
+            raise ValueError(f"a planted effect must be a finite number, got {e:g}")
+    twice = sorted({e for e in out if out.count(e) > 1})
+    if twice:
+        raise ValueError(f"effect {twice[0]:g} is given more than once")
+    return out if 0.0 in out else [0.0] + out
+
+
+def power_screens(eng: HipSVI, effects, n_screens: int, power_seed: int = SEED, plant=None):
+    """``(X (D, K, R, B, G), X_bcmatch or None)``, device tensors: screen (i, j) is planted effect ``effects[i]``, draw j
+    of ``eng.simulate_power(..., plant=plant, seed=power_seed)`` whatever the batching - calls of at most ``MAX_MEMBERS``
+    screens, chunked over the effects (``D_c * K <= MAX_MEMBERS``) and, where ``K > MAX_MEMBERS``, over j with
+    ``first_draw`` advancing as ``bootstrap_screens`` advances it."""
+    from .._lib import MAX_MEMBERS
+
+    effects = [float(e) for e in effects]
+    K = int(n_screens)
+    rows_x, rows_bc = [], []
+    for j0 in range(0, K, MAX_MEMBERS):
+        k = min(MAX_MEMBERS, K - j0)
+        per_call = max(MAX_MEMBERS // k, 1)
+        xs, xbcs = [], []
+        for i0 in range(0, len(effects), per_call):
+            sim = eng.simulate_power(j0, k, effects[i0:i0 + per_call], plant=plant, seed=power_seed)
+            xs.append(sim["X"])
+            if "X_bcmatch" in sim:
+                xbcs.append(sim["X_bcmatch"])
+        rows_x.append(torch.cat(xs))
+        if xbcs:
+            rows_bc.append(torch.cat(xbcs))
+    return torch.cat(rows_x, 1), (torch.cat(rows_bc, 1) if rows_bc else None)
+
+
+def run_inference_power(model, guide, data, effects, n_screens: int = 8, seed: int = SEED, power_seed: int = SEED,
+                        plant=None, initial_lr=0.01, gamma=0.1, num_steps=2000, report_every: int = 100,
+                        verbose: bool = True, max_per_run: int = 63):
+    """Power study: fit the screen, draw ``n_screens`` screens from the fitted model on the device with each effect of
+    ``effects`` planted - ``mu_t = effect``, the value itself, on every target (or on those ``plant`` marks: T booleans)
+    - and refit every one of them with the same ``seed`` (``model/jackknife.py::power_plan``): how large must a variant's
+    effect be for this screen to have called it, and how often does a variant with no effect cross the threshold.
+
+    The screens are the parametric bootstrap's (``bootstrap_engine``: the plug-in, zero noise in every Normal site) with
+    one change: the guides of a planted target sort with the planted mean and the target's fitted ``sd``.  Screen (i, j)
+    uses the pi, Dirichlet and categorical streams of draw j of ``power_seed`` at every effect (common random numbers
+    across effects).  Masks, size factors, ``a0``, ``pi_a0``, editing rates, totals and the control allele counts are the
+    observed screen's.  The variant families share no parameter between targets, so every target is planted at once and
+    each target's refit is still its own experiment.  Effect 0 is added in front of ``effects`` where absent
+    (``power_effects``).
+
+    Returns ``(full, fits)``: ``full`` is exactly what ``run_inference(..., seed=seed)`` returns, ``fits[i][j]`` exactly
+    what it returns for the screen with the counts of effect i, draw j - bit for bit; ``fits`` follows
+    ``power_effects(effects)``.  The refits are members of one engine next to the screen, at most ``max_per_run``
+    (1 ... 63) per engine run, where the batched kernels take the shape; else one after the other (``_fit_plan``).
+    Raises ``PredictiveUnsupported`` - the message names the family - as ``run_inference_bootstrap`` does;
+    ``n_screens < 2``, no effect, an effect given twice and an effect that is not finite are each a ``ValueError``.  A
+    halt's message and dump file (``tmp_result.effect<e>_<j>.pkl``, with ``"effect": e, "screen": j``) name the screen."""
+    import dataclasses
+
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+    from .jackknife import MAX_GUIDE_POSITIONS
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _predictive_refusal(spec, data, world)
+    if why is not None:
+        raise PredictiveUnsupported(f"a power study is not available for {why}: the count simulator serves the sorting "
+                                    "variant Normal and MixtureNormal models on one GPU")
+    n_screens, per_run = int(n_screens), int(max_per_run)
+    if n_screens < 2:
+        raise ValueError(f"a power study needs at least 2 screens per effect, got {n_screens}")
+    effects = power_effects(effects)
+    if not 1 <= per_run <= MAX_GUIDE_POSITIONS:
+        raise ValueError(f"max_per_run must be in [1, {MAX_GUIDE_POSITIONS}] (the screen is member 0 of every run), "
+                         f"got {per_run}")
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+    first = run_inference(model, guide, data, seed=seed, report_every=report_every, verbose=verbose, **common)
+    eng = bootstrap_engine(model, guide, data, first[0])
+    try:
+        x, x_bc = power_screens(eng, effects, n_screens, power_seed, plant=plant)
+        torch.cuda.synchronize(eng.device)
+    finally:
+        eng.close()
+    home = lambda t, like: None if t is None else t.to(like.device, like.dtype)  # noqa: E731
+    plan = power_plan(data, seed, effects, home(x, data.X_masked),
+                      home(x_bc, data.X_bcmatch_masked) if x_bc is not None else None)
+    plan = dataclasses.replace(plan, per_run=per_run)
+    results = _fit_plan(model, guide, data, plan, common, report_every, verbose)
+    return results[0], [results[1 + i * n_screens:1 + (i + 1) * n_screens] for i in range(len(effects))]
 
 
 def identify_model_guide(args):

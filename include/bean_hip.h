@@ -465,6 +465,52 @@ int bean_hip_simulate_design(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_dr
                              int32_t n_depths, void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes,
                              void* stream);
 
+/* K replicate screens at each of D PLANTED EFFECTS in ONE launch: the screens of a power study ("how large must a
+ * variant's effect be for this screen to have called it, and how often does a null variant cross the threshold?").
+ *
+ *   bean_hip_simulate_power       takes the handles bean_hip_predictive_supported takes, any size, n_effects = D >= 1,
+ *                                 n_draws = K >= 1 and D * K <= BEAN_HIP_MAX_MEMBERS.  effects: D finite values in HOST
+ *                                 memory, copied into the launch's arguments before the call returns.  plant: a
+ *                                 DEVICE array of T bytes (non-zero: the target is planted), read by the kernel on
+ *                                 `stream`, or null: every target is planted.  x_out: (D, K, R, B, G) float32,
+ *                                 member-major with member m = i * K + j effect i, draw j - D * K members of
+ *                                 bean_hip_bind_member_counts; xbc_out: the same shape, required exactly when the
+ *                                 handle has BEAN_FLAG_USE_BCMATCH and null (0 bytes) otherwise.
+ *                                 Launches: those of bean_hip_simulate_members - one k_set_step(first_draw, slot 0,
+ *                                 n = 0), one PREP k_param - then one k_simulate_power with the member on blockIdx.y.
+ *                                 Which draw is whose: member (i, j) is member j of bean_hip_simulate_members(seed,
+ *                                 first_draw, K) - the shared Normal sites of draw first_draw (or the injected *_IN
+ *                                 values), draw index first_draw + j for its pi, Dirichlet and categorical sites AT
+ *                                 EVERY EFFECT (common random numbers across effects), BEAN_BUF_PI_IN and
+ *                                 BEAN_FLAG_DUMP_PI as there - except that a (replicate, guide) of a planted target
+ *                                 takes, wherever the table P[b, t] is read,
+ *                                     Phi((z_hi[b] - e) / sigma_t) - Phi((z_lo[b] - e) / sigma_t),   e = effects[i],
+ *                                 with sigma_t from the target's drawn y_t as the PREP launch forms it: mu_t = e, the
+ *                                 value itself and not a shift of the fitted mean.  The operations are those of the
+ *                                 PREP launch's table, so
+ *                                   (a) with nothing planted (an all-zero plant) plane (i, j) is bit for bit plane j of
+ *                                       bean_hip_simulate_members(seed, first_draw, K);
+ *                                   (b) plane (i, j) is bit for bit plane j of bean_hip_simulate_members on a twin
+ *                                       handle that is equal in everything but mu_loc = float32(e) and eps_mu = 0 on
+ *                                       the planted targets (for an e that float32 holds exactly);
+ *                                   (c) every (replicate, guide) of every plane sums to n_obs exactly;
+ *                                   (d) the (replicate, guide) pairs of unplanted targets are those of
+ *                                       bean_hip_simulate_members in every plane.
+ *                                 The variant families share no parameter between targets, so all targets may be
+ *                                 planted at once.  Cost: that of D * K members of bean_hip_simulate_members plus 2 B
+ *                                 normal CDFs per (planted pair, likelihood).  State: as bean_hip_simulate_members -
+ *                                 nothing of the fit is written, and a following bean_hip_svi_resume does not continue
+ *                                 an earlier window.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched, the handle stays usable): a null handle; a
+ * handle that is not supported (the message names bean_hip_predictive_supported) or not prepared; null effects; D < 1,
+ * K < 1 or D * K > BEAN_HIP_MAX_MEMBERS (the message states the product and the limit); an effect that is not finite
+ * (the message states its index and value); byte counts other than 4 D K R B G (the message states D and K); xbc_out on
+ * a handle without BEAN_FLAG_USE_BCMATCH or without it on a handle with the flag. */
+int bean_hip_simulate_power(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t n_draws, const double* effects,
+                            int32_t n_effects, const void* plant, void* x_out, uint64_t x_bytes, void* xbc_out,
+                            uint64_t xbc_bytes, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
