@@ -126,6 +126,17 @@ def get_parser():
                           "screens only; the --fit-negctrl control fit is not checked.  Default 0: off.")
     own.add_argument("--predictive-seed", dest="predictive_seed", type=int, default=101,
                      help="Seed of the draws of --posterior-predictive (default 101).")
+    own.add_argument("--importance-check", dest="importance_check", type=_non_negative_int, default=0, metavar="S",
+                     help="After the fit, draw S times from the fitted mean-field guide on the GPU, weight every draw per "
+                          "target by p(x, z) / q(z) and report, per target, the Pareto tail index of the weights and the "
+                          "importance-corrected posterior: columns psis_k (below 0.5 the Gaussian can be trusted for "
+                          "this target, above 0.7 it cannot be repaired at this S), mu_is / mu_sd_is (on the scale of the "
+                          "column mu), is_ess and n_is in the element table.  No refit; the other tables do not change.  "
+                          "Combines with the member flags and --load-existing: the check is of the fit the tables come "
+                          "from.  At least 25 draws; sorting variant screens only; the --fit-negctrl control fit is not "
+                          "checked.  Default 0: off.")
+    own.add_argument("--importance-seed", dest="importance_seed", type=int, default=101,
+                     help="Seed of the draws of --importance-check (default 101).")
     own.add_argument("--bootstrap", dest="bootstrap", type=_non_negative_int, default=0, metavar="K",
                      help="Parametric bootstrap: after the fit of the screen, draw K screens from the fitted model on the "
                           "GPU (mu, sd and the guide noise at their fitted locations; fresh pi, Dirichlet and count draws; "
@@ -181,12 +192,13 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    from .run import member_mode, particle_count, predictive_draws
+    from .run import importance_draws, member_mode, particle_count, predictive_draws
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
     particle_count(args, parser.error)
     predictive_draws(args, parser.error)
+    importance_draws(args, parser.error)
 
 
 def main(argv=None):

@@ -189,6 +189,29 @@ def predictive_draws(args, fail=_refuse) -> int:
     return n
 
 
+_IMPORTANCE_FAMILY = ("--importance-check weights draws of the sorting variant models (Normal, MixtureNormal) per target and "
+                      "is not available for {what}.")
+IMPORTANCE_MIN_DRAWS = 25  # model/importance.py::MIN_DRAWS: fewer draws have no tail to fit
+
+
+def importance_draws(args, fail=_refuse) -> int:
+    """``--importance-check S``: the number of draws from the fitted guide to weight after the fit (0: none).  Fewer than
+    25 and a family the per-target weights do not take are refused - ``fail(sentence)``, as ``member_mode`` - with the
+    family named."""
+    n = int(getattr(args, "importance_check", 0) or 0)
+    if n < 0:
+        fail(f"--importance-check must be >= 0, got {n}.")
+    if n == 0:
+        return 0
+    if n < IMPORTANCE_MIN_DRAWS:
+        fail(f"--importance-check needs at least {IMPORTANCE_MIN_DRAWS} draws to fit the tail of the weights, got {n}.")
+    if getattr(args, "library_design", None) == "tiling":
+        fail(_IMPORTANCE_FAMILY.format(what="tiling screens (MultiMixtureNormal)"))
+    if getattr(args, "selection", None) == "survival":
+        fail(_IMPORTANCE_FAMILY.format(what="survival screens"))
+    return n
+
+
 def check_guide_jackknife_switches(args) -> bool:
     """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
     return member_mode(args, only=("jackknife_guides",)) == "guides"
@@ -378,6 +401,13 @@ def main(args, return_data=False):
         why = model_run._predictive_refusal(model_run._resolve(model), ndata, world)
         if why is not None:
             raise PredictiveUnsupported(_PREDICTIVE_FAMILY.format(what=why))
+    n_importance = importance_draws(args)
+    if n_importance:
+        from ..engine import PredictiveUnsupported
+
+        why = model_run._predictive_refusal(model_run._resolve(model), ndata, world)
+        if why is not None:
+            raise PredictiveUnsupported(_IMPORTANCE_FAMILY.format(what=why))
     table_columns = {}
     save_dict = dict()
     param_history_dict_negctrl = None
@@ -425,6 +455,15 @@ def main(args, return_data=False):
     if args.save_raw:
         with open(f"{prefix}/{model_label}.result{args.result_suffix}.pkl", "wb") as handle:
             pkl.dump(save_dict, handle)
+    if n_importance:
+        info(f"Importance-sampling check: {n_importance} draws from the fitted guide, weighted per target...")
+        summary = model_run.run_importance_check(model, guide, ndata, param_history_dict, n_draws=n_importance,
+                                                 seed=int(getattr(args, "importance_seed", model_run.SEED)))
+        table_columns = {**table_columns, "importance": {k: v.detach().cpu() for k, v in summary.items()}}
+        k = table_columns["importance"]["psis_k"]
+        info(f"Importance-sampling check: psis_k > 0.7 on {int((k > 0.7).sum())} of {k.numel()} targets "
+             f"({100.0 * float((k > 0.7).double().mean()) if k.numel() else 0.0:.1f} %); median psis_k "
+             f"{float(k.median()) if k.numel() else float('nan'):.3f}.")
     write_result_table(
         target_info_df,
         guide_info_df,

@@ -29,6 +29,7 @@
 #include "../../include/bean_hip.h"
 #include "bean_kernels.hpp"
 #include "bean_predictive.hpp"  // replicate counts drawn on the device (bean_hip_simulate)
+#include "bean_importance.hpp"  // per-target log importance weights (bean_hip_log_weights)
 
 using namespace bean;
 
@@ -2853,6 +2854,63 @@ extern "C" int bean_hip_simulate_power(bean_hip_ctx* c, uint64_t seed, uint64_t 
     with_family_acc(d, [&](auto fam, auto acc) {
         hipLaunchKernelGGL((k_simulate_power<fam(), acc()>), grid, block, lds, stream, d, sa, pw);
     });
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ per-target log importance weights
+// (bean_importance.hpp; at the end of the file, so that every other kernel keeps its place in the code object)
+// log p(x, z) - log q(z) of draws first_draw .. first_draw + n_draws - 1 of the fitted guide, per target: draw d is the
+// draw bean_hip_elbo_grad(seed, step = d) evaluates, formed by the lanes themselves - three launches per call whatever
+// n_draws (the pairs' data-only constants, the pairs, the targets), no k_set_step, no PREP launch, nothing of the
+// workspace written.
+extern "C" int bean_hip_log_weights(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws, void* logw_out,
+                                    uint64_t logw_bytes, void* mu_out, uint64_t mu_bytes, void* y_out, uint64_t y_bytes,
+                                    void* pair_out, uint64_t pair_bytes, void* stream_) {
+    if (!c) return fail("bean_hip_log_weights: null handle");
+    if (!predictive_shape_ok(c))
+        return fail("bean_hip_log_weights: the importance weights do not take this handle "
+                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
+                    "covariates, one member, one particle");
+    if (!c->prepared) return fail("bean_hip_log_weights: call bean_hip_prepare first");
+    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_LOGW_DRAWS)
+        return fail("bean_hip_log_weights: n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) +
+                    "], got " + std::to_string(n_draws));
+    if (check_bound(c, false, false)) return -1;
+    const DevArgs& d0 = c->d;
+    const uint64_t nt = (uint64_t)n_draws * d0.T, np = (uint64_t)n_draws * d0.R * d0.G;
+    const std::string sn = " float64 with n_draws = " + std::to_string(n_draws) + ", ";
+    if (!logw_out || logw_bytes != 8 * nt)
+        return fail("bean_hip_log_weights: logw_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) + " bytes");
+    if (!mu_out || mu_bytes != 8 * nt)
+        return fail("bean_hip_log_weights: mu_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) + " bytes");
+    if (y_out ? y_bytes != 8 * nt : y_bytes != 0)
+        return fail("bean_hip_log_weights: y_out must be null or hold (n_draws, T)" + sn + std::to_string(8 * nt) +
+                    " bytes");
+    if (!pair_out || pair_bytes != 8 * np)
+        return fail("bean_hip_log_weights: pair_out (caller-owned scratch) must hold (n_draws, R, G)" + sn +
+                    std::to_string(8 * np) + " bytes");
+    hipStream_t stream = (hipStream_t)stream_;
+    c->d.seed = seed;
+    c->resume_ok = false;  // (the seed of the handle has changed)
+    const DevArgs& d = c->d;
+    LogwArgs la;
+    la.first_draw = first_draw;
+    la.n_draws = n_draws;
+    la.logw_out = (double*)logw_out;
+    la.mu_out = (double*)mu_out;
+    la.y_out = (double*)y_out;
+    la.pair_out = (double*)pair_out;
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)n_draws), block(64);
+    const size_t lds = simulate_wave2_lds(d.B);
+    const uint64_t rg = (uint64_t)d.R * d.G;
+    hipLaunchKernelGGL(k_logw_consts, dim3((unsigned)((rg + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
+                       la);
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_logw_pairs<fam(), acc()>), grid, block, lds, stream, d, la);
+    });
+    hipLaunchKernelGGL(k_logw_targets, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream,
+                       d, la);
     HIP_OK(hipGetLastError());
     return 0;
 }

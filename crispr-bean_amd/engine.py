@@ -958,6 +958,47 @@ class HipSVI:
             out["X_bcmatch"] = xbc
         return out
 
+    LOGW_PAIR_BYTES = 256 << 20  # the pair plane of one bean_hip_log_weights call stays at or below this
+
+    def log_weights(self, first_draw: int, n_draws: int, seed: int = 101, pairs: bool = False) -> Dict[str, torch.Tensor]:
+        """Per-target log importance weights of ``n_draws`` draws from the guide at the current parameters
+        (``bean_hip_log_weights``): draw ``first_draw + j`` is the draw ``elbo_grad(step=first_draw + j, seed=seed)``
+        evaluates (or, with ``set_noise``, the injected draw every time).  Returns float64 device tensors ``logw``
+        (n_draws, T) - ``log p(x_t, z_t) - log q(z_t)``, whose negative sum over targets is that ``elbo_grad``'s loss -
+        ``mu`` and ``y`` (n_draws, T), the drawn ``mu_t`` and ``log sd_t``, and with ``pairs`` the terms of every
+        (draw, replicate, guide) pair, ``pairs`` (n_draws, R, G), guides in screen order.  The draws go to the library in
+        chunks whose pair plane stays at or below 256 MiB; draw d is the same whatever the chunking.  Leaves the fit alone
+        as ``simulate`` does; the next ``run(resume=True)`` is a plain run."""
+        if not self.predictive_supported or getattr(self.lib, "bean_hip_log_weights", None) is None:
+            raise PredictiveUnsupported(f"the importance weights do not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
+                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        S = int(n_draws)
+        if S < 1:
+            raise ValueError(f"log_weights: n_draws must be at least 1, got {S}")
+        R, G, T = self.data.n_reps, self.data.n_guides, int(self.T)
+        dev = self.device
+        chunk = max(1, min(S, _lib.MAX_LOGW_DRAWS, self.LOGW_PAIR_BYTES // (8 * R * G)))
+        logw = torch.empty((S, T), dtype=torch.float64, device=dev)
+        mu = torch.empty((S, T), dtype=torch.float64, device=dev)
+        y = torch.empty((S, T), dtype=torch.float64, device=dev)
+        plane = torch.empty((S if pairs else chunk, R, G), dtype=torch.float64, device=dev)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        nb = lambda t: t.numel() * t.element_size()
+        with self._on_stream():
+            for j0 in range(0, S, chunk):
+                n = min(chunk, S - j0)
+                pl = plane[j0:j0 + n] if pairs else plane[:n]
+                lw, m, yy = logw[j0:j0 + n], mu[j0:j0 + n], y[j0:j0 + n]
+                self._check(self.lib.bean_hip_log_weights(self._h, int(seed), int(first_draw) + j0, n, ptr(lw), nb(lw),
+                                                          ptr(m), nb(m), ptr(yy), nb(yy), ptr(pl), nb(pl), self._sptr()),
+                            "log_weights")
+        self.invalidate_resume()
+        out = {"logw": logw, "mu": mu, "y": y}
+        if pairs:
+            out["pairs"] = self._to_screen_order(plane, 2)
+        return out
+
     def run_ensemble(self, n_steps: int, seeds, graph_chunk: int = 50, first_step: Optional[int] = None):
         """Enqueue ``n_steps`` SVI steps of all ``n_members`` fits, member k with ``seeds[k]`` (no host
         synchronisation).  Member k is, bit for bit, a single engine's ``run(n_steps, seed=seeds[k])``;

@@ -190,6 +190,7 @@ def write_result_table(
     bootstrap: Optional[dict] = None,
     design: Optional[dict] = None,
     power: Optional[dict] = None,
+    importance: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -233,7 +234,12 @@ def write_result_table(
     and, where negative effects were given, ``mde{...}_neg``; the summary's table - one row per effect: ``effect,
     n_screens, n_planted, power_mean, power_median, shrinkage, median_mu_power_se`` - is written next to the element
     table as ``bean_power.<model_label><suffix>.csv``, also with ``return_result``.  With ``None`` every file is byte for
-    byte what it was and no further one is written."""
+    byte what it was and no further one is written.
+
+    ``importance`` (an importance-sampling check of the guide, ``model/importance.py::importance_summary``): the element
+    table gets exactly the columns ``psis_k``, ``mu_is``, ``mu_sd_is``, ``is_ess`` and ``n_is`` (``mu_is`` / ``mu_sd_is``
+    on the scale of ``mu``, not rescaled), after those of a member set; every other column and the sgRNA table are those
+    of the run without it, and with ``None`` every file is byte for byte what it was."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -278,6 +284,9 @@ def write_result_table(
         element[mde] = _flat(power["mde"])
         if "mde_neg" in power:
             element[mde + "_neg"] = _flat(power["mde_neg"])
+    if importance is not None:
+        _add_summary_columns(element, importance, "the importance-sampling summary",
+                             ("psis_k", "mu_is", "mu_sd_is", "is_ess"), None, "n_is", count_per_target=True)
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

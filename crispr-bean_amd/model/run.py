@@ -463,6 +463,36 @@ def run_posterior_predictive(model, guide, data, param_store, n_draws: int = 200
     return summary
 
 
+def run_importance_check(model, guide, data, param_store, n_draws: int = 1000, seed: int = SEED):
+    """Importance-sampling check of a fit's mean-field posterior (``model/importance.py``): an engine for ``data`` with
+    the fitted parameters of ``param_store`` loaded, ``n_draws`` draws from the guide weighted per target by
+    ``p(x, z) / q(z)`` on the device, and their summary - per target ``psis_k``, ``is_ess``, ``mu_is``, ``mu_sd_is``,
+    ``n_is`` (a dict of device tensors).  No refit.
+
+    Raises ``PredictiveUnsupported`` - the message names the family - for tiling and survival screens,
+    ``ControlNormal``, sample covariates and several ranks."""
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+    from .importance import importance_check
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _predictive_refusal(spec, data, world)
+    if why is not None:
+        raise PredictiveUnsupported(f"an importance-sampling check is not available for {why}: the per-target weights "
+                                    "serve the sorting variant Normal and MixtureNormal models on one GPU")
+    device = torch.device("cuda", torch.cuda.current_device())
+    eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
+    try:
+        load_parameters(eng, param_store)
+        summary = importance_check(eng, n_draws=n_draws, seed=seed)
+        torch.cuda.synchronize(device)
+    finally:
+        eng.close()
+    return summary
+
+
 def bootstrap_engine(model, guide, data, param_store) -> HipSVI:
     """The engine a parametric bootstrap draws its screens from: built for ``data`` as ``run_posterior_predictive``
     builds its own, the fitted parameters of ``param_store`` loaded, and zero standard-normal draws injected into every

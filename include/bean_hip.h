@@ -511,6 +511,42 @@ int bean_hip_simulate_power(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_dra
                             int32_t n_effects, const void* plant, void* x_out, uint64_t x_bytes, void* xbc_out,
                             uint64_t xbc_bytes, void* stream);
 
+/* Per-target log importance weights of S draws from the fitted guide: the device side of the importance-sampling check
+ * of the mean-field posterior (PSIS k-hat, importance-corrected mu and mu_sd per target).
+ *
+ *   bean_hip_log_weights          takes the handles bean_hip_predictive_supported takes, any size, n_draws in
+ *                                 [1, BEAN_HIP_MAX_LOGW_DRAWS].  For j < n_draws, draw d = first_draw + j is the draw
+ *                                 bean_hip_elbo_grad(seed, step = d) evaluates - same sites, counters, operands and bits,
+ *                                 the injected BEAN_BUF_*_IN values honoured (every draw of the call is then the same
+ *                                 draw) - and
+ *                                     logw_out[j, t] = log p(x_t, z_t) - log q(z_t)
+ *                                 of target t: its mu and sd sites, its guides' pi (and, with accessibility, noise)
+ *                                 sites, and the likelihood terms of its (replicate, guide) pairs, data-only constants
+ *                                 included, so that  - sum_t logw_out[j, t]  is the loss bean_hip_elbo_grad reports for
+ *                                 that draw.  mu_out[j, t] / y_out[j, t]: the drawn mu_t and y_t = log sd_t (y_out may
+ *                                 be null with 0 bytes).  pair_out: caller-owned scratch of (n_draws, R, G) float64,
+ *                                 required; after the call it holds the terms of every (draw, replicate, guide) pair -
+ *                                 the two Dirichlet-Multinomial log-probabilities (under the repguide mask and
+ *                                 n > mask_thres), the control-allele Multinomial, log p(pi) under the repguide mask and
+ *                                 - log q(pi), without the per-guide Dirichlet normalisers.  Guides in the handle's
+ *                                 order.  All four arrays are DEVICE memory, float64, draw-major.
+ *                                 Launches: one k_logw_consts (the pairs' data-only constants, once per call), one
+ *                                 k_logw_pairs (grid of k_simulate_members, the draw on blockIdx.y) and one
+ *                                 k_logw_targets, whatever n_draws; no k_set_step, no k_param.
+ *                                 State: parameters, moments, gradients, loss_hist and the workspace are not written;
+ *                                 the handle's seed is, so a following bean_hip_svi_resume does not continue an earlier
+ *                                 window.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched, the handle stays usable): a null handle; a
+ * handle that is not supported (the message names bean_hip_predictive_supported) or not prepared; n_draws outside
+ * [1, BEAN_HIP_MAX_LOGW_DRAWS] (the message states the range); a null logw_out, mu_out or pair_out; byte counts other
+ * than 8 n_draws T (logw_out, mu_out, a non-null y_out), 0 (a null y_out) and 8 n_draws R G (pair_out) - the message
+ * states n_draws and the bytes expected. */
+#define BEAN_HIP_MAX_LOGW_DRAWS 4096
+int bean_hip_log_weights(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t n_draws, void* logw_out,
+                         uint64_t logw_bytes, void* mu_out, uint64_t mu_bytes, void* y_out, uint64_t y_bytes,
+                         void* pair_out, uint64_t pair_bytes, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
