@@ -289,16 +289,24 @@ __device__ __forceinline__ unsigned long long guide_stream_id(const DevArgs& c, 
 // Every wave / block adds its part of the step's loss with INTEGER atomics: the part is split exactly
 // into a multiple of 2^-10 and a remainder rounded to 2^-40, so the sum does not depend on the order
 // in which the parts arrive and the loss history is bitwise reproducible (a float64 atomicAdd is not).
-// Range: |part| < 2^33 (kLossPartMax), |loss| < 2^52; resolution 2^-40.  One address would serialise the chip's ~4000 waves at ~12 ns
+// Range: |part| < 2^40 (kLossPartMax), |loss| < 2^52; resolution 2^-40.  One address would serialise the chip's ~4000 waves at ~12 ns
 // per atomic (tens of microseconds per launch - measured: it dominated the guide kernel), so a slot is
 // kLossSub accumulators in separate 64-byte lines and a part goes to the one its block id selects;
 // integer sums make the choice irrelevant for the result.  k_loss_finalize adds them up into the
 // double in loss_hist.
 constexpr int kLossWords = 8;   // int64 words per accumulator line: 2^-10 units, 2^-40 units, poison count
-// Largest part a wave / block may add: its 2^-10-unit word is < 2^43, so 2^20 parts (a 13 M (replicate, guide)
-// screen has that many waves) cannot wrap the int64 sum; a part beyond it - a diverging fit - poisons the slot
-// and the reported loss is NaN (the host halts the fit at the next report), instead of a finite wrong value.
-constexpr double kLossPartMax = 8589934592.0;  // 2^33
+// Largest part a wave / block may add; a part beyond it - a diverging fit - poisons the slot and the reported loss
+// is NaN (the host halts the fit at the next report), instead of a finite wrong value.  What the data can ask for: a
+// (replicate, guide) pair at the count simulator's clamp of 2^24 - 1 reads holds |sum_b D(a_b, x_b)| and
+// |lgamma(1 + n) - sum_b lgamma(1 + x_b)| of up to n log(a0 + n) = 2.8e8 per likelihood, 2^29 with both; a wave of
+// 64 such pairs adds 2^35, a 256-thread block (k_prepare's constant, the block forms) 2^37.  The bound this had,
+// 2^33, made every loss of a depth study's deepest refits NaN - gradients and parameters were right, the host halted
+// the fit (tests/test_gpu_count_regimes.py).  The integer sums are modular, so they are exact whenever the true total
+// fits: with parts below 2^40 the 2^-10-unit word is below 2^50 and 2^13 parts of the LARGEST size cannot wrap it, and
+// parts of that size exist only where the counts make them - the parts of a screen add up to less than 2^29 per pair,
+// below 2^53 for every screen of fewer than 2^24 pairs, however they are grouped.  Parts below 2^33 take the path
+// they took: the same words, the same loss bits.
+constexpr double kLossPartMax = 1099511627776.0;  // 2^40
 constexpr int kLossSub = 64;    // accumulator lines per loss_hist slot
 __device__ __forceinline__ void fixed_add(long long* acc, double v) {
     if (!(fabs(v) < kLossPartMax)) {  // NaN / inf / out of range: poison the slot (k_loss_finalize reports NaN)

@@ -10,6 +10,7 @@ emit float32 gradients (as the reference's autograd does for float32 leaves), so
 import ast
 import os
 
+import mpmath
 import numpy as np
 import pytest
 import scipy.special as sp
@@ -80,6 +81,118 @@ def test_lgamma_digamma_and_phi(engine):
     u = rng.normal(0, 3, 100_000)
     phi, _ = engine.test_special(3, u)
     assert np.max(np.abs(phi.cpu().numpy() - st.norm.cdf(u))) < 1e-15
+
+
+# The domain a depth study's refits reach: counts up to the simulator's clamp of 2^24 - 1 per pair
+# against concentrations of 1e-5 (get_alpha's clamp) ... 1e7, with the branch edges of lgamma_digamma_diff_inl planted.
+CAP = float((1 << 24) - 1)
+EDGE_X = (1.0, 2.0, 11.0, 12.0, 13.0, 14.0, CAP)                              # product form | series at 12 | 13
+EDGE_A = (1e-5, float(np.nextafter(6.0, 0.0)), 6.0, float(np.nextafter(10.0, 0.0)), 10.0, 1e7)  # kShiftLo, kShift
+N_WIDE = 6000
+N_DEEP_WAVES = 32  # the first 32 waves of 64 hold x > 12 in every lane: lgamma_digamma_diff2's two-chain form
+
+
+def wide_domain_inputs():
+    """(a, x, sum10): 6 000 points, a log-uniform on [1e-5, 1e7], x an integer log-uniform on [1, 2^24 - 1].  Elements
+    0 ... 2047 are whole waves with every x > 12 and hold EDGE_A x {13, 14, 2^24 - 1}; the waves after them mix counts on
+    both sides of 12 and hold EDGE_A x EDGE_X and, with non-integer x (the series branch with a second argument that
+    needs its shift), pairs whose a + x is the double just below 10 and exactly 10 (`sum10`: their indices)."""
+    rng = np.random.default_rng(11)
+    n, deep = N_WIDE, 64 * N_DEEP_WAVES
+    a = np.exp(rng.uniform(np.log(1e-5), np.log(1e7), n))
+    x = np.clip(np.floor(np.exp(rng.uniform(0.0, np.log(CAP), n))), 1.0, CAP)
+    x[:deep] = np.maximum(x[:deep], 13.0)
+    i = 5
+    for av in EDGE_A:
+        for xv in EDGE_X[4:]:
+            a[i], x[i] = av, xv
+            i += 37  # spread over the deep waves, odd and even lanes (op 5 pairs element i with i ^ 1)
+    assert i < deep
+    i = deep + 3
+    for av in EDGE_A:
+        for xv in EDGE_X:
+            a[i], x[i] = av, xv
+            i += 41
+    sum10 = []
+    for av in (0.37, 3.25, 5.75, 6.5, 7.5):  # shifts of the first argument: six, three, one, none, none
+        at = 10.0 - av
+        while av + at < 10.0:
+            at = float(np.nextafter(at, np.inf))
+        assert av + at == 10.0 and at != np.floor(at)
+        below = at
+        while av + below >= 10.0:
+            below = float(np.nextafter(below, 0.0))
+        assert av + below == float(np.nextafter(10.0, 0.0))
+        for xv in (below, at):
+            a[i], x[i] = av, xv
+            sum10.append(i)
+            i += 41
+    assert i < n and x[:deep].min() > 12 and (x[deep:] <= 12).sum() > 500
+    return a, x, np.array(sum10)
+
+
+def mp_differences(a, x, dps=50):
+    """lgamma(a + x) - lgamma(a), digamma(a + x) - digamma(a) and |lgamma(a + x)| + |lgamma(a)|, formed at `dps` digits
+    from the float64 inputs: exact to float64, so the reference needs no cancellation allowance."""
+    d, dp, mag = np.empty(len(a)), np.empty(len(a)), np.empty(len(a))
+    with mpmath.workdps(dps):
+        for i, (av, xv) in enumerate(zip(a, x)):
+            am, zm = mpmath.mpf(float(av)), mpmath.mpf(float(av)) + mpmath.mpf(float(xv))
+            l2, l1 = mpmath.loggamma(zm), mpmath.loggamma(am)
+            d[i], dp[i], mag[i] = float(l2 - l1), float(mpmath.digamma(zm) - mpmath.digamma(am)), float(abs(l2) + abs(l1))
+    return d, dp, mag
+
+
+def wide_domain_rules(ref_d, ref_dp, mag):
+    """The allowances of the two outputs: 1e-13 relative on d plus the rounding of the Stirling head's two products
+    (8 eps of their magnitudes: what test_lgamma_digamma_differences grants); 1e-12 relative on dp, the constant
+    grad_bounds.C_DIGAMMA rests on, with no allowance at all."""
+    eps = np.finfo(float).eps
+    return 1e-13 * np.maximum(1.0, np.abs(ref_d)) + 8 * eps * mag, 1e-12 * np.maximum(1.0, np.abs(ref_dp))
+
+
+def test_lgamma_digamma_differences_on_the_depth_study_domain(engine):
+    a, x, sum10 = wide_domain_inputs()
+    d, dp = (t.cpu().numpy() for t in engine.test_special(0, a, x))
+    ref_d, ref_dp, mag = mp_differences(a, x)
+    tol_d, tol_dp = wide_domain_rules(ref_d, ref_dp, mag)
+    r_d, r_dp = np.abs(d - ref_d) / tol_d, np.abs(dp - ref_dp) / tol_dp
+    i, j = int(np.argmax(r_d)), int(np.argmax(r_dp))
+    print(f"WIDE DOMAIN d: worst err / rule {r_d[i]:.4f} at a = {a[i]!r}, x = {x[i]!r}; "
+          f"dp: worst err / rule {r_dp[j]:.4f} at a = {a[j]!r}, x = {x[j]!r}; "
+          f"at a + x = 10 | just below: d {r_d[sum10].max():.4f}, dp {r_dp[sum10].max():.4f}")
+    bad = np.nonzero((r_d > 1) | (r_dp > 1) | ~np.isfinite(d) | ~np.isfinite(dp))[0]
+    assert bad.size == 0, [(float(a[k]), float(x[k]), float(r_d[k]), float(r_dp[k])) for k in bad[:20]]
+
+
+def test_two_chain_difference_is_bitwise_the_one_chain_function_on_the_depth_study_domain(engine):
+    """The property of test_two_chain_difference_is_bitwise_the_one_chain_function for counts up to 2^24 - 1: the first
+    32 waves hold x > 12 in every lane and take the two-chain form (every planted a among them), the others mix."""
+    a, x, _ = wide_domain_inputs()
+    waves = x[: 64 * (N_WIDE // 64)].reshape(-1, 64)
+    all_deep = (waves > 12).all(1)
+    assert all_deep[:N_DEEP_WAVES].all() and (~all_deep[N_DEEP_WAVES:]).sum() >= 50
+    d1, p1 = engine.test_special(0, a, x)
+    d2, p2 = engine.test_special(5, a, x)
+    assert torch.equal(d1.view(torch.int64), d2.view(torch.int64))
+    assert torch.equal(p1.view(torch.int64), p2.view(torch.int64))
+
+
+def test_lgamma_digamma_up_to_the_largest_second_argument(engine):
+    """lgamma / digamma (op 1) up to 2e7, the largest a + x, against 50 digits at the 1e-13 relative of
+    test_lgamma_digamma_and_phi."""
+    rng = np.random.default_rng(12)
+    z = np.exp(rng.uniform(np.log(1e-5), np.log(2e7), 4000))
+    z[:8] = (1e-5, 6.0, float(np.nextafter(10.0, 0.0)), 10.0, CAP, CAP + 1e-5, 1e7 + CAP, 2e7)
+    lg, dg = (t.cpu().numpy() for t in engine.test_special(1, z))
+    with mpmath.workdps(50):
+        ref_lg = np.array([float(mpmath.loggamma(mpmath.mpf(float(v)))) for v in z])
+        ref_dg = np.array([float(mpmath.digamma(mpmath.mpf(float(v)))) for v in z])
+    r_lg = np.abs(lg - ref_lg) / np.maximum(1.0, np.abs(ref_lg))
+    r_dg = np.abs(dg - ref_dg) / np.maximum(1.0, np.abs(ref_dg))
+    print(f"WIDE DOMAIN lgamma: worst relative error {r_lg.max():.3e} at {z[int(np.argmax(r_lg))]!r}; "
+          f"digamma: {r_dg.max():.3e} at {z[int(np.argmax(r_dg))]!r}")
+    assert r_lg.max() < 1e-13 and r_dg.max() < 1e-13
 
 
 def test_dirichlet_grad_matches_torch(engine):
