@@ -15,8 +15,9 @@ test inject the random draws (standard-normal ``eps_*`` and the Dirichlet sample
 """
 from __future__ import annotations
 
+import contextlib
 import math
-from typing import Dict, Optional
+from typing import Callable, Dict, Optional
 
 import torch
 import torch.distributions as tdist
@@ -45,21 +46,39 @@ def dirichlet_multinomial_log_prob(conc: torch.Tensor, value: torch.Tensor):
     return log_beta_1(conc.sum(-1), value.sum(-1)) - log_beta_1(conc, value).sum(-1)
 
 
+_implicit_grad: Optional[Callable] = None  # set by ``implicit_gradient``; None: torch._dirichlet_grad
+
+
+@contextlib.contextmanager
+def implicit_gradient(fn: Optional[Callable]):
+    """Inside the block every supplied Dirichlet draw takes ``fn(x, concentration, total)`` (the signature of
+    ``torch._dirichlet_grad``) as its implicit gradient - for concentrations at which torch's own evaluation cannot
+    serve as a reference.  A draw keeps the function it was made under when its backward runs later."""
+    global _implicit_grad
+    saved, _implicit_grad = _implicit_grad, fn
+    try:
+        yield
+    finally:
+        _implicit_grad = saved
+
+
 class _DirichletGivenSample(torch.autograd.Function):
     """Identity on a supplied Dirichlet draw ``x`` whose backward is the implicit
     reparameterisation gradient torch uses for ``Dirichlet.rsample``
-    (``torch/distributions/dirichlet.py:17-36``)."""
+    (``torch/distributions/dirichlet.py:17-36``), or the one ``implicit_gradient``
+    names."""
 
     @staticmethod
     def forward(ctx, concentration, x):
         ctx.save_for_backward(x, concentration)
+        ctx.implicit_grad = _implicit_grad
         return x.clone()
 
     @staticmethod
     def backward(ctx, grad_output):
         x, concentration = ctx.saved_tensors
         total = concentration.sum(-1, True).expand_as(concentration)
-        grad = torch._dirichlet_grad(x, concentration, total)
+        grad = (ctx.implicit_grad or torch._dirichlet_grad)(x, concentration, total)
         return grad * (grad_output - (x * grad_output).sum(-1, True)), None
 
 

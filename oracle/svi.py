@@ -12,10 +12,13 @@ step and parameter: ``lr *= lrd``; ``grad.clamp_(-clip, clip)`` with
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Callable, Dict, List, Optional
 
 import torch
+
+from . import elbo as _elbo
 
 
 class ClippedAdam:
@@ -54,13 +57,15 @@ def svi_step(loss_fn: Callable, data, params, optim: ClippedAdam, noise=None, **
     return float(loss.detach())
 
 
-def loss_and_grads(loss_fn: Callable, data, params, noise=None, **kw):
-    """Loss and d loss / d (unconstrained params) for one noise draw."""
+def loss_and_grads(loss_fn: Callable, data, params, noise=None, dirichlet_grad: Optional[Callable] = None, **kw):
+    """Loss and d loss / d (unconstrained params) for one noise draw.  ``dirichlet_grad`` replaces
+    ``torch._dirichlet_grad`` as the implicit gradient of the supplied Dirichlet draws (``elbo.implicit_gradient``)."""
     for p in params.values():
         p.grad = None
     rec = {}
-    loss = loss_fn(data, params, noise=noise, record=rec, **kw)
-    loss.backward()
+    with (_elbo.implicit_gradient(dirichlet_grad) if dirichlet_grad is not None else contextlib.nullcontext()):
+        loss = loss_fn(data, params, noise=noise, record=rec, **kw)
+        loss.backward()
     grads = {k: (p.grad.clone() if p.grad is not None else torch.zeros_like(p)) for k, p in params.items()}
     return float(loss.detach()), grads, rec
 

@@ -24,8 +24,13 @@ barcode-matched plane is ``floor(0.8 X + 0.5)``.
 ``generated_deep(maker, **gen_kw)`` is no rewrite: the generator itself at ``depth_per_guide = 2e5`` (pair totals of
 1e6 ... 4e6, a refitted ``a0`` of 1.5e4 ... 1e6 - both arguments of the count likelihood large).  Its ``pi_a0`` is
 clamped to ``PI_A0_MAX = 2e3``: the generators give up to 7e4 there, and above concentrations of 2e3 torch's implicit
-Dirichlet gradient - the oracle's - moves by up to 8e-7 relative when an input moves by one ulp, so it cannot serve as
-the reference, and the constants of grad_bounds.py were pinned on [1e-3, 2e3] only.
+Dirichlet gradient - the oracle's - is up to 6e-8 off the formula it evaluates (1e-5 in the small-beta series: its own
+rounding inside cancelling intermediates, tests/dirichlet_grad_reference.py), so it cannot serve as the reference, and
+the constants of grad_bounds.py were pinned on [1e-3, 2e3] only.
+
+``generated_deep_unclamped(maker, **gen_kw)`` is that screen with ``pi_a0`` as the generator gives it.  Its tests take
+``dirichlet_grad_reference.port64`` as the oracle's implicit gradient and hold each evaluation to the error budget of
+its own inputs (tests/dirichlet_grad_reference.py) in place of the two pathwise constants.
 """
 from __future__ import annotations
 
@@ -150,10 +155,18 @@ def generated_deep(maker, **gen_kw):
     return data
 
 
+def generated_deep_unclamped(maker, **gen_kw):
+    """The generator's own screen at ``DEEP_DEPTH`` reads per guide, ``pi_a0`` as generated (up to 7e4)."""
+    return maker(**dict(gen_kw, depth_per_guide=DEEP_DEPTH))
+
+
 def regime_screen(maker, gen_kw, regime: str):
-    """The screen of a regime name: one of ``REGIMES`` rewrites ``maker(**gen_kw)``, ``generated_deep`` generates."""
+    """The screen of a regime name: one of ``REGIMES`` rewrites ``maker(**gen_kw)``, ``generated_deep`` and
+    ``generated_deep_unclamped`` generate."""
     if regime == "generated_deep":
         return generated_deep(maker, **gen_kw)
+    if regime == "generated_deep_unclamped":
+        return generated_deep_unclamped(maker, **gen_kw)
     return rewrite_counts(maker(**gen_kw), regime)
 
 

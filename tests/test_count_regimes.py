@@ -10,6 +10,7 @@ import torch
 
 import bean_amd  # noqa: F401
 import count_regimes as cr
+import dirichlet_grad_reference as dgr
 import grad_bounds as gb
 from bean_amd.preprocessing.synthetic import (make_sorting_tiling_screen, make_sorting_variant_screen,
                                               make_survival_tiling_screen, make_survival_variant_screen)
@@ -143,9 +144,9 @@ def test_generated_deep_has_both_arguments_large(kind):
 
 
 # ---------------------------------------------------------------- the oracle and its tolerance on these planes
-def _evaluation(base, kind, regime):
+def _evaluation(base, kind, regime, **bounds_kw):
     _, _, family, mod = KINDS[kind]
-    data = _screen(base, kind, regime)
+    data = cr.regime_screen(*KINDS[kind][:2], regime) if regime == "generated_deep_unclamped" else _screen(base, kind, regime)
     g = torch.Generator().manual_seed(7)
     params = {k: (v.detach() + 0.3 * torch.randn(v.shape, generator=g)).float()
               for k, v in mod.init_params(family, data).items()}
@@ -154,7 +155,59 @@ def _evaluation(base, kind, regime):
         params["alpha_pi"] = torch.where(data.allele_mask, params["alpha_pi"], start)
     noise = cr.host_noise(kind, data, params)
     d64 = elbo.as_float64(data)
-    return d64, params, noise, gb.elementwise_bounds(LOSS[kind], d64, params, noise, {})
+    return d64, params, noise, gb.elementwise_bounds(LOSS[kind], d64, params, noise, {}, **bounds_kw)
+
+
+@pytest.mark.parametrize("kind", ["variant", "tiling", "survival"])
+def test_the_unclamped_screen_is_held_by_each_evaluations_own_budget(base, kind):
+    """generated_deep_unclamped: pi_a0 as generated, at least a quarter of the implicit-gradient evaluations with a
+    concentration above 2e3; with port64 as the oracle's implicit gradient and the per-evaluation allowance, tol and
+    tol_tail are one finite array, the oracle with torch's implicit gradient lies within it (torch is within K of the
+    same budget, K below the device's), and the typical element is still held to better than 1e-5 of itself."""
+    k_dev, seen = dgr.device_k(), []
+    d64, params, noise, (loss, ref, tol, tol_tail) = _evaluation(
+        base, kind, "generated_deep_unclamped", dirichlet_grad=dgr.port64_torch, path_allowance=dgr.path_allowance(k_dev, seen))
+    assert float(d64.pi_a0.max()) > cr.PI_A0_MAX
+    al, tot = (np.concatenate([s[i] for s in seen]) for i in (1, 2))
+    high = np.maximum(al, tot - al) > cr.PI_A0_MAX
+    print(f"UNCLAMPED {kind}: pi_a0 {float(d64.pi_a0.min()):.3g} ... {float(d64.pi_a0.max()):.3g}, {int(high.sum())} of "
+          f"{high.size} evaluations above 2e3")
+    assert high.mean() >= 0.25
+    loss_t, ref_t, _, _ = gb.elementwise_bounds(LOSS[kind], d64, params, noise, {})
+    assert loss_t == loss
+    for k, r in ref.items():
+        assert np.isfinite(r).all() and np.isfinite(tol[k]).all() and np.array_equal(tol[k], tol_tail[k]), k
+        assert np.all(np.abs(ref_t[k] - r) <= tol[k]), k
+        live = r != 0
+        assert float(np.median(tol[k][live] / np.abs(r[live]))) < 1e-5, k
+
+
+@pytest.mark.parametrize("kind", ["variant", "tiling", "survival"])
+def test_a_float32_exponential_of_the_concentrations_parameters_moves_tiling_alpha_pi_alone(base, kind):
+    """The kernels take `alpha = (double)expf(alpha_pi)` (and q0 likewise) in float32, as the reference's float32
+    parameters do; the float64 oracle takes the exponential in float64.  On the unclamped screen, with the
+    per-evaluation allowance, the oracle at float32-exponentiated parameters stays within `tol_k` of itself in the variant
+    and survival cases (2 alleles: the gradient is one product, moved by 2^-24 of itself) and leaves it in a few elements
+    of tiling `alpha_pi` (5 alleles: `c_k (G_k - sum_a w_a G_a)` cancels) - which is why
+    test_every_gradient_element_matches_the_oracle_above_2e3 (tests/test_gpu_count_regimes.py) evaluates the oracle at
+    the kernels' constrained values.  No other tensor moves at all."""
+    k_dev = dgr.device_k()
+    bounds_kw = dict(dirichlet_grad=dgr.port64_torch, path_allowance=dgr.path_allowance(k_dev))
+    d64, params, noise, (loss, ref, tol, _) = _evaluation(base, kind, "generated_deep_unclamped", **bounds_kw)
+    as_kernels = {k: v.double() for k, v in params.items()}
+    for k in ("alpha_pi", "q0"):
+        if k in params:
+            as_kernels[k] = params[k].float().exp().double().log()  # exp of it in float64 is the float32 exponential
+    _, moved, _, _ = gb.elementwise_bounds(LOSS[kind], d64, as_kernels, noise, {}, dirichlet_grad=dgr.port64_torch)
+    for k, r in ref.items():
+        ratio = np.abs(moved[k] - r) / np.where(tol[k] > 0, tol[k], 1.0)
+        print(f"FLOAT32 EXP {kind} {k}: worst |moved - ref| / tol {ratio.max():.3f}, {int((ratio > 1).sum())} of {ratio.size} beyond")
+        if k not in ("alpha_pi", "q0"):
+            assert ratio.max() < 1e-3, k
+        elif kind == "tiling":
+            assert 0 < (ratio > 1).sum() < 0.05 * ratio.size, k
+        else:
+            assert ratio.max() < 1.0, k
 
 
 @pytest.mark.parametrize("regime", ALL_REGIMES)

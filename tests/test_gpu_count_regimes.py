@@ -13,6 +13,7 @@ import torch
 
 import bean_amd  # noqa: F401
 import count_regimes as cr
+import dirichlet_grad_reference as dgr
 from bean_amd.preprocessing.synthetic import make_sorting_variant_screen
 from members_common import SEED, STEPS, _assert_same, _single, _state
 from oracle import elbo
@@ -63,6 +64,51 @@ def test_every_gradient_element_matches_the_oracle_on_the_plane(engine, shape, r
     kind, gen_kw, kw, kernel, family, loss_fn = SHAPES[shape]
     data = cr.regime_screen(MAKERS[kind], gen_kw, regime)
     evaluate(engine, f"{shape}@{regime}", point, kind, data, kw, kernel, family=family, loss_fn=loss_fn)
+
+
+# generated deep with pi_a0 as generated (up to 7e4): above concentrations of 2e3 torch's implicit gradient is up to 3e-7 off
+# its own formula, so the oracle takes dirichlet_grad_reference.port64, and each evaluation's share
+# of the tolerance is K_dev (2^-52 |g| + budget) at its own inputs - the rule test_dirichlet_grad_matches_its_formula
+# (tests/test_gpu_parity.py) holds the device function to - in place of the constants pinned on [1e-3, 2e3]
+UNCLAMPED = ("variant_130x2", "tiling_130x2_a5", "survival_130x2")
+
+
+def constrained_as_the_kernels(params):
+    """The parameters at which the float64 oracle constrains `alpha_pi` and `q0` to the values the kernels use: they form
+    `(double)expf(theta)`, a float32 exponential - as the reference's float32 parameters do - where the oracle's float64
+    mode takes `exp` in float64.  The float32 exponential is taken on the device; its log in float64 is handed to the
+    oracle, whose `exp` returns it (d alpha / d theta = alpha on both sides)."""
+    out = dict(params)
+    for k in ("alpha_pi", "q0"):
+        if k in params:
+            out[k] = torch.exp(params[k].float().to(DEV)).double().log().cpu()
+    return out
+
+
+@pytest.mark.parametrize("shape", UNCLAMPED)
+def test_every_gradient_element_matches_the_oracle_above_2e3(engine, shape):
+    """The oracle is evaluated at `constrained_as_the_kernels`.  Measured, one MI355X: every tensor of the three
+    cases at 0.40 ... 0.49 of `tol_k` (tiling `alpha_pi` 0.45).  With the oracle's own float64 exponential the
+    variant and survival cases are where they are now, and `tiling_130x2_a5` has 3 of its 650 `alpha_pi` elements
+    beyond `tol_k`, the worst 3.17 `tol_k` at (51, 2) (ref 249.0511, got 249.0520, in a tensor whose median
+    |element| is 4e4): up to a float32 ulp in every alpha, which the gradient `c_k (G_k - sum_a w_a G_a)` of a guide
+    with five alleles amplifies by |G| / |G_k - mean| (with two alleles it is one product).
+    tests/test_count_regimes.py shows the same on the host.  The pathwise constants absorb it in the clamped cases
+    (`generated_deep` tiling needs its tail constant for it); the per-evaluation allowance has no room for it, and
+    it is no error of the kernels - the reference's float32 parameters are constrained in float32 too (DESIGN.md
+    section 5)."""
+    kind, gen_kw, kw, kernel, family, loss_fn = SHAPES[shape]
+    data = cr.regime_screen(MAKERS[kind], gen_kw, "generated_deep_unclamped")
+    assert float(data.pi_a0.max()) > cr.PI_A0_MAX
+    seen = []
+    evaluate(engine, f"{shape}@generated_deep_unclamped", "perturbed", kind, data, kw, kernel, family=family, loss_fn=loss_fn,
+             oracle_params=constrained_as_the_kernels, dirichlet_grad=dgr.port64_torch,
+             path_allowance=dgr.path_allowance(dgr.device_k(), seen))
+    al, tot, br = (np.concatenate([s[i] for s in seen]) for i in (1, 2, 3))
+    high = np.maximum(al, tot - al) > cr.PI_A0_MAX
+    print(f"ABOVE 2e3 {shape}: {int(high.sum())} of {high.size} evaluations hold a concentration above 2e3; branches " +
+          ", ".join(f"{b} {int(n)}" for b, n in zip(dgr.BRANCHES, np.bincount(br, minlength=5))))
+    assert high.mean() >= 0.25, (shape, float(high.mean()))
 
 
 def test_edges_with_fifteen_bins(engine):

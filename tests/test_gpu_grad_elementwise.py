@@ -130,9 +130,13 @@ def run_case(engine, monkeypatch, name, point):
     evaluate(engine, name, point, kind, MAKERS[kind](**gen_kw), kw, kernel, variant)
 
 
-def evaluate(engine, name, point, kind, data, kw, kernel, variant=None, family=None, loss_fn=None):
+def evaluate(engine, name, point, kind, data, kw, kernel, variant=None, family=None, loss_fn=None, oracle_params=None,
+             **bounds_kw):
     """One evaluation of the screen `data` at `point` against the oracle: the kernel (where one is named), the loss to
-    1e-9, every gradient element within its tolerance.  `family` / `loss_fn` default to the mixture family of `kind`."""
+    1e-9, every gradient element within its tolerance.  `family` / `loss_fn` default to the mixture family of `kind`;
+    `bounds_kw` goes to grad_bounds.elementwise_bounds (another implicit gradient for the oracle, a per-evaluation
+    allowance in place of the pathwise constants: then no element has a tail constant, and one beyond `tol` fails);
+    `oracle_params` maps the point's float32 parameters to the ones the oracle is evaluated at."""
     family, loss_fn = family or FAMILY[kind], loss_fn or LOSS[kind]
     extra = dict(lib_variant=variant) if variant else {}
     eng = engine.HipSVI(family, data.to(DEV), dump_noise=True, num_steps=50, **kw, **extra)
@@ -145,7 +149,8 @@ def evaluate(engine, name, point, kind, data, kw, kernel, variant=None, family=N
     draws = {k: v.cpu() for k, v in eng.drawn_noise().items()}
     eng.close()
     assert np.isfinite(loss)
-    ref_loss, ref, tol, tol_tail = gb.elementwise_bounds(loss_fn, elbo.as_float64(data), params, draws, kw)
+    at = params if oracle_params is None else oracle_params(params)
+    ref_loss, ref, tol, tol_tail = gb.elementwise_bounds(loss_fn, elbo.as_float64(data), at, draws, kw, **bounds_kw)
     print(f"LOSS {name} {point}: |loss - ref| / |ref| {abs(loss - ref_loss) / abs(ref_loss):.3e}")
     assert abs(loss - ref_loss) <= 1e-9 * abs(ref_loss), (name, point, loss, ref_loss)
     if "alpha_pi" not in params:  # the Normal family: no Dirichlet site in the guide, no implicit gradient

@@ -18,6 +18,7 @@ import scipy.stats as st
 import torch
 
 import bean_amd  # noqa: F401
+import dirichlet_grad_reference as dgr
 from bean_amd.preprocessing.synthetic import DEFAULT_BINS, make_sorting_variant_screen
 from oracle import elbo, svi
 
@@ -210,6 +211,55 @@ def test_dirichlet_grad_matches_torch(engine):
     # rounding sensitivity, so bound the tail loosely and the bulk tightly
     assert rel.max() < 1e-6, rel.max()
     assert np.quantile(rel, 0.9) < 1e-12 and np.quantile(rel, 0.999) < 1e-8
+
+
+# The implicit gradient against its exact formula on tests/golden/dirichlet_grad_cases.npz: concentrations of 1e-5 ... 1e5,
+# draws on the kernels' clamps, every branch edge planted (tests/dirichlet_grad_reference.py).
+@pytest.fixture(scope="module")
+def formula_cases():
+    f = dgr.load_fixture()
+    return f, dgr.device_k(f)
+
+
+def held_to_the_formula(what, got, f, k_dev):
+    """|got - ref| <= K_dev (2^-52 |ref| + budget) at every fixture point, K_dev four times what torch's float64
+    evaluation needs in that branch; a point within 1e-12 of a branch edge may match either of its two branches, one
+    planted exactly on an edge only the branch exact arithmetic takes.  Prints the worst ratio per branch."""
+    assert np.isfinite(got).all(), (what, np.nonzero(~np.isfinite(got))[0][:10])
+    assert (got != 0).all(), (what, np.nonzero(got == 0)[0][:10])  # no isnan -> 0 fallback fired: no reference is zero
+    ratio, br = dgr.fixture_ratio(got, f)
+    for b, name in enumerate(dgr.BRANCHES):
+        idx = np.nonzero(br == b)[0]
+        i = idx[int(np.argmax(ratio[idx]))]
+        print(f"FORMULA {what} {name}: worst err / (2^-52 |ref| + budget) {ratio[i]:.3f} of K_dev {k_dev[b]:.2f} at "
+              f"(x, alpha, total) = ({f['x'][i]!r}, {f['alpha'][i]!r}, {f['total'][i]!r}), relative error "
+              f"{abs(got[i] / f['ref'][i] - 1):.2e}, {len(idx)} points")
+        first = br[idx] == f["branch"][idx]
+        rel = np.abs(got[idx] / np.where(first, f["ref"][idx], f["ref2"][idx]) - 1)
+        j = int(np.argmax(rel))
+        print(f"FORMULA {what} {name}: largest relative error {rel[j]:.2e} at ({f['x'][idx[j]]!r}, {f['alpha'][idx[j]]!r}, "
+              f"{f['total'][idx[j]]!r}), where the budget is "
+              f"{np.where(first, f['budget_rel'][idx], f['budget2_rel'][idx])[j]:.2e} of the value")
+    bad = np.nonzero(ratio > k_dev[br])[0]
+    assert bad.size == 0, [(what, dgr.BRANCHES[br[k]], float(f["x"][k]), float(f["alpha"][k]), float(f["total"][k]),
+                            float(ratio[k])) for k in bad[:20]]
+
+
+@pytest.mark.parametrize("op", [2, 10])
+def test_dirichlet_grad_matches_its_formula(engine, formula_cases, op):
+    """Op 2 (dirichlet_grad_one) and op 10 (dirichlet_grad_one_pre, the device's own digammas supplied)."""
+    f, k_dev = formula_cases
+    g, _ = engine.test_special(op, f["alpha"], f["x"], f["total"])
+    held_to_the_formula(f"op {op}", g.cpu().numpy(), f, k_dev)
+
+
+def test_precomputed_digamma_form_is_bitwise_the_plain_function_on_the_whole_domain(engine, formula_cases):
+    """The property of test_precomputed_digamma_form_is_bitwise_the_plain_function (tests/test_gpu_grad_elementwise.py)
+    on [1e-5, 1e5] and on the clamps."""
+    f, _ = formula_cases
+    plain, _ = engine.test_special(2, f["alpha"], f["x"], f["total"])
+    pre, _ = engine.test_special(10, f["alpha"], f["x"], f["total"])
+    assert torch.equal(plain.view(torch.int64), pre.view(torch.int64))
 
 
 @pytest.mark.parametrize("a,b", [(0.3, 0.7), (0.9, 14.0), (2.5, 2.5), (40.0, 7.0), (1e-5, 3.0)])
