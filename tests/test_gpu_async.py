@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None, resume=False, blocks=None, fin=None):
+def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None, resume=False, blocks=None, fin=None, start=None):
+    """`start(eng)` writes the parameters the fit begins at (the default initial values where it is None)."""
     from bean_amd import engine
 
     monkeypatch.setenv("BEAN_HIP_STEP", mode)
@@ -26,6 +27,8 @@ def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None, resume=Fal
             monkeypatch.delenv(key, raising=False)
     eng = engine.HipSVI(family, data.to(DEV), num_steps=steps, **eng_kw)
     assert eng.dominant_kernel == ("k_guide_wave2" if mode == "pair" else "k_svi_async")
+    if start is not None:
+        start(eng)
     for n in (chunks or [steps]):
         eng.run(n, seed=5, resume=resume)
     torch.cuda.synchronize()
@@ -35,9 +38,9 @@ def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None, resume=Fal
     return out, loss
 
 
-def _same(monkeypatch, family, data, steps, eng_kw=None, chunks=None, resume=False, blocks=None, fin=None):
-    a, la = _fit(monkeypatch, "pair", family, data, steps, eng_kw or {}, chunks, resume)
-    b, lb = _fit(monkeypatch, "async", family, data, steps, eng_kw or {}, chunks, resume, blocks, fin)
+def _same(monkeypatch, family, data, steps, eng_kw=None, chunks=None, resume=False, blocks=None, fin=None, start=None):
+    a, la = _fit(monkeypatch, "pair", family, data, steps, eng_kw or {}, chunks, resume, start=start)
+    b, lb = _fit(monkeypatch, "async", family, data, steps, eng_kw or {}, chunks, resume, blocks, fin, start=start)
     assert np.all(np.isfinite(la)) and len(la) == steps == len(lb)
     for k in a:
         assert torch.equal(a[k], b[k]), (k, (a[k] - b[k]).abs().max().item())

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import bean_amd  # noqa: F401
+import effect_regimes as er
 import grad_bounds as gb
 from bean_amd.preprocessing.synthetic import (make_sorting_tiling_screen, make_sorting_variant_screen,
                                               make_survival_tiling_screen, make_survival_variant_screen)
@@ -87,7 +88,7 @@ def engine():
 def point_parameters(kind, data, start, point, seed=7):
     """The unconstrained parameters of an evaluation point from the engine's start values, formed on the host:
     every tensor + 0.3 randn (masked alleles keep their fixed storage); "fitted": alpha_pi replaced by
-    ``grad_bounds.fitted_like_alpha_pi``."""
+    ``grad_bounds.fitted_like_alpha_pi``; "effect": the Normal side replaced too, ``effect_regimes.effect_point``."""
     g = torch.Generator().manual_seed(seed)
     out = {}
     for k, v in start.items():
@@ -98,6 +99,8 @@ def point_parameters(kind, data, start, point, seed=7):
         out[k] = v + noise
     if point == "fitted":
         out["alpha_pi"] = gb.fitted_like_alpha_pi(data, out["alpha_pi"], seed=seed)
+    if point == "effect":
+        out = er.effect_point(kind, data, out, seed=seed)
     return out
 
 
@@ -131,12 +134,15 @@ def run_case(engine, monkeypatch, name, point):
 
 
 def evaluate(engine, name, point, kind, data, kw, kernel, variant=None, family=None, loss_fn=None, oracle_params=None,
-             **bounds_kw):
+             inject=None, **bounds_kw):
     """One evaluation of the screen `data` at `point` against the oracle: the kernel (where one is named), the loss to
     1e-9, every gradient element within its tolerance.  `family` / `loss_fn` default to the mixture family of `kind`;
     `bounds_kw` goes to grad_bounds.elementwise_bounds (another implicit gradient for the oracle, a per-evaluation
     allowance in place of the pathwise constants: then no element has a tail constant, and one beyond `tol` fails);
-    `oracle_params` maps the point's float32 parameters to the ones the oracle is evaluated at."""
+    `oracle_params` maps the point's float32 parameters to the ones the oracle is evaluated at; `inject(engine)` returns
+    draws to hand in (`set_noise`) in place of the engine's own - the branches of the implicit gradient are then whatever
+    those draws give and are not asserted.  At the "effect" point the census of the dumped draws is printed
+    (effect_regimes.floor_census) and returned."""
     family, loss_fn = family or FAMILY[kind], loss_fn or LOSS[kind]
     extra = dict(lib_variant=variant) if variant else {}
     eng = engine.HipSVI(family, data.to(DEV), dump_noise=True, num_steps=50, **kw, **extra)
@@ -145,29 +151,36 @@ def evaluate(engine, name, point, kind, data, kw, kernel, variant=None, family=N
     params = point_parameters(kind, data, eng.unconstrained, point)
     for k, v in eng.unconstrained.items():
         v.copy_(params[k].to(DEV))
+    if inject is not None:
+        eng.set_noise(inject(eng))
     loss, grads = eng.elbo_grad(step=2, seed=7)
     draws = {k: v.cpu() for k, v in eng.drawn_noise().items()}
     eng.close()
     assert np.isfinite(loss)
     at = params if oracle_params is None else oracle_params(params)
+    census = None
+    if point == "effect":
+        census = er.floor_census(data, at, draws, kw, loss_fn)
+        print(f"CENSUS {name} {point}: {er.census_line(census)}")
     ref_loss, ref, tol, tol_tail = gb.elementwise_bounds(loss_fn, elbo.as_float64(data), at, draws, kw, **bounds_kw)
     print(f"LOSS {name} {point}: |loss - ref| / |ref| {abs(loss - ref_loss) / abs(ref_loss):.3e}")
     assert abs(loss - ref_loss) <= 1e-9 * abs(ref_loss), (name, point, loss, ref_loss)
     if "alpha_pi" not in params:  # the Normal family: no Dirichlet site in the guide, no implicit gradient
         check_elementwise(name, point, grads, ref, tol, tol_tail)
-        return
+        return census
     if kind.endswith("tiling"):
         # the gradient of a masked allele's alpha is exactly zero (in-place write at model.py:645)
         assert torch.all(grads["alpha_pi"][~data.allele_mask.to(DEV)] == 0), (name, point)
     counts = gb.branch_counts(data, params["alpha_pi"], draws["pi"], survival=kind.startswith("survival"))
     print(f"BRANCHES {name} {point}: " + ", ".join(f"{b} {int(n)}" for b, n in zip(gb.BRANCHES, counts)) +
           f" of {int(counts.sum())}")
-    if point == "fitted":
+    if point in ("fitted", "effect") and inject is None:
         if kind == "variant":
             assert counts.min() >= 0.1 * counts.sum(), (name, counts)
         else:
             assert counts.min() >= 1, (name, counts)
     check_elementwise(name, point, grads, ref, tol, tol_tail)
+    return census
 
 
 PRODUCT = [n for n, c in CASES.items() if c[5] is None]

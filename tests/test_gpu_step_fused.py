@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None):
+def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None, start=None):
+    """`start(eng)` writes the parameters the fit begins at (the default initial values where it is None)."""
     from bean_amd import engine
 
     if mode == "pair":  # the product library
@@ -24,6 +25,8 @@ def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None):
         eng = engine.HipSVI(family, data.to(DEV), num_steps=steps, lib_variant="ab", **eng_kw)
     assert data.n_targets >= 64  # fewer targets: k_param's one-block-per-target mode, two launches
     assert eng.dominant_kernel == ("k_guide_wave2" if mode == "pair" else "k_step_wave2")
+    if start is not None:
+        start(eng)
     for n in (chunks or [steps]):
         eng.run(n, seed=5)
     torch.cuda.synchronize()
@@ -33,9 +36,9 @@ def _fit(monkeypatch, mode, family, data, steps, eng_kw, chunks=None):
     return out, loss
 
 
-def _same(monkeypatch, family, data, steps, eng_kw=None, chunks=None):
-    a, la = _fit(monkeypatch, "pair", family, data, steps, eng_kw or {}, chunks)
-    b, lb = _fit(monkeypatch, "fused", family, data, steps, eng_kw or {}, chunks)
+def _same(monkeypatch, family, data, steps, eng_kw=None, chunks=None, start=None):
+    a, la = _fit(monkeypatch, "pair", family, data, steps, eng_kw or {}, chunks, start)
+    b, lb = _fit(monkeypatch, "fused", family, data, steps, eng_kw or {}, chunks, start)
     assert np.all(np.isfinite(la)) and len(la) == steps == len(lb)
     for k in a:
         assert torch.equal(a[k], b[k]), (k, (a[k] - b[k]).abs().max().item())

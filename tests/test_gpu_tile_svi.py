@@ -36,10 +36,14 @@ def _engine(family, data, pair, **kw):
     return eng
 
 
-def _compare(family, data, chunks=(1, 7, 30), **kw):
+def _compare(family, data, chunks=(1, 7, 30), start=None, **kw):
+    """`start(eng)` writes the parameters both fits begin at (the default initial values where it is None)."""
     a = _engine(family, data, pair=False, **kw)
     b = _engine(family, data, pair=True, **kw)
     assert a.dominant_kernel == "k_svi_tile" and b.dominant_kernel == "k_guide_wave2"
+    if start is not None:
+        start(a)
+        start(b)
     for n in chunks:  # several calls: each begins with a PREP-only launch and ends without one
         a.run(n, seed=13)
         b.run(n, seed=13)
