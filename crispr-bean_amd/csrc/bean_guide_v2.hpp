@@ -310,8 +310,41 @@ __device__ __forceinline__ double guide_pair_math(const DevArgs& c, const StepCt
         // by the implicit-gradient calls below
         const double dgS = w2_ld<STEP>(c.dgq + 3 * (long)G + g), dg0 = w2_ld<STEP>(c.dgq + 4 * (long)G + g),
                      dg1 = w2_ld<STEP>(c.dgq + 5 * (long)G + g);
+        // ... and, issued with them, the x-free factors of the FIRST call (DevArgs::dgt, written with dgq; one set per
+        // component).  torch's approximation switches formula on x <= 0.5 / x >= 0.5: a lane takes its SMALLER
+        // component in the first call and the larger one in the second, so that a call runs one side's formulas for
+        // the whole wave (in component order every call ran both sides': 13 % of the kernel).
+        // The calls are out of line and a callee waits for every load in flight, so a set asked for at its call would
+        // put a round trip (agent scope in k_svi_async: past this XCD's L2) in front of it.  The first set travels under
+        // the logs and reciprocals below; the first call is made BEFORE the Multinomial and Dirichlet terms (it needs
+        // none of them: only its product with gpi - proj does), and the second set travels under those.  Both sets at
+        // once, with the digammas, cost k_svi_async<2, false> 8 spilled VGPRs.  Same calls, same arguments, same bits.
+        const int first = pi0 <= pi1 ? 0 : 1;
+        const bool on_a = !(first ? cl1 : cl0), on_b = !(first ? cl0 : cl1);  // first / second call: not on the clamp
+        double tq[kDgtRows];
+        if (c.dgt) {
+            const double* t = c.dgt + (long)first * kDgtRows * G + g;
+#pragma unroll
+            for (int k = 0; k < kDgtRows; ++k) tq[k] = w2_ld<STEP>(t + (long)k * G);
+        }
         const double lpi0 = flog(pi0), lpi1 = flog(pi1);
         const double rpi0 = frcp(pi0), rpi1 = frcp(pi1);
+        const double total = cq0 + cq1;
+        double dv_a = 0.0, dv_b = 0.0;
+#if BEAN_GW_DIAG == 2
+        dv_a = first ? pi1 : pi0;
+        dv_b = first ? pi0 : pi1;
+#else
+        if (on_a)
+            dv_a = c.dgt ? dirichlet_grad_one_tab(first ? pi1 : pi0, first ? cq1 : cq0, total, first ? dg1 : dg0, dgS, tq[0],
+                                                  tq[1], tq[2], tq[3], tq[4], tq[5])
+                         : dirichlet_grad_one_pre(first ? pi1 : pi0, first ? cq1 : cq0, total, first ? dg1 : dg0, dgS);
+        if (c.dgt) {
+            const double* t = c.dgt + (long)(first ^ 1) * kDgtRows * G + g;
+#pragma unroll
+            for (int k = 0; k < kDgtRows; ++k) tq[k] = w2_ld<STEP>(t + (long)k * G);
+        }
+#endif
         if (rgm) {
             // Multinomial(probs = pi) on control allele counts (model.py:470-474):
             // torch renormalises the probabilities and clamps them to [eps, 1 - eps]
@@ -339,25 +372,20 @@ __device__ __forceinline__ double guide_pair_math(const DevArgs& c, const StepCt
         gpi1 += (cq1 - 1.0) * rpi1;
         nll += (cq0 - 1.0) * lpi0 + (cq1 - 1.0) * lpi1;
         const double proj = pi0 * gpi0 + pi1 * gpi1;
-        const double total = cq0 + cq1;
-        double path0 = 0.0, path1 = 0.0;
-        // torch's approximation switches formula on x <= 0.5 / x >= 0.5: a lane takes its SMALLER
-        // component in the first pass and the larger one in the second, so that a pass runs one side's
-        // formulas for the whole wave (in component order every pass ran both sides': 13 % of
-        // the kernel).  Same calls, same arguments, same bits.
-        const int first = pi0 <= pi1 ? 0 : 1;
-#pragma unroll 1
-        for (int pass = 0; pass < 2; ++pass) {
-            const int a = pass ^ first;
-            if (a ? cl1 : cl0) continue;
-#if BEAN_GW_DIAG == 2
-            const double v = (a ? pi1 : pi0) * ((a ? gpi1 : gpi0) - proj);
-#else
-            const double v = dirichlet_grad_one_pre(a ? pi1 : pi0, a ? cq1 : cq0, total, a ? dg1 : dg0, dgS) *
-                             ((a ? gpi1 : gpi0) - proj);
+#if BEAN_GW_DIAG != 2
+        if (on_b)
+            dv_b = c.dgt ? dirichlet_grad_one_tab(first ? pi0 : pi1, first ? cq0 : cq1, total, first ? dg0 : dg1, dgS, tq[0],
+                                                  tq[1], tq[2], tq[3], tq[4], tq[5])
+                         : dirichlet_grad_one_pre(first ? pi0 : pi1, first ? cq0 : cq1, total, first ? dg0 : dg1, dgS);
 #endif
-            path0 = a ? path0 : v;
-            path1 = a ? v : path1;
+        // the pathwise terms: (the call of component a) * (gpi_a - proj), 0 for a component on its clamp
+        // (products of their own, as they were inside the two-pass loop: not to be fused into the additions below)
+        const double dv0 = first ? dv_b : dv_a, dv1 = first ? dv_a : dv_b;
+        double path0, path1;
+        {
+#pragma clang fp contract(off)
+            path0 = cl0 ? 0.0 : dv0 * (gpi0 - proj);
+            path1 = cl1 ? 0.0 : dv1 * (gpi1 - proj);
         }
         // d loss / d c_a of this replicate apart from the per-guide normaliser terms:
         // (c_q unclamped) log pi_a + pathwise term, minus (masked) log pi_a of the model site

@@ -121,6 +121,7 @@ struct bean_hip_ctx {
     void* resume_stream = nullptr;
     // all the steps of a call in ONE launch, tile-asynchronous (bean_async_v2.hpp): eligible shape and switched on
     bool async_step = false;
+    bool dirgrad_tab = true;  // DevArgs::dgt is allocated and filled (BEAN_HIP_DIRGRAD_TAB=0 at create: not, A/B)
     int* async_ws = nullptr;   // device: 8 queue counters (kAsyncQueueStride apart), the abort word, done[n_tiles]
     int async_blocks = 0;      // grid: resident single-wave workgroups that pull items, a multiple of 8 (0: not yet measured)
     int async_fin_blocks = 0;  // ... and that only finish tiles (0: no roles, the last arriver finishes)
@@ -475,6 +476,7 @@ static void workspace_regions(const bean_hip_ctx* c, DevArgs& d, V&& v, int** ti
     }
     const bool wave_rows = c->wave2 || c->surv_wave;
     opt(d.dgq, (wave_rows && s.family == BEAN_FAMILY_MIXTURE_NORMAL) ? 6 * G : 0);
+    opt(d.dgt, (c->dirgrad_tab && wave_rows && s.family == BEAN_FAMILY_MIXTURE_NORMAL) ? 2 * (uint64_t)kDgtRows * G : 0);
     opt(d.dgq_t, (c->tiling_wave || c->tiling_rep) ? (uint64_t)(kAMax + 1) * G : 0);
     opt(d.lpart, 3 * (uint64_t)d.n_lpart);  // per-wave loss parts of the wave-form guide kernels
     v(d.q0_ctr, 1);
@@ -635,6 +637,11 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
         if (s->n_condits > 16) c->tiling_rep_w = 1;  // LDS: (3 B + ...) x 64 W doubles per workgroup
     }
     d.wide_alleles = c->tiling_wide ? 1 : 0;
+    {
+        // =0: every implicit-gradient call forms its x-free factors itself, as before the table (A/B, same bits)
+        const char* dt = getenv("BEAN_HIP_DIRGRAD_TAB");
+        c->dirgrad_tab = !(dt && !strcmp(dt, "0"));
+    }
     d.trow_summed = (c->tiling_wave || c->tiling_rep) ? 1 : 0;
     {
         const char* tc = getenv("BEAN_HIP_TOT_CONST");  // =0: the total terms are evaluated every step (A/B)
@@ -2634,7 +2641,7 @@ extern "C" int bean_hip_debug_stamps(bean_hip_ctx* c, unsigned long long* host, 
 
 extern "C" int bean_hip_test_special(int32_t op, uint64_t n, const double* a, const double* x,
                                      const double* b, double* out0, double* out1, void* stream_) {
-    if (op < 0 || op > 10) return fail("bean_hip_test_special: unknown op");
+    if (op < 0 || op > 11) return fail("bean_hip_test_special: unknown op");
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_test_special, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
                        (int)op, (long)n, a, x, b, out0, out1);

@@ -151,6 +151,11 @@ struct DevArgs {
     int trow_summed;                   // k_sum_trow has reduced trow into part
     int wide_alleles;                  // tiling with more alleles per guide than kAMax: bean_tiling_wide.hpp
     double* dgq;
+    // (2 kDgtRows, G) or null: the x-free factors of the implicit Dirichlet gradient's alpha > 6 && beta > 6 branch
+    // (DirGradTab, bean_special.hpp), one set per component, of the SAME concentrations as dgq and written with it by
+    // param_guide_mix PREP; read by guide_pair_math and k_guide_survival_wave.  Null (BEAN_HIP_DIRGRAD_TAB=0, A/B):
+    // every call forms them itself (dirichlet_grad_one_pre) - same bits.
+    double* dgt;
     double* dgq_t;                     // tiling: (kAMax + 1, G) digamma(c_q[a]) rows and digamma(sum c_q), same contract
     long long* lpart;                  // (n_lpart, 3) per-wave loss parts of the wave-form guide kernels, or null
     int n_lpart;
@@ -1251,6 +1256,26 @@ __device__ __forceinline__ void param_guide_mix(const DevArgs& c, int g, AdamCoe
         coh_st<COH>(c.dgq + 3 * Gl + g, dgS);
         coh_st<COH>(c.dgq + 4 * Gl + g, dg0);
         coh_st<COH>(c.dgq + 5 * Gl + g, dg1);
+        if (c.dgt) {
+            // the implicit gradient's x-free factors (DirGradTab), for the calls of the next guide kernel: of the
+            // concentrations as THAT kernel forms them (guide_pair_draw: al * (frcp(s) * pa0), not al / s * pa0 - the
+            // factors must be those of the very alpha and total the call is given)
+            const double rs = frcp(s) * pa0;
+            const double k0 = al0 * rs, k1 = al1 * rs;
+            const double cq0 = k0 < 1e-5 ? 1e-5 : k0, cq1 = k1 < 1e-5 ? 1e-5 : k1;
+            const double total = cq0 + cq1;
+#pragma unroll
+            for (int a = 0; a < 2; ++a) {
+                const DirGradTab t = dirgrad_tab_make(a ? cq1 : cq0, total);
+                double* o = c.dgt + (long)a * kDgtRows * Gl + g;
+                coh_st<COH>(o, t.rtot);
+                coh_st<COH>(o + Gl, t.sd);
+                coh_st<COH>(o + 2 * Gl, t.stir);
+                coh_st<COH>(o + 3 * Gl, t.rpf);
+                coh_st<COH>(o + 4 * Gl, t.t3);
+                coh_st<COH>(o + 5 * Gl, t.h1);
+            }
+        }
     }
 }
 
@@ -3389,6 +3414,12 @@ __global__ __launch_bounds__(256) void k_test_special(int op, long n, const doub
     } else if (op == 10) {
         // the form the product kernels call, handed the device's own digammas (must equal op 2 bit for bit)
         o0[i] = dirichlet_grad_one_pre(x[i], a[i], b[i], digamma(a[i]), digamma(b[i]));
+    } else if (op == 11) {
+        // ... with the x-free factors tabulated as param_guide_mix PREP tabulates them (DevArgs::dgt; must equal op 10
+        // bit for bit)
+        const DirGradTab t = dirgrad_tab_make(a[i], b[i]);
+        o0[i] = dirichlet_grad_one_tab(x[i], a[i], b[i], digamma(a[i]), digamma(b[i]), t.rtot, t.sd, t.stir, t.rpf, t.t3,
+                                       t.h1);
     }
 }
 

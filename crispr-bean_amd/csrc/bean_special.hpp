@@ -3,6 +3,11 @@
 // All arithmetic is float64: the reference's likelihood runs in float64 through
 // dtype promotion and MI355X issues v_fma_f64 at the same rate as
 // non-packed f32.
+//
+// What depends on a guide's concentrations alone is formed once per guide and step by the finish (param_guide_mix
+// PREP) and read by every replicate's call: the digammas (DevArgs::dgq) and the x-free factors of the implicit
+// Dirichlet gradient's alpha > 6 && beta > 6 branch (DevArgs::dgt: DirGradTab, dirgrad_tab_make,
+// dirichlet_grad_one_tab below - six factors per component, bit-identical to forming them in the call).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocrand/rocrand_kernel.h>
@@ -402,6 +407,76 @@ __device__ inline double beta_grad_alpha_mid(double x, double alpha, double beta
     return stirling * prefactor * term1234;
 }
 
+// The factors of beta_grad_alpha_mid that do not depend on x, for ONE call (alpha, total): they are functions of the
+// guide's concentrations only, which change once per step, while the call is repeated by every replicate of the guide.
+// param_guide_mix PREP forms them once per guide and step (DevArgs::dgt, next to the digammas of DevArgs::dgq) and
+// dirichlet_grad_one_tab consumes them: five of the six square roots and six of the eleven reciprocals of the branch.
+//   rtot  1 / (alpha + beta)                     sd    sqrt(alpha beta / (total + 1)) / total (the Taylor window)
+//   stir  the Stirling factor                    rpf   1 / sqrt(2 alpha beta / total), the x-free part of `prefactor`
+//   t3    sqrt(8 alpha beta / total) of term3    h1    sqrt(2 alpha / beta) total^(3/2), the head of term1_den
+// One set PER COMPONENT, also of the factors that are symmetric in (alpha, beta) on paper: a call sees
+// beta = total - alpha and alpha + beta, ROUNDED, and fl(total - c_q0) is not c_q1 (nor is fl(c_q1 + fl(total - c_q1))
+// always total) - a shared row would change the last bit of one of the two calls.
+// Same bits as beta_grad_alpha_mid: that function is compiled under the default contraction and its roundings are
+// the compiler's choices inside dirichlet_grad_one_pre; here contraction is off and every fma stands where that
+// code object has one (read from its machine code), every product keeps its order.
+// Outside alpha > 6 && beta > 6 the values are never read (and may be inf / nan: beta can round to 0).
+struct DirGradTab {
+    double rtot, sd, stir, rpf, t3, h1;
+};
+constexpr int kDgtRows = 6;  // rows per component of DevArgs::dgt: row (a kDgtRows + k) G + g, k in the order above
+__device__ __forceinline__ DirGradTab dirgrad_tab_make(double alpha, double total_in) {
+#pragma clang fp contract(off)
+    const double beta = total_in - alpha;  // as dirichlet_grad_one_t forms it
+    const double total = alpha + beta;
+    DirGradTab t;
+    t.rtot = frcp(total);
+    t.sd = fsqrt(alpha * beta * frcp(total + 1.0)) * t.rtot;
+    const double ra = frcp(alpha), rb = frcp(beta);
+    t.rpf = frcp(fsqrt(2.0 * alpha * beta * t.rtot));
+    t.stir = fma(1.0 / 288.0, ra * ra, fma(1.0 / 12.0, ra, 1.0)) * fma(1.0 / 288.0, rb * rb, fma(1.0 / 12.0, rb, 1.0)) *
+             frcp(fma(1.0 / 288.0, t.rtot * t.rtot, fma(1.0 / 12.0, t.rtot, 1.0)));
+    t.h1 = fsqrt(2.0 * alpha * rb) * (total * fsqrt(total));
+    t.t3 = fsqrt(8.0 * alpha * beta * t.rtot);
+    return t;
+}
+// beta_grad_alpha_mid with the x-free factors handed in
+__device__ __forceinline__ double beta_grad_alpha_mid_tab(double x, double alpha, double beta, const DirGradTab& t) {
+#pragma clang fp contract(off)
+    const double total = alpha + beta;
+    const double rtot = t.rtot;
+    const double mean = alpha * rtot;
+    const double om = 1.0 - x;
+    const double b2 = beta * beta;
+    if (fma(t.sd, -0.1, mean) <= x && x <= fma(t.sd, 0.1, mean)) {
+        const double t1 = 47.0 * x * b2;
+        const double t2 = b2 * fma(x, 20.0 * fma(beta, 27.0, 16.0), 43.0);
+        const double t3 = 3.0 * fma(x, -90.0, fma(beta, 180.0, 59.0));
+        const double t4 = beta * fma(x, -455.0, fma(om, 1620.0 * beta, 453.0));
+        const double t5 = 8.0 * om * fma(beta, 135.0, -11.0);
+        double p = alpha * fma(alpha, t5, t4);
+        p = alpha * fma(b2, t3, p);
+        p = alpha * fma(beta, t2, p);
+        const double poly = fma(b2, t1, p);
+        const double pre_num = fma(alpha, 12.0, 1.0) * fma(beta, 12.0, 1.0) * rtot * rtot;
+        const double pre_den = 12960.0 * alpha * alpha * alpha * beta * beta * fma(total, 12.0, 1.0);
+        return pre_num * poly * frcp(om * pre_den);
+    }
+    const double xm1 = x - 1.0;
+    const double prefactor = -x * t.rpf;
+    const double term1_num = fma(b2, -x, fma(2.0 * (alpha * alpha), xm1, alpha * beta * xm1));
+    const double axbx = fma(alpha, xm1, beta * x);
+    const double term1_den = t.h1 * axbx * axbx;
+    const double la = flog(alpha * frcp(total * x));
+    const double lb = flog(beta * frcp(total * om));
+    const double term2 = 0.5 * la;
+    const double term4_base = fma(beta, lb, alpha * la);
+    const double term4 = frcp(term4_base * fsqrt(term4_base));
+    const double term34 = fma(t.t3, frcp(axbx), x < mean ? term4 : -term4);
+    const double term1234 = fma(term1_num, frcp(term1_den), term2 * term34);
+    return t.stir * prefactor * term1234;
+}
+
 // c[num/den][u^i][a^j][b^k] of the rational correction in dirichlet_grad_one
 __device__ __constant__ const double kDirGradC[2][3][3][4] = {
     {{{1.003668233, -0.01061107488, -0.0657888334, 0.01201642863},
@@ -424,14 +499,16 @@ __device__ __constant__ const double kDirGradC[2][3][3][4] = {
       {-0.0003477407336, 6.959756487e-05, 1.097287507e-05, -1.650964693e-06}}},
 };
 
-template <bool PRE>
+// TAB: the alpha > 6 && beta > 6 branch takes its x-free factors from `tab` (this call's DirGradTab); every other
+// branch is the same code.
+template <bool PRE, bool TAB = false>
 __device__ __forceinline__ double dirichlet_grad_one_t(double x, double alpha, double total, double dg_alpha,
-                                                       double dg_total) {
+                                                       double dg_total, const DirGradTab* tab = nullptr) {
     const double beta = total - alpha;
     const double boundary = total * x * (1.0 - x);
     if (x <= 0.5 && boundary < 2.5) return beta_grad_alpha_small_t<PRE>(x, alpha, beta, dg_alpha, dg_total);
     if (x >= 0.5 && boundary < 0.75) return -beta_grad_beta_small_t<PRE>(1.0 - x, beta, alpha, dg_total, dg_alpha);
-    if (alpha > 6.0 && beta > 6.0) return beta_grad_alpha_mid(x, alpha, beta);
+    if (alpha > 6.0 && beta > 6.0) return TAB ? beta_grad_alpha_mid_tab(x, alpha, beta, *tab) : beta_grad_alpha_mid(x, alpha, beta);
     // rational correction to an analytic approximation (kDirGradC below)
     const auto& c = kDirGradC;
     const double u = flog(x);
@@ -464,6 +541,13 @@ __device__ BEAN_NOINLINE double dirichlet_grad_one(double x, double alpha, doubl
 __device__ BEAN_NOINLINE double dirichlet_grad_one_pre(double x, double alpha, double total, double dg_alpha,
                                                        double dg_total) {
     return dirichlet_grad_one_t<true>(x, alpha, total, dg_alpha, dg_total);
+}
+// ... and the x-free factors of the alpha > 6 && beta > 6 branch (DirGradTab of this (alpha, total)): same bits
+__device__ BEAN_NOINLINE double dirichlet_grad_one_tab(double x, double alpha, double total, double dg_alpha,
+                                                       double dg_total, double rtot, double sd, double stir, double rpf,
+                                                       double t3, double h1) {
+    const DirGradTab t = {rtot, sd, stir, rpf, t3, h1};
+    return dirichlet_grad_one_t<true, true>(x, alpha, total, dg_alpha, dg_total, &t);
 }
 
 // ---------------------------------------------------------------------------

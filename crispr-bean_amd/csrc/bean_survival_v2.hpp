@@ -425,8 +425,16 @@ void k_guide_survival_wave(DevArgs c) {
             for (int pass = 0; pass < 2; ++pass) {
                 const int a = pass ^ first;
                 if (a ? cl1 : cl0) continue;
-                const double v = dirichlet_grad_one_pre(a ? pi1 : pi0, a ? cq1 : cq0, total, a ? dg1 : dg0, dgS) *
-                                 ((a ? gpi1 : gpi0) - proj);
+                double dv;
+                if (c.dgt) {
+                    // this component's x-free factors (DevArgs::dgt, written with dgq)
+                    const double* tq = c.dgt + (long)a * kDgtRows * G + g;
+                    dv = dirichlet_grad_one_tab(a ? pi1 : pi0, a ? cq1 : cq0, total, a ? dg1 : dg0, dgS, tq[0], tq[G],
+                                                tq[2 * (long)G], tq[3 * (long)G], tq[4 * (long)G], tq[5 * (long)G]);
+                } else {
+                    dv = dirichlet_grad_one_pre(a ? pi1 : pi0, a ? cq1 : cq0, total, a ? dg1 : dg0, dgS);
+                }
+                const double v = dv * ((a ? gpi1 : gpi0) - proj);
                 path0 = a ? path0 : v;
                 path1 = a ? v : path1;
             }

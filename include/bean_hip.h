@@ -639,7 +639,9 @@ int bean_hip_get_profile(bean_hip_ctx* ctx, double* avg_ms, uint64_t* launches);
  *   op 7: the same from the float32-floor sampler of the survival q0 site (must equal op 6 draw for draw)
  *   op 8: out0, out1 = max(Gamma(a), DBL_MIN), max(Gamma(b), DBL_MIN) from the plain pair sampler
  *   op 9: the same from the double-floor sampler of the wide tiling kernel (must equal op 8 draw for draw)
- *   op 10: as op 2 through dirichlet_grad_one_pre with digamma(a), digamma(b) supplied (must equal op 2 bit for bit) */
+ *   op 10: as op 2 through dirichlet_grad_one_pre with digamma(a), digamma(b) supplied (must equal op 2 bit for bit)
+ *   op 11: as op 10 through dirichlet_grad_one_tab, its x-free factors tabulated in the kernel as the finish tabulates
+ *          them (must equal op 10 bit for bit) */
 int bean_hip_test_special(int32_t op, uint64_t n, const double* a, const double* x,
                           const double* b, double* out0, double* out1, void* stream);
 
