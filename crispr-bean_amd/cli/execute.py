@@ -137,6 +137,18 @@ def get_parser():
                           "checked.  Default 0: off.")
     own.add_argument("--importance-seed", dest="importance_seed", type=int, default=101,
                      help="Seed of the draws of --importance-check (default 101).")
+    own.add_argument("--importance-integrate-pi", dest="importance_integrate_pi", action="store_true",
+                     help="With --importance-check S: also weight the same draws by the weight of (mu, sd) alone, the "
+                          "editing rates pi integrated out of the model by quadrature on the GPU - the joint weight of a "
+                          "MixtureNormal target covers its 2 x replicates x guides pi coordinates, for which the guide is "
+                          "a poor proposal whatever the quality of the Gaussian of mu.  Columns psis_k_marg, mu_is_marg, "
+                          "mu_sd_is_marg, is_ess_marg and n_pairs_unresolved behind those of --importance-check; a target "
+                          "with a (replicate, guide) pair the quadrature rule does not resolve (an essentially unedited "
+                          "guide: prior concentration plus control reads of an allele below 2) has n_pairs_unresolved > 0 "
+                          "and empty marginal columns.  With the Normal model, which has no pi, the marginal columns equal "
+                          "the joint ones.")
+    own.add_argument("--importance-nodes", dest="importance_nodes", type=int, default=32, metavar="Q",
+                     help="Quadrature nodes per integral of --importance-integrate-pi: 16, 32 or 64 (default 32).")
     own.add_argument("--bootstrap", dest="bootstrap", type=_non_negative_int, default=0, metavar="K",
                      help="Parametric bootstrap: after the fit of the screen, draw K screens from the fitted model on the "
                           "GPU (mu, sd and the guide noise at their fitted locations; fresh pi, Dirichlet and count draws; "
@@ -192,13 +204,14 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    from .run import importance_draws, member_mode, particle_count, predictive_draws
+    from .run import importance_draws, importance_nodes, member_mode, particle_count, predictive_draws
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
     particle_count(args, parser.error)
     predictive_draws(args, parser.error)
     importance_draws(args, parser.error)
+    importance_nodes(args, parser.error)
 
 
 def main(argv=None):

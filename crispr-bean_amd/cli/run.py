@@ -212,6 +212,23 @@ def importance_draws(args, fail=_refuse) -> int:
     return n
 
 
+IMPORTANCE_NODES = (16, 32, 64)  # _lib.MARGINAL_NODES
+
+
+def importance_nodes(args, fail=_refuse):
+    """``--importance-integrate-pi [--importance-nodes Q]``: the quadrature nodes of the marginal check (``pi`` integrated
+    out of the model), or None without the flag.  It rides on ``--importance-check`` - refused without it, and for every
+    family that flag is refused for (``importance_draws`` names it)."""
+    nodes = int(getattr(args, "importance_nodes", 32) or 32)
+    if nodes not in IMPORTANCE_NODES:
+        fail(f"--importance-nodes must be one of 16, 32, 64, got {nodes}.")
+    if not getattr(args, "importance_integrate_pi", False):
+        return None
+    if not int(getattr(args, "importance_check", 0) or 0):
+        fail("--importance-integrate-pi integrates pi out of the weights of --importance-check S and needs that flag.")
+    return nodes
+
+
 def check_guide_jackknife_switches(args) -> bool:
     """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
     return member_mode(args, only=("jackknife_guides",)) == "guides"
@@ -402,6 +419,7 @@ def main(args, return_data=False):
         if why is not None:
             raise PredictiveUnsupported(_PREDICTIVE_FAMILY.format(what=why))
     n_importance = importance_draws(args)
+    n_nodes = importance_nodes(args)
     if n_importance:
         from ..engine import PredictiveUnsupported
 
@@ -458,12 +476,20 @@ def main(args, return_data=False):
     if n_importance:
         info(f"Importance-sampling check: {n_importance} draws from the fitted guide, weighted per target...")
         summary = model_run.run_importance_check(model, guide, ndata, param_history_dict, n_draws=n_importance,
-                                                 seed=int(getattr(args, "importance_seed", model_run.SEED)))
+                                                 seed=int(getattr(args, "importance_seed", model_run.SEED)),
+                                                 **({"integrate_pi": n_nodes} if n_nodes else {}))
         table_columns = {**table_columns, "importance": {k: v.detach().cpu() for k, v in summary.items()}}
         k = table_columns["importance"]["psis_k"]
         info(f"Importance-sampling check: psis_k > 0.7 on {int((k > 0.7).sum())} of {k.numel()} targets "
              f"({100.0 * float((k > 0.7).double().mean()) if k.numel() else 0.0:.1f} %); median psis_k "
              f"{float(k.median()) if k.numel() else float('nan'):.3f}.")
+        if n_nodes:
+            km = table_columns["importance"]["psis_k_marg"]
+            left_out = table_columns["importance"]["n_pairs_unresolved"] > 0
+            share = lambda m: 100.0 * float(m.double().mean()) if m.numel() else 0.0  # noqa: E731
+            info(f"Importance-sampling check, pi integrated out ({n_nodes} nodes): psis_k_marg > 0.7 on "
+                 f"{int((km > 0.7).sum())} of {km.numel()} targets ({share(km > 0.7):.1f} %); {int(left_out.sum())} of "
+                 f"{km.numel()} targets ({share(left_out):.1f} %) left out as unresolved.")
     write_result_table(
         target_info_df,
         guide_info_df,

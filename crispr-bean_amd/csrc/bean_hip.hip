@@ -30,6 +30,7 @@
 #include "bean_kernels.hpp"
 #include "bean_predictive.hpp"  // replicate counts drawn on the device (bean_hip_simulate)
 #include "bean_importance.hpp"  // per-target log importance weights (bean_hip_log_weights)
+#include "bean_importance_marg.hpp"  // ... with pi integrated out (bean_hip_log_weights_marginal)
 
 using namespace bean;
 
@@ -2918,6 +2919,82 @@ extern "C" int bean_hip_log_weights(bean_hip_ctx* c, uint64_t seed, uint64_t fir
     });
     hipLaunchKernelGGL(k_logw_targets, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream,
                        d, la);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ ... with pi integrated out of the model
+// (bean_importance_marg.hpp) logw_marg of the same draws: the weight of (mu_t, sd_t) alone.  MixtureNormal: four launches
+// per call whatever n_draws (the pairs' constants, the unresolved pairs per target, the pairs' integrals, the targets);
+// Normal has no pi: exactly the launches of bean_hip_log_weights and unresolved_out zeroed.
+extern "C" int bean_hip_log_weights_marginal(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                             int32_t n_nodes, void* logw_out, uint64_t logw_bytes, void* mu_out,
+                                             uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out,
+                                             uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
+                                             void* stream_) {
+    if (!c) return fail("bean_hip_log_weights_marginal: null handle");
+    if (!predictive_shape_ok(c))
+        return fail("bean_hip_log_weights_marginal: the importance weights do not take this handle "
+                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
+                    "covariates, one member, one particle");
+    if (!c->prepared) return fail("bean_hip_log_weights_marginal: call bean_hip_prepare first");
+    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_LOGW_DRAWS)
+        return fail("bean_hip_log_weights_marginal: n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) +
+                    "], got " + std::to_string(n_draws));
+    if (n_nodes != 16 && n_nodes != 32 && n_nodes != 64)
+        return fail("bean_hip_log_weights_marginal: n_nodes must be 16, 32 or 64, got " + std::to_string(n_nodes));
+    if (check_bound(c, false, false)) return -1;
+    const DevArgs& d0 = c->d;
+    const uint64_t nt = (uint64_t)n_draws * d0.T, np = (uint64_t)n_draws * d0.R * d0.G;
+    const std::string sn = " float64 with n_draws = " + std::to_string(n_draws) + ", ";
+    if (!logw_out || logw_bytes != 8 * nt)
+        return fail("bean_hip_log_weights_marginal: logw_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) +
+                    " bytes");
+    if (!mu_out || mu_bytes != 8 * nt)
+        return fail("bean_hip_log_weights_marginal: mu_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) +
+                    " bytes");
+    if (y_out ? y_bytes != 8 * nt : y_bytes != 0)
+        return fail("bean_hip_log_weights_marginal: y_out must be null or hold (n_draws, T)" + sn +
+                    std::to_string(8 * nt) + " bytes");
+    if (!pair_out || pair_bytes != 8 * np)
+        return fail("bean_hip_log_weights_marginal: pair_out (caller-owned scratch) must hold (n_draws, R, G)" + sn +
+                    std::to_string(8 * np) + " bytes");
+    if (!unresolved_out || unresolved_bytes != 4 * (uint64_t)d0.T)
+        return fail("bean_hip_log_weights_marginal: unresolved_out must hold (T) int32, " +
+                    std::to_string(4 * (uint64_t)d0.T) + " bytes");
+    hipStream_t stream = (hipStream_t)stream_;
+    if (d0.family != kMixture) {
+        // no pi to integrate out: the joint weights are the marginal ones, and no pair is unresolved
+        HIP_OK(hipMemsetAsync(unresolved_out, 0, unresolved_bytes, stream));
+        return bean_hip_log_weights(c, seed, first_draw, n_draws, logw_out, logw_bytes, mu_out, mu_bytes, y_out, y_bytes,
+                                    pair_out, pair_bytes, stream_);
+    }
+    c->d.seed = seed;
+    c->resume_ok = false;  // (the seed of the handle has changed)
+    const DevArgs& d = c->d;
+    LogwArgs la;
+    la.first_draw = first_draw;
+    la.n_draws = n_draws;
+    la.logw_out = (double*)logw_out;
+    la.mu_out = (double*)mu_out;
+    la.y_out = (double*)y_out;
+    la.pair_out = (double*)pair_out;
+    MargArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.n_nodes = n_nodes;
+    ma.unresolved_out = (int*)unresolved_out;
+    gauss_hermite_half(n_nodes, ma.x, ma.lw);
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)n_draws), block(64);
+    const size_t lds = logw_marg_lds(d.B);
+    const uint64_t rg = (uint64_t)d.R * d.G;
+    hipLaunchKernelGGL(k_logw_consts, dim3((unsigned)((rg + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
+                       la);
+    hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
+                       stream, d, ma);
+    if (d.flags & kAcc) hipLaunchKernelGGL(k_logw_pairs_marg<true>, grid, block, lds, stream, d, la, ma);
+    else hipLaunchKernelGGL(k_logw_pairs_marg<false>, grid, block, lds, stream, d, la, ma);
+    hipLaunchKernelGGL(k_logw_targets_marg, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
+                       stream, d, la);
     HIP_OK(hipGetLastError());
     return 0;
 }

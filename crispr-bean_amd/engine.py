@@ -960,7 +960,8 @@ class HipSVI:
 
     LOGW_PAIR_BYTES = 256 << 20  # the pair plane of one bean_hip_log_weights call stays at or below this
 
-    def log_weights(self, first_draw: int, n_draws: int, seed: int = 101, pairs: bool = False) -> Dict[str, torch.Tensor]:
+    def log_weights(self, first_draw: int, n_draws: int, seed: int = 101, pairs: bool = False,
+                    integrate_pi: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """Per-target log importance weights of ``n_draws`` draws from the guide at the current parameters
         (``bean_hip_log_weights``): draw ``first_draw + j`` is the draw ``elbo_grad(step=first_draw + j, seed=seed)``
         evaluates (or, with ``set_noise``, the injected draw every time).  Returns float64 device tensors ``logw``
@@ -968,7 +969,20 @@ class HipSVI:
         ``mu`` and ``y`` (n_draws, T), the drawn ``mu_t`` and ``log sd_t``, and with ``pairs`` the terms of every
         (draw, replicate, guide) pair, ``pairs`` (n_draws, R, G), guides in screen order.  The draws go to the library in
         chunks whose pair plane stays at or below 256 MiB; draw d is the same whatever the chunking.  Leaves the fit alone
-        as ``simulate`` does; the next ``run(resume=True)`` is a plain run."""
+        as ``simulate`` does; the next ``run(resume=True)`` is a plain run.
+
+        ``integrate_pi=Q`` (16, 32 or 64; ``bean_hip_log_weights_marginal``): ``logw`` is the weight of ``(mu_t, sd_t)``
+        alone - ``pi`` integrated out of the model by Q-node quadrature per (draw, replicate, guide), no term of
+        ``q(pi)``; ``mu`` and ``y`` are the same bits; ``pairs`` then holds the pairs' constants plus the logs of their
+        integrals; and ``n_unresolved`` (T, int32) counts, per target, the pairs at which the rule is not valid (the
+        weights of such a target are not to be used).  For the ``Normal`` family, which has no ``pi``, ``logw`` is that of
+        the plain call bit for bit."""
+        if integrate_pi is not None:
+            if getattr(self.lib, "bean_hip_log_weights_marginal", None) is None:
+                raise PredictiveUnsupported("this library build has no bean_hip_log_weights_marginal")
+            if int(integrate_pi) not in _lib.MARGINAL_NODES:
+                raise ValueError(f"log_weights: integrate_pi must be one of {_lib.MARGINAL_NODES} quadrature nodes, got "
+                                 f"{integrate_pi!r}")
         if not self.predictive_supported or getattr(self.lib, "bean_hip_log_weights", None) is None:
             raise PredictiveUnsupported(f"the importance weights do not take this engine ({self.family}"
                                         f"{', survival' if self.survival else ''}): sorting variant Normal / "
@@ -983,6 +997,8 @@ class HipSVI:
         mu = torch.empty((S, T), dtype=torch.float64, device=dev)
         y = torch.empty((S, T), dtype=torch.float64, device=dev)
         plane = torch.empty((S if pairs else chunk, R, G), dtype=torch.float64, device=dev)
+        # (a draw-independent count: every chunk writes the same values)
+        unresolved = None if integrate_pi is None else torch.empty(T, dtype=torch.int32, device=dev)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         nb = lambda t: t.numel() * t.element_size()
         with self._on_stream():
@@ -990,11 +1006,19 @@ class HipSVI:
                 n = min(chunk, S - j0)
                 pl = plane[j0:j0 + n] if pairs else plane[:n]
                 lw, m, yy = logw[j0:j0 + n], mu[j0:j0 + n], y[j0:j0 + n]
-                self._check(self.lib.bean_hip_log_weights(self._h, int(seed), int(first_draw) + j0, n, ptr(lw), nb(lw),
-                                                          ptr(m), nb(m), ptr(yy), nb(yy), ptr(pl), nb(pl), self._sptr()),
-                            "log_weights")
+                if integrate_pi is None:
+                    self._check(self.lib.bean_hip_log_weights(self._h, int(seed), int(first_draw) + j0, n, ptr(lw), nb(lw),
+                                                              ptr(m), nb(m), ptr(yy), nb(yy), ptr(pl), nb(pl),
+                                                              self._sptr()), "log_weights")
+                else:
+                    self._check(self.lib.bean_hip_log_weights_marginal(
+                        self._h, int(seed), int(first_draw) + j0, n, int(integrate_pi), ptr(lw), nb(lw), ptr(m), nb(m),
+                        ptr(yy), nb(yy), ptr(pl), nb(pl), ptr(unresolved), nb(unresolved), self._sptr()),
+                        "log_weights_marginal")
         self.invalidate_resume()
         out = {"logw": logw, "mu": mu, "y": y}
+        if unresolved is not None:
+            out["n_unresolved"] = unresolved
         if pairs:
             out["pairs"] = self._to_screen_order(plane, 2)
         return out

@@ -12,6 +12,9 @@ torch float64, vectorised over targets, on whatever device the weights live.
   truncated at the raw maximum.
 * ``importance_summary``: ``psis_k``, the self-normalised smoothed weights' effective sample size and the
   importance-corrected posterior mean and sd of ``mu``.
+* ``marginal_summary``: the same of the weights of ``(mu_t, sd_t)`` alone - ``HipSVI.log_weights(integrate_pi=Q)``, ``pi``
+  integrated out of the model by quadrature (``csrc/bean_importance_marg.hpp``) - keys suffixed ``_marg``, NaN for a target
+  with a pair the rule does not resolve.
 
 What ``k`` says (Yao et al. 2018): below 0.5 the guide is a good proposal for this target and the corrected moments can
 be trusted; up to 0.7 they are usable; above it the guide is too light-tailed or misplaced for importance sampling to
@@ -120,8 +123,31 @@ def importance_summary(logw: torch.Tensor, mu: torch.Tensor) -> Dict[str, torch.
     }
 
 
-def importance_check(engine, n_draws: int = 1000, seed: int = 101) -> Dict[str, torch.Tensor]:
+MARGINAL_KEYS = ("psis_k_marg", "mu_is_marg", "mu_sd_is_marg", "is_ess_marg", "n_pairs_unresolved")
+
+
+def marginal_summary(logw_marg: torch.Tensor, mu: torch.Tensor, n_unresolved: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """``importance_summary`` of the weights with ``pi`` integrated out (``HipSVI.log_weights(integrate_pi=Q)``), keys
+    suffixed ``_marg``, plus ``n_pairs_unresolved``: the (replicate, guide) pairs of the target at which the quadrature
+    rule is not valid.  A target with such a pair has NaN in the four marginal values - its weights are not reported."""
+    s = importance_summary(logw_marg, mu)
+    n = torch.as_tensor(n_unresolved).to(s["psis_k"].device)
+    if n.shape != s["psis_k"].shape:
+        raise ValueError(f"marginal_summary: n_unresolved {tuple(n.shape)} is not one count per target "
+                         f"{tuple(s['psis_k'].shape)}")
+    nan = torch.full_like(s["psis_k"], math.nan)
+    out = {f"{k}_marg": torch.where(n > 0, nan, s[k]) for k in ("psis_k", "mu_is", "mu_sd_is", "is_ess")}
+    out["n_pairs_unresolved"] = n.to(s["psis_k"].dtype)
+    return out
+
+
+def importance_check(engine, n_draws: int = 1000, seed: int = 101, integrate_pi=None) -> Dict[str, torch.Tensor]:
     """``importance_summary`` of ``n_draws`` draws (0 .. n_draws - 1) from the guide of ``engine`` at its current
-    parameters; device tensors of length T."""
+    parameters; device tensors of length T.  ``integrate_pi=Q`` (16, 32 or 64 quadrature nodes): merged with the
+    ``marginal_summary`` of the same draws' weights of ``(mu_t, sd_t)`` alone."""
     out = engine.log_weights(0, int(n_draws), seed=seed)
-    return importance_summary(out["logw"], out["mu"])
+    summary = importance_summary(out["logw"], out["mu"])
+    if integrate_pi is not None:
+        marg = engine.log_weights(0, int(n_draws), seed=seed, integrate_pi=int(integrate_pi))
+        summary.update(marginal_summary(marg["logw"], marg["mu"], marg["n_unresolved"]))
+    return summary

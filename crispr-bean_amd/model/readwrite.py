@@ -239,7 +239,9 @@ def write_result_table(
     ``importance`` (an importance-sampling check of the guide, ``model/importance.py::importance_summary``): the element
     table gets exactly the columns ``psis_k``, ``mu_is``, ``mu_sd_is``, ``is_ess`` and ``n_is`` (``mu_is`` / ``mu_sd_is``
     on the scale of ``mu``, not rescaled), after those of a member set; every other column and the sgRNA table are those
-    of the run without it, and with ``None`` every file is byte for byte what it was."""
+    of the run without it, and with ``None`` every file is byte for byte what it was.  Where the summary also holds the
+    marginal check (``marginal_summary``: ``pi`` integrated out), ``psis_k_marg``, ``mu_is_marg``, ``mu_sd_is_marg``,
+    ``is_ess_marg`` (empty for a target with unresolved pairs) and ``n_pairs_unresolved`` follow behind them."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -287,6 +289,11 @@ def write_result_table(
     if importance is not None:
         _add_summary_columns(element, importance, "the importance-sampling summary",
                              ("psis_k", "mu_is", "mu_sd_is", "is_ess"), None, "n_is", count_per_target=True)
+        if "psis_k_marg" in importance:
+            # ... with pi integrated out (model/importance.py::marginal_summary): five more columns, behind those
+            _add_summary_columns(element, importance, "the marginal importance-sampling summary",
+                                 ("psis_k_marg", "mu_is_marg", "mu_sd_is_marg", "is_ess_marg"), None,
+                                 "n_pairs_unresolved", count_per_target=True)
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

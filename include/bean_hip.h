@@ -547,6 +547,37 @@ int bean_hip_log_weights(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, 
                          uint64_t logw_bytes, void* mu_out, uint64_t mu_bytes, void* y_out, uint64_t y_bytes,
                          void* pair_out, uint64_t pair_bytes, void* stream);
 
+/* The same weights with pi integrated out of the model: the importance weight of (mu_t, sd_t) alone (DESIGN.md section
+ * 21).  MixtureNormal's joint weight covers the 2 R n_guides pi coordinates of a target, for which the product Dirichlet
+ * guide is a poor proposal whatever the quality of q(mu_t); this one is a 2-D importance-sampling problem per target.
+ *
+ *   bean_hip_log_weights_marginal takes the handles, draws and arrays of bean_hip_log_weights with the same size
+ *                                 checks, and
+ *                                     logw_out[j, t] = log p(x_t, mu_t, sd_t[, noise]) - log q(mu_t, sd_t[, noise]),
+ *                                 the pi site of every (replicate, guide) integrated out of the model: one 1-D integral
+ *                                 per (draw, replicate, guide) in u = logit(pi_1), by n_nodes-point Gauss-Hermite
+ *                                 centred at the mode of the log integrand and scaled by its curvature there (a fixed
+ *                                 number of clamped Newton steps from the Beta factor's centre).  n_nodes is 16, 32 or
+ *                                 64.  No term of q(pi) appears.  mu_out / y_out are bean_hip_log_weights', bit for bit;
+ *                                 injected eps_mu / eps_sd / eps_noise are honoured, an injected pi is ignored.
+ *                                 pair_out[j, r, g] afterwards: the pair's data-only constants plus, under the repguide
+ *                                 mask, the log of its integral.
+ *                                 unresolved_out[t] (DEVICE int32, T of them): the pairs of target t under the repguide
+ *                                 mask at which the rule is not valid - min over the two alleles of (c_p + control
+ *                                 allele counts) below 2; a draw-independent count.  The weights of a target with such a
+ *                                 pair are computed all the same and are not to be used.
+ *                                 BEAN_FAMILY_NORMAL has no pi: exactly the launches of bean_hip_log_weights (logw_out
+ *                                 bit for bit) and unresolved_out zeroed.
+ *                                 Launches (MixtureNormal): k_logw_consts, k_logw_unresolved, k_logw_pairs_marg,
+ *                                 k_logw_targets_marg, whatever n_draws.  State: as bean_hip_log_weights.
+ *
+ * Errors: those of bean_hip_log_weights under this function's name; n_nodes other than 16, 32, 64 (the message names
+ * n_nodes); a null unresolved_out or unresolved_bytes other than 4 T. */
+int bean_hip_log_weights_marginal(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t n_draws, int32_t n_nodes,
+                                  void* logw_out, uint64_t logw_bytes, void* mu_out, uint64_t mu_bytes, void* y_out,
+                                  uint64_t y_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
+                                  uint64_t unresolved_bytes, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
