@@ -149,6 +149,19 @@ def get_parser():
                           "the joint ones.")
     own.add_argument("--importance-nodes", dest="importance_nodes", type=int, default=32, metavar="Q",
                      help="Quadrature nodes per integral of --importance-integrate-pi: 16, 32 or 64 (default 32).")
+    own.add_argument("--grid-posterior", dest="grid_posterior", action="store_true",
+                     help="After the fit, evaluate every target's posterior of (mu, sd) itself on the GPU - its log joint on "
+                          "a grid of (mu, log sd) placed by zoom passes from the fitted values, the editing rates pi "
+                          "integrated out by quadrature, no Gaussian and no guide involved - and report, per target: "
+                          "columns mu_grid / mu_sd_grid (posterior mean and sd of mu without the mean-field assumption, "
+                          "on the scale of the column mu), sd_grid, p_mu_pos_grid (P(mu > 0 | x)), log_evidence_grid, "
+                          "log_bf10_grid (log Bayes factor against mu = 0), grid_ok and n_pairs_unresolved behind the "
+                          "importance columns of the element table.  A target whose grid did not settle (grid_ok 0) or "
+                          "with a (replicate, guide) pair the quadrature rule does not resolve has empty columns.  The "
+                          "zoom follows one peak: a second mode of mu outside the final box is not detected.  No refit; "
+                          "the other tables do not change.  Sorting variant screens only; not with --scale-by-acc.")
+    own.add_argument("--grid-nodes", dest="grid_nodes", type=int, default=32, metavar="Q",
+                     help="Quadrature nodes per integral of --grid-posterior: 16, 32 or 64 (default 32).")
     own.add_argument("--bootstrap", dest="bootstrap", type=_non_negative_int, default=0, metavar="K",
                      help="Parametric bootstrap: after the fit of the screen, draw K screens from the fitted model on the "
                           "GPU (mu, sd and the guide noise at their fitted locations; fresh pi, Dirichlet and count draws; "
@@ -204,7 +217,7 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    from .run import importance_draws, importance_nodes, member_mode, particle_count, predictive_draws
+    from .run import grid_nodes, importance_draws, importance_nodes, member_mode, particle_count, predictive_draws
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
@@ -212,6 +225,7 @@ def check_run_switches(parser, args):
     predictive_draws(args, parser.error)
     importance_draws(args, parser.error)
     importance_nodes(args, parser.error)
+    grid_nodes(args, parser.error)
 
 
 def main(argv=None):

@@ -229,6 +229,30 @@ def importance_nodes(args, fail=_refuse):
     return nodes
 
 
+_GRID_FAMILY = ("--grid-posterior evaluates the posterior of (mu, sd) per target of the sorting variant models (Normal, "
+                "MixtureNormal) and is not available for {what}.")
+_GRID_ACC = ("--grid-posterior is not available with --scale-by-acc: the guide noise is a further latent per guide, so the "
+             "posterior of a target is not a function of (mu, sd) alone.")
+
+
+def grid_nodes(args, fail=_refuse):
+    """``--grid-posterior [--grid-nodes Q]``: the quadrature nodes of the grid posterior, or None without the flag.
+    Refused - ``fail(sentence)``, as ``member_mode`` - for every family ``--importance-check`` is refused for, with the
+    family named, and with ``--scale-by-acc``."""
+    nodes = int(getattr(args, "grid_nodes", 32) or 32)
+    if nodes not in IMPORTANCE_NODES:
+        fail(f"--grid-nodes must be one of 16, 32, 64, got {nodes}.")
+    if not getattr(args, "grid_posterior", False):
+        return None
+    if getattr(args, "library_design", None) == "tiling":
+        fail(_GRID_FAMILY.format(what="tiling screens (MultiMixtureNormal)"))
+    if getattr(args, "selection", None) == "survival":
+        fail(_GRID_FAMILY.format(what="survival screens"))
+    if getattr(args, "scale_by_acc", False):
+        fail(_GRID_ACC)
+    return nodes
+
+
 def check_guide_jackknife_switches(args) -> bool:
     """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
     return member_mode(args, only=("jackknife_guides",)) == "guides"
@@ -426,6 +450,13 @@ def main(args, return_data=False):
         why = model_run._predictive_refusal(model_run._resolve(model), ndata, world)
         if why is not None:
             raise PredictiveUnsupported(_IMPORTANCE_FAMILY.format(what=why))
+    n_grid = grid_nodes(args)
+    if n_grid:
+        from ..engine import PredictiveUnsupported
+
+        why = model_run._predictive_refusal(model_run._resolve(model), ndata, world)
+        if why is not None:
+            raise PredictiveUnsupported(_GRID_FAMILY.format(what=why))
     table_columns = {}
     save_dict = dict()
     param_history_dict_negctrl = None
@@ -490,6 +521,19 @@ def main(args, return_data=False):
             info(f"Importance-sampling check, pi integrated out ({n_nodes} nodes): psis_k_marg > 0.7 on "
                  f"{int((km > 0.7).sum())} of {km.numel()} targets ({share(km > 0.7):.1f} %); {int(left_out.sum())} of "
                  f"{km.numel()} targets ({share(left_out):.1f} %) left out as unresolved.")
+    if n_grid:
+        import torch
+
+        info(f"Grid posterior: the log joint of (mu, sd) per target on its own grid, pi integrated out ({n_grid} nodes)...")
+        summary = model_run.run_grid_posterior(model, guide, ndata, param_history_dict, nodes=n_grid)
+        grid = {k: v.detach().cpu() for k, v in summary.items()}
+        table_columns = {**table_columns, "grid": grid}
+        out_of = ~grid["grid_ok"] | (grid["n_pairs_unresolved"] > 0)
+        fitted_sd = torch.as_tensor(param_history_dict["mu_scale"]).detach().cpu().double().reshape(-1)
+        ratio = (fitted_sd / grid["mu_sd_grid"])[~out_of]
+        info(f"Grid posterior: {int(out_of.sum())} of {out_of.numel()} targets "
+             f"({100.0 * float(out_of.double().mean()) if out_of.numel() else 0.0:.1f} %) not grid_ok or unresolved; median "
+             f"mu_sd / mu_sd_grid over the others {float(ratio.median()) if ratio.numel() else float('nan'):.3f}.")
     write_result_table(
         target_info_df,
         guide_info_df,

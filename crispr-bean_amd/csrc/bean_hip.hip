@@ -31,6 +31,7 @@
 #include "bean_predictive.hpp"  // replicate counts drawn on the device (bean_hip_simulate)
 #include "bean_importance.hpp"  // per-target log importance weights (bean_hip_log_weights)
 #include "bean_importance_marg.hpp"  // ... with pi integrated out (bean_hip_log_weights_marginal)
+#include "bean_grid.hpp"  // the same log joint at given (mu, y) per target and node (bean_hip_marginal_grid)
 
 using namespace bean;
 
@@ -2995,6 +2996,88 @@ extern "C" int bean_hip_log_weights_marginal(bean_hip_ctx* c, uint64_t seed, uin
     else hipLaunchKernelGGL(k_logw_pairs_marg<false>, grid, block, lds, stream, d, la, ma);
     hipLaunchKernelGGL(k_logw_targets_marg, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
                        stream, d, la);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ the log joint on a grid of (mu, y) per target
+// (bean_grid.hpp) lj of n_mu * n_y given nodes per target, pi integrated out: four launches per call whatever the grid
+// (the pairs' constants, the unresolved pairs per target, the pairs' terms, the targets).  No seed, no draw, no term of
+// q; nothing of the handle is written.
+extern "C" int bean_hip_marginal_grid(bean_hip_ctx* c, int32_t n_nodes, int32_t n_mu, int32_t n_y, const void* centre_mu,
+                                      const void* centre_y, const void* step_mu, const void* step_y, void* lj_out,
+                                      uint64_t lj_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
+                                      uint64_t unresolved_bytes, void* stream_) {
+    if (!c) return fail("bean_hip_marginal_grid: null handle");
+    if (!predictive_shape_ok(c))
+        return fail("bean_hip_marginal_grid: the grid posterior does not take this handle "
+                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
+                    "covariates, one member, one particle");
+    if (!c->prepared) return fail("bean_hip_marginal_grid: call bean_hip_prepare first");
+    if (c->shape.flags & BEAN_FLAG_SCALE_BY_ACC)
+        return fail("bean_hip_marginal_grid: a handle with accessibility (BEAN_FLAG_SCALE_BY_ACC) is refused: the guide "
+                    "noise is a further latent per guide, so the posterior of a target is not 2-D");
+    if (n_nodes != 16 && n_nodes != 32 && n_nodes != 64)
+        return fail("bean_hip_marginal_grid: n_nodes must be 16, 32 or 64, got " + std::to_string(n_nodes));
+    if (n_mu < 1 || n_y < 1 || (int64_t)n_mu * n_y > BEAN_HIP_MAX_LOGW_DRAWS)
+        return fail("bean_hip_marginal_grid: n_mu >= 1, n_y >= 1 and n_mu * n_y <= " +
+                    std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) + ", got " + std::to_string(n_mu) + " x " +
+                    std::to_string(n_y) + " = " + std::to_string((int64_t)n_mu * n_y));
+    if (check_bound(c, false, false)) return -1;
+    const DevArgs& d = c->d;
+    const int N = n_mu * n_y;
+    const uint64_t nt = (uint64_t)N * d.T, np = (uint64_t)N * d.R * d.G;
+    if (!centre_mu || !centre_y || !step_mu || !step_y)
+        return fail("bean_hip_marginal_grid: centre_mu, centre_y, step_mu and step_y must each hold (T) float64 on the "
+                    "device; one of them is null");
+    const std::string sn = " float64 with N = n_mu * n_y = " + std::to_string(N) + ", ";
+    if (!lj_out || lj_bytes != 8 * nt)
+        return fail("bean_hip_marginal_grid: lj_out must hold (N, T)" + sn + std::to_string(8 * nt) + " bytes");
+    if (!pair_out || pair_bytes != 8 * np)
+        return fail("bean_hip_marginal_grid: pair_out (caller-owned scratch) must hold (N, R, G)" + sn +
+                    std::to_string(8 * np) + " bytes");
+    if (!unresolved_out || unresolved_bytes != 4 * (uint64_t)d.T)
+        return fail("bean_hip_marginal_grid: unresolved_out must hold (T) int32 (N = " + std::to_string(N) + "), " +
+                    std::to_string(4 * (uint64_t)d.T) + " bytes");
+    hipStream_t stream = (hipStream_t)stream_;
+    LogwArgs la;
+    la.first_draw = 0;
+    la.n_draws = N;
+    la.logw_out = nullptr;
+    la.mu_out = nullptr;
+    la.y_out = nullptr;
+    la.pair_out = (double*)pair_out;
+    GridArgs ga;
+    ga.n_mu = n_mu;
+    ga.n_y = n_y;
+    ga.centre_mu = (const double*)centre_mu;
+    ga.centre_y = (const double*)centre_y;
+    ga.step_mu = (const double*)step_mu;
+    ga.step_y = (const double*)step_y;
+    ga.lj_out = (double*)lj_out;
+    ga.pair_out = (double*)pair_out;
+    MargArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.n_nodes = n_nodes;
+    ma.unresolved_out = (int*)unresolved_out;
+    gauss_hermite_half(n_nodes, ma.x, ma.lw);
+    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)((N + kGridChunk - 1) / kGridChunk)),
+        block(64);
+    const size_t lds = logw_marg_lds(d.B);
+    const uint64_t rg = (uint64_t)d.R * d.G;
+    hipLaunchKernelGGL(k_logw_consts, dim3((unsigned)((rg + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
+                       la);
+    if (d.family == kMixture) {
+        hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
+                           stream, d, ma);
+        hipLaunchKernelGGL(k_grid_pairs<kMixture>, grid, block, lds, stream, d, ga, ma);
+    } else {
+        // no pi to integrate out, and no pair is unresolved
+        HIP_OK(hipMemsetAsync(unresolved_out, 0, unresolved_bytes, stream));
+        hipLaunchKernelGGL(k_grid_pairs<kNormal>, grid, block, lds, stream, d, ga, ma);
+    }
+    hipLaunchKernelGGL(k_grid_targets, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream,
+                       d, ga);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -1023,6 +1023,80 @@ class HipSVI:
             out["pairs"] = self._to_screen_order(plane, 2)
         return out
 
+    def marginal_grid(self, centre_mu, centre_y, step_mu, step_y, n_mu: int, n_y: int, nodes: int = 32,
+                      pairs: bool = False) -> Dict[str, torch.Tensor]:
+        """The log joint of every target on its own ``n_mu x n_y`` grid of given ``(mu_t, y_t = log sd_t)``, ``pi``
+        integrated out of the model by ``nodes``-point quadrature (``bean_hip_marginal_grid``): node (i, k) of target t
+        is ``mu = centre_mu[t] + (i - (n_mu - 1) / 2) step_mu[t]``, ``y = centre_y[t] + (k - (n_y - 1) / 2) step_y[t]``
+        (four tensors of T values, float64).  Returns ``lj`` (n_mu, n_y, T), a float64 device tensor - the log joint as
+        a density in ``(mu, y)``: no draw, no seed, no term of the guide - ``n_unresolved`` (T, int32: the pairs of the
+        target at which the rule is not valid; its values are not to be used) and, with ``pairs``, the pair planes
+        ``pairs`` (n_mu, n_y, R, G), guides in screen order.
+
+        Nodes go to the library in chunks whose pair plane stays at or below ``LOGW_PAIR_BYTES``: the whole grid, or
+        one line of ``mu`` per call, or one node per call.  A line or node is sent as a grid of one with its coordinate
+        as the centre, which the library's formula returns as it is, so a node's value is the same bits whatever the
+        chunking.  Nothing of the fit is written; ``run(resume=True)`` continues its window."""
+        if getattr(self.lib, "bean_hip_marginal_grid", None) is None:
+            raise PredictiveUnsupported("this library build has no bean_hip_marginal_grid")
+        if not self.predictive_supported or self.scale_by_accessibility:
+            raise PredictiveUnsupported(f"the grid posterior does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ''}"
+                                        f"{', accessibility' if self.scale_by_accessibility else ''}): sorting variant "
+                                        "Normal / MixtureNormal, unsharded, no sample covariates, one member, one "
+                                        "particle, no accessibility")
+        if int(nodes) not in _lib.MARGINAL_NODES:
+            raise ValueError(f"marginal_grid: nodes must be one of {_lib.MARGINAL_NODES} quadrature nodes, got {nodes!r}")
+        n_mu, n_y = int(n_mu), int(n_y)
+        if n_mu < 1 or n_y < 1 or n_mu * n_y > _lib.MAX_LOGW_DRAWS:
+            raise ValueError(f"marginal_grid: n_mu >= 1, n_y >= 1 and n_mu * n_y <= {_lib.MAX_LOGW_DRAWS}, got "
+                             f"{n_mu} x {n_y}")
+        R, G, T = self.data.n_reps, self.data.n_guides, int(self.T)
+        dev = self.device
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        nb = lambda t: t.numel() * t.element_size()
+        # Every tensor a library call reads or writes is formed HERE, on the caller's current stream: _on_stream() makes
+        # the engine's stream wait for what is queued on the current stream when the scope is entered, and nothing else
+        # orders torch's work before the library's launches.
+        arrs = []
+        for name, v in (("centre_mu", centre_mu), ("centre_y", centre_y), ("step_mu", step_mu), ("step_y", step_y)):
+            v = torch.as_tensor(v, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+            if v.numel() != T:
+                raise ValueError(f"marginal_grid: {name} must hold one value per target ({T}), got {v.numel()}")
+            arrs.append(v)
+        c_mu, c_y, s_mu, s_y = arrs
+        N = n_mu * n_y
+        per_node = 8 * R * G
+        whole = N * per_node <= self.LOGW_PAIR_BYTES
+        by_line = not whole and n_y * per_node <= self.LOGW_PAIR_BYTES
+        lj = torch.empty((n_mu, n_y, T), dtype=torch.float64, device=dev)
+        n_chunk = N if whole else (n_y if by_line else 1)
+        plane = torch.empty((n_mu, n_y, R, G) if pairs else (n_chunk, R, G), dtype=torch.float64, device=dev)
+        unresolved = torch.empty(T, dtype=torch.int32, device=dev)
+        # the library's coordinates of a line or node, two roundings each (a product, a sum)
+        mus = [] if whole else [c_mu + s_mu * (i - (n_mu - 1) / 2.0) for i in range(n_mu)]
+        ys = [] if whole or by_line else [c_y + s_y * (k - (n_y - 1) / 2.0) for k in range(n_y)]
+
+        def call(cm, cy, nm, ny, out, pl):
+            self._check(self.lib.bean_hip_marginal_grid(self._h, int(nodes), nm, ny, ptr(cm), ptr(cy), ptr(s_mu),
+                                                        ptr(s_y), ptr(out), nb(out), ptr(pl), nb(pl), ptr(unresolved),
+                                                        nb(unresolved), self._sptr()), "marginal_grid")
+
+        with self._on_stream():
+            if whole:
+                call(c_mu, c_y, n_mu, n_y, lj, plane)
+            else:
+                for i in range(n_mu):
+                    if by_line:
+                        call(mus[i], c_y, 1, n_y, lj[i], plane[i] if pairs else plane)
+                    else:
+                        for k in range(n_y):
+                            call(mus[i], ys[k], 1, 1, lj[i, k:k + 1], plane[i, k:k + 1] if pairs else plane)
+        out = {"lj": lj, "n_unresolved": unresolved}
+        if pairs:
+            out["pairs"] = self._to_screen_order(plane, 3)
+        return out
+
     def run_ensemble(self, n_steps: int, seeds, graph_chunk: int = 50, first_step: Optional[int] = None):
         """Enqueue ``n_steps`` SVI steps of all ``n_members`` fits, member k with ``seeds[k]`` (no host
         synchronisation).  Member k is, bit for bit, a single engine's ``run(n_steps, seed=seeds[k])``;

@@ -191,6 +191,7 @@ def write_result_table(
     design: Optional[dict] = None,
     power: Optional[dict] = None,
     importance: Optional[dict] = None,
+    grid: Optional[dict] = None,
 ) -> Union[pd.DataFrame, None]:
     """Combine target information and fitted scores into the element table (written
     or returned) and write the sgRNA table (``bean/model/readwrite.py:49-215``: same arguments, columns, row order
@@ -241,7 +242,13 @@ def write_result_table(
     on the scale of ``mu``, not rescaled), after those of a member set; every other column and the sgRNA table are those
     of the run without it, and with ``None`` every file is byte for byte what it was.  Where the summary also holds the
     marginal check (``marginal_summary``: ``pi`` integrated out), ``psis_k_marg``, ``mu_is_marg``, ``mu_sd_is_marg``,
-    ``is_ess_marg`` (empty for a target with unresolved pairs) and ``n_pairs_unresolved`` follow behind them."""
+    ``is_ess_marg`` (empty for a target with unresolved pairs) and ``n_pairs_unresolved`` follow behind them.
+
+    ``grid`` (a grid posterior, ``model/grid_posterior.py::grid_posterior``): the element table gets the columns
+    ``mu_grid``, ``mu_sd_grid``, ``sd_grid``, ``p_mu_pos_grid``, ``log_evidence_grid``, ``log_bf10_grid`` (on the scale of
+    ``mu``, not rescaled; empty where ``grid_ok`` is 0 or the target has unresolved pairs), ``grid_ok`` (0 / 1) and, unless
+    the marginal importance check has already written it, ``n_pairs_unresolved`` - behind the importance columns; with
+    ``None`` every file is byte for byte what it was."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -294,6 +301,12 @@ def write_result_table(
             _add_summary_columns(element, importance, "the marginal importance-sampling summary",
                                  ("psis_k_marg", "mu_is_marg", "mu_sd_is_marg", "is_ess_marg"), None,
                                  "n_pairs_unresolved", count_per_target=True)
+    if grid is not None:
+        _add_summary_columns(element, grid, "the grid posterior summary",
+                             ("mu_grid", "mu_sd_grid", "sd_grid", "p_mu_pos_grid", "log_evidence_grid", "log_bf10_grid"),
+                             None, "grid_ok", count_per_target=True)
+        if "n_pairs_unresolved" not in element.columns:
+            element["n_pairs_unresolved"] = _flat(grid["n_pairs_unresolved"]).astype(np.int64)
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

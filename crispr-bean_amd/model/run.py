@@ -495,6 +495,40 @@ def run_importance_check(model, guide, data, param_store, n_draws: int = 1000, s
     return summary
 
 
+def run_grid_posterior(model, guide, data, param_store, nodes: int = 32):
+    """Grid posterior of ``(mu, sd)`` per target (``model/grid_posterior.py``): an engine for ``data`` with the fitted
+    parameters of ``param_store`` loaded - they place the first zoom box and nothing else - and the summary of the log
+    joint on every target's own grid, ``pi`` integrated out by ``nodes``-point quadrature: ``mu_grid``, ``mu_sd_grid``,
+    ``sd_grid``, ``p_mu_pos_grid``, ``log_evidence_grid``, ``log_bf10_grid`` (NaN where ``grid_ok`` is false),
+    ``grid_ok``, ``n_pairs_unresolved`` and the diagnostics (a dict of device tensors).  No refit.
+
+    Raises ``PredictiveUnsupported`` - the message names the reason - for tiling and survival screens,
+    ``ControlNormal``, sample covariates, several ranks and accessibility scaling."""
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+    from .grid_posterior import grid_posterior
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _predictive_refusal(spec, data, world)
+    if why is None and spec.get("scale_by_accessibility", False):
+        why = f"fits with accessibility scaling ({spec.family}): the guide noise is a further latent per guide"
+    if why is not None:
+        raise PredictiveUnsupported(f"a grid posterior is not available for {why}: the posterior of a target is a "
+                                    "function of (mu, sd) alone in the sorting variant Normal and MixtureNormal models "
+                                    "without accessibility, on one GPU")
+    device = torch.device("cuda", torch.cuda.current_device())
+    eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
+    try:
+        load_parameters(eng, param_store)
+        summary = grid_posterior(eng, nodes=int(nodes))
+        torch.cuda.synchronize(device)
+    finally:
+        eng.close()
+    return summary
+
+
 def bootstrap_engine(model, guide, data, param_store) -> HipSVI:
     """The engine a parametric bootstrap draws its screens from: built for ``data`` as ``run_posterior_predictive``
     builds its own, the fitted parameters of ``param_store`` loaded, and zero standard-normal draws injected into every

@@ -578,6 +578,43 @@ int bean_hip_log_weights_marginal(bean_hip_ctx* ctx, uint64_t seed, uint64_t fir
                                   uint64_t y_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
                                   uint64_t unresolved_bytes, void* stream);
 
+/* The log joint of every target on a grid of GIVEN (mu_t, y_t = log sd_t), pi integrated out of the model: the device
+ * side of the grid posterior of (mu, sd) per target (posterior mean and sd of mu without a mean-field assumption,
+ * P(mu > 0 | x), log evidence).  In the sorting variant families the targets share no parameter,
+ * so with pi integrated out the posterior of a target is a function of two numbers.
+ *
+ *   bean_hip_marginal_grid        takes the handles bean_hip_predictive_supported takes, without accessibility.
+ *                                 N = n_mu * n_y nodes per target; node n = i * n_y + k of target t is
+ *                                     mu = centre_mu[t] + (i - (n_mu - 1) / 2) * step_mu[t]
+ *                                     y  = centre_y[t]  + (k - (n_y - 1) / 2) * step_y[t]
+ *                                 formed in float64: every target has its own affine grid.  centre_mu, centre_y, step_mu
+ *                                 and step_y are DEVICE float64 arrays of T.  No seed, no draw, no term of q.
+ *                                     lj_out[n, t] = log p(mu) + log p(sd) + y
+ *                                                  + sum_g nrg_g (lgamma(c_p0 + c_p1) - lgamma(c_p0) - lgamma(c_p1))
+ *                                                  + sum_r sum_g ( const[r, g] + [rg] log int f(pi) dpi ),
+ *                                 the log joint of the target as a density in (mu, y): the priors are those of the fit
+ *                                 (BEAN_BUF_PRIOR_* included), const, f, the n_nodes-point rule (16, 32 or 64) and its
+ *                                 validity predicate those of bean_hip_log_weights_marginal.  BEAN_FAMILY_NORMAL has no
+ *                                 pi: a pair's term is its likelihood term, and unresolved_out is zeroed.
+ *                                 pair_out: caller-owned scratch of (N, R, G) float64, required; afterwards
+ *                                 pair_out[n, r, g] holds the pair's data-only constants plus, under the repguide mask,
+ *                                 its term at node n.  unresolved_out: as bean_hip_log_weights_marginal's.
+ *                                 Launches: k_logw_consts, k_logw_unresolved (MixtureNormal), k_grid_pairs,
+ *                                 k_grid_targets, whatever N.
+ *                                 State: nothing of the handle is written - no parameters, moments, gradients,
+ *                                 loss_hist, workspace or seed; a following bean_hip_svi_resume continues its window.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched, the handle stays usable): a null handle; a
+ * handle that is not supported (the message names bean_hip_predictive_supported), not prepared, or has accessibility
+ * (the message says so: with it the guide noise is a further latent per guide and the posterior is not 2-D); n_nodes
+ * other than 16, 32, 64; n_mu or n_y below 1 or n_mu * n_y above BEAN_HIP_MAX_LOGW_DRAWS (the message states both and
+ * the limit); a null array; byte counts other than 8 N T (lj_out), 8 N R G (pair_out) and 4 T (unresolved_out) - the
+ * message states N and the bytes expected. */
+int bean_hip_marginal_grid(bean_hip_ctx* ctx, int32_t n_nodes, int32_t n_mu, int32_t n_y, const void* centre_mu,
+                           const void* centre_y, const void* step_mu, const void* step_y, void* lj_out, uint64_t lj_bytes,
+                           void* pair_out, uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
+                           void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
