@@ -72,8 +72,9 @@
 // batch: 45.59 - 45.75 / 44.09 - 44.42; the final build 45.42 - 45.71 / 44.13 - 44.29, -3.0 %; 20 steps after 5: 49.91 - 50.34 /
 // 48.67 - 48.96.  Not adopted: the same
 // one-load form for the FINISHERS' poll (async_finish_tile) - 44.09 - 44.51 without / 44.78 - 44.99 with it: the finisher
-// waves poll twice as often and take issue slots from their SIMD's item waves.  Not built: the targets' next-step
-// normals and ue_idx / ue_z ahead of the ring poll.
+// waves poll twice as often and take issue slots from their SIMD's item waves.  The targets' next-step normals, ue_idx /
+// ue_z, tdesc and - behind a gate - the first pass's state ahead of the ring poll: async_finish_tile, "the targets' part
+// ahead of the poll".
 //
 // Order and progress.  The queue is one counter per XCD group (blockIdx & 7, a label: the blocks that share a label
 // share an L2; nothing depends on it but speed), items in (step, tile, replicate) order; tile k belongs to group
@@ -196,6 +197,8 @@ struct AsyncArgs {
     // tile fills the tile's position(s) of its group's finish ring instead of finishing it itself
     int n_guide_blocks;        // 0: every wave pulls items and the last arriver finishes (no roles)
     int fin_split;             // 1: a tile's finish is two ring positions (targets, guides); 0: one
+    int early;                 // the targets' part ahead of a finisher's poll (BEAN_HIP_ASYNC_EARLY): 0 none, 1 static
+                               // inputs and - gate open - the state, 2 static inputs only
     int* fhead;                // [8 * kAsyncQueueStride] next ring position a finisher takes
     int* fring;                // [8 * fring_stride] by position (async_fin_pos): local step + 1 once the tile is complete; 0 = not yet
     long fring_stride;
@@ -303,17 +306,61 @@ __device__ __forceinline__ void async_give_up(const DevArgs* cp, const AsyncArgs
 // matched, as before: the arithmetic and the order of every addition are unchanged, only when three lookups are made
 // moves.  A finish that is taken when it is already filled (wait_slot = nullptr: the last arriver without roles, a
 // waiting item wave that takes the oldest filled position) runs prepare inline.
+//
+// The targets' part ahead of the poll (AsyncArgs::early, BEAN_HIP_ASYNC_EARLY at create: 1 the default, 0 the order
+// before it, 2 the static half only).  A finisher with a position in hand also stages, in its own LDS, what the first
+// pass of 16 targets and the Phi phase read that no wave of any launch writes - tdesc, the next draw's Philox /
+// Box-Muller normals (target index and step: known from the position), ue_idx and ue_z - and, behind a GATE, the first
+// pass's state (p / m / v of the lane's parameter, p[1], p[3], eps_mu, eps_sd, mu_t, y_t) with what follows from it
+// alone (tgt_prior_terms, exp(p_j)).  That state was written by the finish of step s - 1 of this tile, or of a neighbour
+// for a straddling target, and is final once done[] shows that step finished.  The gate is ONE load of every lane, the
+// form of the items' poll, issued in front of the prepare's other loads: done[2 tile] and, where a target straddles,
+// done[2 (tile -+ 1)].  It is looked at ONCE.  Every needed word >= the local step s (trivially at a call's first step:
+// k_async_head zeroed the words, the state comes from the previous call in stream order): the state loads go out at
+// agent scope after the gate's load has returned - the items' visibility rule.  Not so: the state takes the path after
+// the ring poll, as before.  There is no new wait and no new poll loop, so the progress argument above holds word for
+// word.  No arithmetic operation, operand or order of addition changes; a straddling target that the boundary counter
+// then gives to the neighbour is not looked up (it adds no loss term and stores nothing, as before); passes beyond the
+// first, tsum, the boundary counters and the loss parts are never touched before the ring word has matched
+// (tests/test_gpu_async_finish_early.py: parameters equal to the pair path under all three settings).
+// Measured at the metric shape (profiles/r09_*; bench.py, 2 000 steps, five alternating runs, us per step): parent 43.55 -
+// 43.72, this form 43.03 - 43.20 (every run faster, -1.1 %), =2 43.00 - 43.25, =0 43.15 - 43.48; 20 steps after 5: 47.74 -
+// 47.99 / 47.44 - 47.73.  Most of the step's gain is not the prefetch: the finish now takes its lane index through
+// w2_lane_here, so nothing it derives from the lane is hoisted in front of the item loop (k_svi_async<2, false> 128 ->
+// 124 VGPRs, <2, true> 2 spilled -> none), and =0 alone is 0.3 us faster than the parent.  Stamp builds
+// (r09_async_timeline_50000_*.json, medians): the targets' part 8.04 -> 7.32 us, of it sums / Adam / draw 2.92 -> 2.40
+// and the Phi phase 2.76 -> 2.72 (the three ue_idx / ue_z round trips were already hidden under its exp); tile complete
+// -> last part published 9.60 -> 8.84.  With =2 the targets' part is the parent's (8.08): the static half alone buys
+// nothing, the state does.  A first form chose per LANE between slot and late path (a pass that starts at t0 + 1 did
+// not find its sixteenth target): every load of the late path then sat under a lane condition and was waited for where
+// it ended - the targets' part with =0 went from 8.08 to 9.28 us and the step showed no gain (43.44 - 43.73 against
+// 43.45 - 43.88); hence seventeen slots and wave-uniform conditions.  Not built here: the guides' part ahead of the
+// poll (param_guide_mix in two halves), the loss parts parked in LDS, the loss atomics behind phase A, a new grid table.
 // Returns kAsyncFinDone, or why the wave must leave: the abort word was seen, or the poll ran out.
 constexpr int kAsyncFinDone = 0, kAsyncFinLeave = 1, kAsyncFinGaveUp = 2;
 template <int FAM, bool ACC>
 __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned long long step, unsigned long long slot,
                                               float step_size, int tile, int part, const int* wait_slot,
-                                              const int* abort_flag BEAN_ASYNC_ST_ARG) {
+                                              const int* abort_flag, const int* done, int s_local, int n_tiles,
+                                              int early BEAN_ASYNC_ST_ARG) {
     // part: 1 = the tile's targets (sums, priors, ClippedAdam, draw, Phi tables; the R waves' loss parts), 2 = its guides
     // (alpha_pi, the noise site, digamma tables), 3 = both.  The two do not depend on each other: with finisher roles they
     // are two positions of the finish ring and run on two waves at the same time.
     // (the tile's next step waits for this chain: it goes first on its SIMD - but not while it only polls)
     if (BEAN_ASYNC_PRIO && !wait_slot) __builtin_amdgcn_s_setprio(3);
+    // ---- the gate of the early targets' part (header, "PREPARE and COMPLETE"): ONE load, every lane, the form of the
+    // items' poll, issued in front of everything else the prepare asks for - lane 0 the targets' word of this tile, lanes
+    // 1 / 2 of its two neighbours (clamped; needed only where a target straddles that boundary), the others this tile's
+    // word, dropped.  Looked at once, below; nothing waits for it to change.
+    const bool try_early = wait_slot != nullptr && early != 0 && (part & 1) != 0;
+    int gate_w = 0;
+    if (try_early && early == 1) {
+        const int ln = w2_lane_here();  // (not followed back to threadIdx.x: nothing derived from it is hoisted out of the loop)
+        const int q = ln == 1 ? tile - 1 : (ln == 2 ? tile + 1 : tile);
+        const int qc = q < 0 ? 0 : (q >= n_tiles ? n_tiles - 1 : q);
+        gate_w = __hip_atomic_load(done + 2 * qc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("" ::: "memory");  // (the gate's load is issued above this line)
+    }
     const DevArgs c = dev_args_in_sgprs(cp);
     part = rfl_i(part);
     step = rfl_u64(step);
@@ -339,13 +386,93 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
     constexpr bool MIX = FAM == kMixture;
     constexpr int COH = 2;
     extern __shared__ double tabs[];
-    const int lane = threadIdx.x, R = c.R, G = c.G, B = c.B;
+    // (the lane index as a value the compiler does not follow back to threadIdx.x, w2_lane_here: what the finish derives
+    // from it is computed here and not in front of the item loop, where it would stay live across every item)
+    const int lane = w2_lane_here(), R = c.R, G = c.G, B = c.B;
     const int t1 = t0 + nt - 1;
     int tof0, tof1;
     {
         const int tv = c.toff[lane == 0 ? t0 : t1 + 1];
         tof0 = __builtin_amdgcn_readlane(tv, 0);
         tof1 = __builtin_amdgcn_readlane(tv, 1);
+    }
+    const int g_first = tile * 64 - c.g_sh > 0 ? tile * 64 - c.g_sh : 0;
+    const int g_last = tile * 64 + 63 - c.g_sh < G ? tile * 64 + 63 - c.g_sh : G - 1;
+    const bool left_str = tof0 < g_first;
+    const bool right_str = tof1 > g_last + 1;
+    // ---- the targets' part ahead of the poll.  What the first pass of 16 targets and the Phi phase read that no wave of
+    // any launch writes goes into the wave's LDS now: the distinct bin edges (ue_z, ue_idx) behind the Phi phase's three
+    // tables, and per lane - slot (t - t0) * 4 + j, the targets t0 ... t0 + 16 - the target's descriptor and the normal
+    // of its next draw (Philox keyed by the target and the step: known from the position).  Gate open (every needed
+    // completed-step word of step s - 1 seen): the lane's state is loaded too, at agent scope and after the gate's load
+    // has returned - the items' visibility rule - and what follows from it alone is computed: the prior terms, the
+    // entropy terms, exp(p_j).  Gate not open, or BEAN_HIP_ASYNC_EARLY=2: the state takes the path after the poll, as
+    // before.  Which of t0 / t0 + 1 the first pass starts at is known only after the boundary counters, so COMPLETE looks
+    // its target up by t - t0; a straddling target the counter gives to the neighbour is simply not looked up.  The slots
+    // lie over the Phi phase's tables (free until every pass is through) and the LDS behind them: nothing is held in
+    // registers across the poll.  Sums, boundary counters and loss parts are not touched here.
+    // Seventeen targets have slots: a first pass that starts at t0 + 1 ends at t0 + 16, whose four slots lanes 0 - 3 fill
+    // in a second round where the tile has a left straddler (the only case in which the pass can start there).
+    constexpr int kEarlyN = 68, kEarlySlots = 128, kEarlyUe = 608;  // doubles from tabs: 7 x 68 per-lane slots, then the bin edges
+    double* const es_eps = tabs + kEarlySlots;        // the draw's standard normal of parameter j's site
+    double* const es_dlp = es_eps + kEarlyN;          // d log p / d (mu or y)
+    double* const es_lt = es_dlp + kEarlyN;           // the target's prior / entropy loss term
+    double* const es_exp = es_lt + kEarlyN;           // exp(p_j)
+    float* const es_p = (float*)(es_exp + kEarlyN);   // p_j, m_j, v_j, the next draw's normal: kEarlyN floats each
+    int2* const es_dsc = (int2*)(es_exp + kEarlyN + 2 * kEarlyN);
+    double* const ue_zs = tabs + kEarlyUe;
+    int* const ue_is = (int*)(ue_zs + 2 * B);
+    bool pre_static = false, pre_state = false;
+    if (try_early && guide_wave2_lds(B, c.tile_targets) >= (size_t)(kEarlyUe + 2 * B) * sizeof(double) + (size_t)(2 * B + 1) * sizeof(int)) {
+        pre_static = true;
+        const int ln = w2_lane_here();  // (as above: the slots' addresses are computed here, not in front of the item loop)
+        const int j = ln & 3;
+        if (early == 1) {
+            const bool need = ln == 0 || (ln == 1 && left_str && tile > 0) || (ln == 2 && right_str && tile + 1 < n_tiles);
+            pre_state = __all(!need || gate_w >= s_local);
+        }
+        asm volatile("" ::: "memory");  // (no state load is issued before the gate's answer has been looked at)
+        for (int i = ln; i < 2 * B; i += 64) ue_zs[i] = c.ue_z[i];
+        for (int i = ln; i <= 2 * B; i += 64) ue_is[i] = c.ue_idx[i];
+        // slot `sl` <- target tp
+        auto prep = [&](int sl, int tp) {
+            float pj = 0.f, mj = 0.f, vj = 0.f, p1 = 0.f, p3 = 0.f;
+            double eps1 = 0.0, eps2 = 0.0, mu = 0.0, y = 0.0;
+            if (pre_state) {
+                const float* const P = j == 0 ? c.p[0] : (j == 1 ? c.p[1] : (j == 2 ? c.p[2] : c.p[3]));
+                const float* const M = j == 0 ? c.m[0] : (j == 1 ? c.m[1] : (j == 2 ? c.m[2] : c.m[3]));
+                const float* const V = j == 0 ? c.v[0] : (j == 1 ? c.v[1] : (j == 2 ? c.v[2] : c.v[3]));
+                pj = coh_ld<COH>(P + tp), mj = coh_ld<COH>(M + tp), vj = coh_ld<COH>(V + tp);
+                p1 = coh_ld<COH>(c.p[1] + tp), p3 = coh_ld<COH>(c.p[3] + tp);
+                eps1 = coh_ld<COH>(c.eps_mu + tp), eps2 = coh_ld<COH>(c.eps_sd + tp);
+                mu = coh_ld<COH>(c.mu_t + tp), y = coh_ld<COH>(c.y_t + tp);
+            }
+            int2 dsc;
+            dsc.x = 0;
+            dsc.y = 2;
+            if (!c.tsum_direct) dsc = c.tdesc[tp];
+            const float2 nrm = normal2_at(c.seed, ((unsigned long long)kSiteTarget << 48) + (unsigned long long)(c.t_off + tp),
+                                          (step + 1) * 4ull);
+            es_p[3 * kEarlyN + sl] = j < 2 ? nrm.x : nrm.y;
+            es_dsc[sl] = dsc;
+            if (pre_state) {
+                double dlogp_mu, dlogp_dy, lt;
+                tgt_prior_terms(c, tp, tgt_sd_prior(c, tp), mu, y, eps1, eps2, p1, p3, dlogp_mu, dlogp_dy, lt);
+                es_eps[sl] = j < 2 ? eps1 : eps2;
+                es_dlp[sl] = j < 2 ? dlogp_mu : dlogp_dy;
+                es_lt[sl] = lt;
+                es_exp[sl] = exp((double)pj);
+                es_p[sl] = pj;
+                es_p[kEarlyN + sl] = mj;
+                es_p[2 * kEarlyN + sl] = vj;
+            }
+        };
+        const int rounds = left_str && t0 + 16 <= t1 ? 2 : 1;
+#pragma clang loop unroll(disable)
+        for (int rd = 0; rd < rounds; ++rd) {
+            const int k = rd * 16 + (ln >> 2);
+            if (rd == 0 || ln < 4) prep(k * 4 + j, t0 + k < t1 ? t0 + k : t1);
+        }
     }
     // ---- prepared: now wait until the tile's last wave has arrived (lane 0 polls the position's word, lane 1 the abort
     // word; bounded).  The rows, sums and loss parts of all R waves had completed before the arrival that filled the word,
@@ -371,10 +498,6 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
     AdamCoef ak;
     ak.step_size = ctr.step_size;
     ak.clip = (float)c.clip;
-    const int g_first = tile * 64 - c.g_sh > 0 ? tile * 64 - c.g_sh : 0;
-    const int g_last = tile * 64 + 63 - c.g_sh < G ? tile * 64 + 63 - c.g_sh : G - 1;
-    const bool left_str = tof0 < g_first;
-    const bool right_str = tof1 > g_last + 1;
     // Which wave finishes a straddling target depends on timing, so the prior / entropy terms are not added up as
     // doubles per wave: every TERM goes into the loss's fixed-point form by itself (fixed_add's split) and the wave
     // adds integers - the loss history is bitwise reproducible run to run, whoever finished what.
@@ -415,19 +538,32 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
         float* const M = j == 0 ? c.m[0] : (j == 1 ? c.m[1] : (j == 2 ? c.m[2] : c.m[3]));
         float* const V = j == 0 ? c.v[0] : (j == 1 ? c.v[1] : (j == 2 ? c.v[2] : c.v[3]));
         for (int base = ta; base <= tb; base += 16) {
+            // The first pass takes what PREPARE left in the slots, slot (t - t0) * 4 + j (a pass that starts at t0 + 1 finds
+            // its targets four slots up): `pre` the descriptor and the normal, `pre_s` the state too, with what follows from
+            // it alone.  Both are wave-uniform - a load under a LANE condition is waited for where the condition ends -
+            // and with neither set everything is asked for here, in the order it had before there was a PREPARE.
+            const bool pre = pre_static && base == ta, pre_s = pre && pre_state;
             const int t = base + (lane >> 2);
             const bool act = t <= tb;
             const int tc = act ? t : tb;
+            const int es = (tc - t0) * 4 + j;
             int2 dsc;
             dsc.x = 0;
             dsc.y = 2;
-            if (!c.tsum_direct) dsc = c.tdesc[tc];
+            if (pre) dsc = es_dsc[es];
+            else if (!c.tsum_direct) dsc = c.tdesc[tc];
             const int n = dsc.y * R, ntm = c.tile_targets;
             const long S = c.tsum_direct ? 2 * (long)c.T : (long)c.n_tiles * ntm;
-            float pj = coh_ld<COH>(P + tc), mj = coh_ld<COH>(M + tc), vj = coh_ld<COH>(V + tc);
-            const float p1 = coh_ld<COH>(c.p[1] + tc), p3 = coh_ld<COH>(c.p[3] + tc);
-            const double eps1 = coh_ld<COH>(c.eps_mu + tc), eps2 = coh_ld<COH>(c.eps_sd + tc);
-            const double mu = coh_ld<COH>(c.mu_t + tc), y = coh_ld<COH>(c.y_t + tc);
+            float pj = 0.f, mj = 0.f, vj = 0.f, p1 = 0.f, p3 = 0.f;
+            double eps1 = 0.0, eps2 = 0.0, mu = 0.0, y = 0.0;
+            double epsj = 0.0, dlogp = 0.0, lt = 0.0, spj = 0.0;  // eps / d log p of parameter j's site, loss term, exp(p_j)
+            // (prepared state is taken from its slots behind the sums: nothing more is live across their loads than before)
+            if (!pre_s) {
+                pj = coh_ld<COH>(P + tc), mj = coh_ld<COH>(M + tc), vj = coh_ld<COH>(V + tc);
+                p1 = coh_ld<COH>(c.p[1] + tc), p3 = coh_ld<COH>(c.p[3] + tc);
+                eps1 = coh_ld<COH>(c.eps_mu + tc), eps2 = coh_ld<COH>(c.eps_sd + tc);
+                mu = coh_ld<COH>(c.mu_t + tc), y = coh_ld<COH>(c.y_t + tc);
+            }
             // the (part, replicate) sums of the target in k_param's order (16 lanes, xor tree 8, 4, 2, 1)
             double am[4] = {0.0, 0.0, 0.0, 0.0}, ay[4] = {0.0, 0.0, 0.0, 0.0};
             const float rR = 1.0f / (float)R;
@@ -466,11 +602,19 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
             gmu += __shfl_xor(gmu, 1, 64);
             gy += __shfl_xor(gy, 1, 64);
             // FINISH of this step
-            double dlogp_mu, dlogp_dy, lt;
-            tgt_prior_terms(c, tc, tgt_sd_prior(c, tc), mu, y, eps1, eps2, p1, p3, dlogp_mu, dlogp_dy, lt);
+            if (pre_s) {
+                pj = es_p[es], mj = es_p[kEarlyN + es], vj = es_p[2 * kEarlyN + es];
+                epsj = es_eps[es], dlogp = es_dlp[es], lt = es_lt[es], spj = es_exp[es];
+            } else {
+                double dlogp_mu, dlogp_dy;
+                tgt_prior_terms(c, tc, tgt_sd_prior(c, tc), mu, y, eps1, eps2, p1, p3, dlogp_mu, dlogp_dy, lt);
+                epsj = j < 2 ? eps1 : eps2;
+                dlogp = j < 2 ? dlogp_mu : dlogp_dy;
+                spj = exp((double)pj);
+            }
             if (act && j == 0) loss_term(lt);
-            const double Gd = j < 2 ? gmu - dlogp_mu : gy - dlogp_dy;
-            const double grad = tgt_grad(j, Gd, j < 2 ? eps1 : eps2, exp((double)pj));
+            const double Gd = (j < 2 ? gmu : gy) - dlogp;
+            const double grad = tgt_grad(j, Gd, epsj, spj);
             adam_update(pj, mj, vj, (float)grad, ak);
             if (act) {
                 coh_st<COH>(P + t, pj);
@@ -478,9 +622,14 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
                 coh_st<COH>(V + t, vj);
             }
             // PREP of the next step: the draw (Philox keyed by the global target index and the step)
-            const float2 nrm = normal2_at(c.seed, ((unsigned long long)kSiteTarget << 48) + (unsigned long long)(c.t_off + tc),
-                                          s_prep * 4ull);
-            const double en = j < 2 ? (double)nrm.x : (double)nrm.y;
+            double en;
+            if (pre) {
+                en = (double)es_p[3 * kEarlyN + es];
+            } else {
+                const float2 nrm = normal2_at(c.seed, ((unsigned long long)kSiteTarget << 48) + (unsigned long long)(c.t_off + tc),
+                                              s_prep * 4ull);
+                en = j < 2 ? (double)nrm.x : (double)nrm.y;
+            }
             const float p_scale = __shfl_xor(pj, 1, 64);  // even lanes: the updated log scale of their pair
             const double val = tgt_draw(pj, en, p_scale);
             if (act && (j & 1) == 0) {
@@ -495,7 +644,12 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
     // ---- phase C: the Phi tables of the new draws (one lane per distinct finite bin edge, then one per (target, bin))
     {
 #pragma clang fp contract(off)
-        const int nue = c.ue_idx[2 * B];
+        // (the bin edges come from the wave's LDS where PREPARE staged them - three dependent round trips less - and from
+        // global memory otherwise; each read stands in front of the arithmetic it used to be scheduled over)
+        const bool staged = pre_static;
+        int nue;
+        if (staged) nue = __builtin_amdgcn_readfirstlane(ue_is[2 * B]);
+        else nue = c.ue_idx[2 * B];
         const int nu1 = nue > 0 ? nue : 1, per = 64 / nu1;
         double* const ecdf = tabs + 128;
         double* const epdf = ecdf + 64;
@@ -506,10 +660,13 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
             const bool live = grp < per && t <= tb && nue > 0;
             const int tl = live ? t - ta : 0;
             {
+                double z;
+                if (staged) z = ue_zs[live ? ue : 0];
+                else z = c.ue_z[live ? ue : 0];
                 const double mu = hmu[tl], y = hy[tl];
                 const double sigma = c.family == kNormal ? exp(0.5 * y) : exp(y);
                 const double inv = 1.0 / sigma;
-                const double u = (c.ue_z[live ? ue : 0] - mu) * inv;
+                const double u = (z - mu) * inv;
                 const double pdf = norm_pdf(u);
                 if (live) {
                     ecdf[lane] = norm_cdf(u);
@@ -521,11 +678,13 @@ __device__ BEAN_ASYNC_INLINE int async_finish_tile(const DevArgs* cp, unsigned l
             const int cnt = (tb - base + 1 < per ? tb - base + 1 : per) * B;
             for (int q = lane; q < cnt; q += 64) {
                 const int gq = q / B, b = q - gq * B, tq = base + gq;
+                int ih, il;
+                if (staged) ih = ue_is[b], il = ue_is[B + b];
+                else ih = c.ue_idx[b], il = c.ue_idx[B + b];
                 const double y = hy[tq - ta];
                 const double sigma = c.family == kNormal ? exp(0.5 * y) : exp(y);
                 const double dsig_dy = c.family == kNormal ? 0.5 * sigma : sigma;
                 const double inv = 1.0 / sigma;
-                const int ih = c.ue_idx[b], il = c.ue_idx[B + b];
                 const double ch = ih < 0 ? 1.0 : ecdf[gq * nu1 + ih], cl = il < 0 ? 0.0 : ecdf[gq * nu1 + il];
                 const double fh = ih < 0 ? 0.0 : epdf[gq * nu1 + ih], fl = il < 0 ? 0.0 : epdf[gq * nu1 + il];
                 const double uh = ih < 0 ? 0.0 : eupd[gq * nu1 + ih], ul = il < 0 ? 0.0 : eupd[gq * nu1 + il];
@@ -816,7 +975,7 @@ void k_svi_async(const DevArgs* cp, int R, int n_tiles, AsyncArgs a) {
 #endif
             const unsigned long long step = a.step0 + (unsigned long long)fin_s, slot = a.slot0 + (unsigned long long)fin_s;
             const int left = async_finish_tile<FAM, ACC>(cp, step, slot, a.step_sizes[fin_s], fin_tile, fin_part, fin_wait,
-                                                         a.abort_flag BEAN_ASYNC_ST_PASS);
+                                                         a.abort_flag, a.done, fin_s, n_tiles, a.early BEAN_ASYNC_ST_PASS);
             if (BEAN_ASYNC_PRIO) __builtin_amdgcn_s_setprio(0);
             if (left != kAsyncFinDone) {
                 if (left == kAsyncFinGaveUp && lane == 0) async_give_up(cp, a);

@@ -127,6 +127,8 @@ struct bean_hip_ctx {
     int* async_ws = nullptr;   // device: 8 queue counters (kAsyncQueueStride apart), the abort word, done[n_tiles]
     int async_blocks = 0;      // grid: resident single-wave workgroups that pull items, a multiple of 8 (0: not yet measured)
     int async_fin_blocks = 0;  // ... and that only finish tiles (0: no roles, the last arriver finishes)
+    int async_early = 1;       // the targets' part of a finish ahead of the finisher's poll (BEAN_HIP_ASYNC_EARLY at create: 0 / 1 / 2,
+                               // AsyncArgs::early; A/B and the tests' three paths)
     size_t async_ws_ints = 0;
     unsigned long long* async_stamps = nullptr;  // diagnostic builds (-DBEAN_ASYNC_STAMP): the last call's item timeline
     size_t async_stamp_words = 0;
@@ -643,6 +645,11 @@ extern "C" int bean_hip_create(const bean_hip_shape* s, bean_hip_ctx** out) {
         // =0: every implicit-gradient call forms its x-free factors itself, as before the table (A/B, same bits)
         const char* dt = getenv("BEAN_HIP_DIRGRAD_TAB");
         c->dirgrad_tab = !(dt && !strcmp(dt, "0"));
+    }
+    {
+        // =0: a finisher asks for everything after its poll, as before; =2: the static inputs ahead of it, never the state
+        const char* ae = getenv("BEAN_HIP_ASYNC_EARLY");
+        c->async_early = (ae && !strcmp(ae, "0")) ? 0 : ((ae && !strcmp(ae, "2")) ? 2 : 1);
     }
     d.trow_summed = (c->tiling_wave || c->tiling_rep) ? 1 : 0;
     {
@@ -1733,6 +1740,7 @@ static int launch_svi_async(bean_hip_ctx* c, hipStream_t stream, uint64_t step0,
     a.fring_stride = (long)fring_stride;
     a.n_guide_blocks = 0;  // (set by launch_svi_async_t, where the grid is decided)
     a.fin_split = 0;
+    a.early = c->async_early;
     a.step_sizes = c->step_sizes;
     a.stamps = nullptr;
     // queue, abort and completed-step words to zero, step sizes, the DevArgs copy, the step counters the call leaves
