@@ -3420,6 +3420,37 @@ __global__ __launch_bounds__(256) void k_test_special(int op, long n, const doub
         const DirGradTab t = dirgrad_tab_make(a[i], b[i]);
         o0[i] = dirichlet_grad_one_tab(x[i], a[i], b[i], digamma(a[i]), digamma(b[i]), t.rtot, t.sd, t.stir, t.rpf, t.t3,
                                        t.h1);
+    } else if (op >= 12 && op <= 23) {
+        // the inlined sampler with the acceptance test settled in float32 where it can be (12 - 14: FLOOR 0, 1, 2) and
+        // with the float64 test (15 - 17) - the same draws, unfloored, and (18 - 23, in o0) the same generator position
+        unsigned long long seed;
+        memcpy(&seed, &x[0], 8);
+        Rng rng(seed, kSiteAux, (unsigned long long)i, 0ull);
+        const int form = (op - 12) % 6;
+        GammaPair gp;
+        if (form == 0) gp = sample_gamma_pair_inl<0, false>(a[i], b[i], rng);
+        else if (form == 1) gp = sample_gamma_pair_inl<1, false>(a[i], b[i], rng);
+        else if (form == 2) gp = sample_gamma_pair_inl<2, false>(a[i], b[i], rng);
+        else if (form == 3) gp = sample_gamma_pair(a[i], b[i], rng);
+        else if (form == 4) gp = sample_gamma_pair_floor32(a[i], b[i], rng);
+        else gp = sample_gamma_pair_floord(a[i], b[i], rng);
+        o0[i] = op >= 18 ? (double)gp.k : gp.g0;
+        o1[i] = gp.g1;
+    } else if (op == 24) {
+        // the acceptance decision alone at (d, n, u) = (a, x, b), as the sampler's loop forms its arguments: o0 the
+        // float64 decision (-1: y <= 0, no test), o1 the float32 form's decision + 2 where float32 settled it
+        const double d = a[i], na = x[i], u = b[i];
+        const double cc = frcp(sqrt(9.0 * d));
+        const double y = 1.0 + cc * na;
+        o0[i] = -1.0;
+        o1[i] = -1.0;
+        if (y > 0.0) {
+            const double v = y * y * y, xx = na * na;
+            bool acc = false;
+            const bool settled = mt_accept_f32(u, xx, d, v, acc);
+            o0[i] = mt_accept_exact(u, xx, d, v) ? 1.0 : 0.0;
+            o1[i] = (mt_accept<false>(u, xx, d, v) ? 1.0 : 0.0) + (settled ? 2.0 : 0.0);
+        }
     }
 }
 

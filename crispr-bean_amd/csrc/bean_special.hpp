@@ -8,6 +8,11 @@
 // PREP) and read by every replicate's call: the digammas (DevArgs::dgq) and the x-free factors of the implicit
 // Dirichlet gradient's alpha > 6 && beta > 6 branch (DevArgs::dgt: DirGradTab, dirgrad_tab_make,
 // dirichlet_grad_one_tab below - six factors per component, bit-identical to forming them in the call).
+//
+// One place decides in float32: the Marsaglia-Tsang acceptance inequality of the inlined pair sampler (mt_accept).  Only
+// its outcome is used, so two hardware float32 logs and an error bound settle it for all but ~0.3 % of the lanes that
+// reach it; those take the float64 test, out of line.  Same decisions, same draws, same generator positions as the
+// float64 test everywhere (-DBEAN_MT_EXACT builds every sampler with it; the out-of-line sample_gamma_pair* keep it).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocrand/rocrand_kernel.h>
@@ -679,6 +684,57 @@ __device__ __noinline__ GammaRound gamma_round_at(unsigned long long seed, unsig
 // log in the Marsaglia-Tsang acceptance test (taken only when the squeeze test fails)
 __device__ __forceinline__ double accept_log(double x) { return flog(x); }
 
+// The acceptance test of a lane whose squeeze test failed: log u < xx / 2 + d (1 - v + log v), with
+// v = (1 + c n)^3, xx = n^2.  Only its OUTCOME is used, and in the first round some lane of a wave fails the
+// squeeze nearly always, so every wave pays for it.
+//   mt_accept_exact   the inequality in float64 (two flog: 68 float64 instructions).  Out of line on purpose:
+//                     inlined, the compiler speculates both logs into the caller's block.
+//   mt_accept_f32     settles it from two hardware float32 logs where the margin allows, and says where not.
+//   mt_accept<EXACT>  what the sampler calls: the float32 form, and the exact one behind a wave-uniform vote
+//                     for the lanes it left undecided.  Same decisions as mt_accept_exact, lane for lane.
+#ifndef BEAN_MT_EXACT  // -DBEAN_MT_EXACT: every sampler takes the float64 test (the A/B library of this form)
+#define BEAN_MT_EXACT 0
+#endif
+__device__ __forceinline__ bool mt_accept_exact_inl(double u, double xx, double d, double v) {
+    return accept_log(u) < 0.5 * xx + d * (1.0 - v + accept_log(v));
+}
+__device__ __noinline__ bool mt_accept_exact(double u, double xx, double d, double v) {
+    return mt_accept_exact_inl(u, xx, d, v);
+}
+// Returns whether float32 settled it; `acc` is the decision where it did.
+//   t = xx / 2 + d (1 - v + lv) - lu,  lu = ln 2 log2 (float)u, lv = ln 2 log2 (float)v, the log2 by v_log_f32 (the
+//   bare instruction: its arguments are normal floats here, u >= 2^-33 and v checked), all else in float64.
+// The exact test is P > 0 with P = [xx / 2 + d (1 - v + L(v))] - L(u), L = flog (x < y and y - x > 0 are the same
+// statement in IEEE arithmetic).  |t - P| is at most
+//   * the logs: (float)x is off by 2^-24 relative, which moves ln by 2^-24; v_log_f32 is good to 1 ulp of log2 x,
+//     2^-23 |l| (counted as 2^-23 absolute as well, should it not keep a RELATIVE ulp near x = 1).  Together below
+//     2^-22 (1 + |l|) per log, the one of v multiplied by d:
+//         2^-22 (1 + |lu| + d (1 + |lv|));
+//   * flog against the true log, 1e-15 (1 + |l|), and the float64 roundings of either combination, a few 2^-53
+//     of the terms' magnitudes, xx / 2 <= 23, v <= 51 (the 32-bit Box-Muller radius ends at 6.7, d >= 2/3):
+//     below 2^-44 of the same bracket.
+// E = 2^-19 (1 + |lu| + d (1 + |lv|)) is 8 x that.  t > E accepts, t < -E rejects, anything else - a NaN, and a
+// v below FLT_MIN, where the hardware log has no normal argument - is left to the exact test.
+__device__ __forceinline__ bool mt_accept_f32(double u, double xx, double d, double v, bool& acc) {
+    const float vf = (float)v;
+    constexpr double kLn2 = 0.69314718055994530942;
+    const double lu = kLn2 * (double)__builtin_amdgcn_logf((float)u), lv = kLn2 * (double)__builtin_amdgcn_logf(vf);
+    const double t = 0.5 * xx + d * (1.0 - v + lv) - lu;
+    const double E = 1.9073486328125e-6 * fma(d, 1.0 + fabs(lv), 1.0 + fabs(lu));
+    acc = t > E;
+    return (acc || t < -E) && vf >= 1.17549435e-38f;
+}
+template <bool EXACT>
+__device__ __forceinline__ bool mt_accept(double u, double xx, double d, double v) {
+    if (EXACT) return mt_accept_exact_inl(u, xx, d, v);
+    bool acc;
+    const bool open = !mt_accept_f32(u, xx, d, v, acc);
+    if (__any(open)) {  // (one wave in ~30 at the metric screen's concentrations)
+        if (open) acc = mt_accept_exact(u, xx, d, v);
+    }
+    return acc;
+}
+
 struct GammaPair {
     double g0, g1;
     unsigned int k;  // generator position after the draw
@@ -698,7 +754,7 @@ struct GammaPair {
 // FLOOR = 2, the same shortcut for callers that keep max(g, DBL_MIN) (the tiling pi sites: masked alleles are
 // components with concentrations of ~1e-6, whose boost underflows for 99.9 % of the draws): a boosted component
 // with U^(1/alpha) < e^-716 gives a product below DBL_MIN whatever its Marsaglia-Tsang factor (<= 86) is.
-template <int FLOOR = 0>
+template <int FLOOR = 0, bool EXACT = BEAN_MT_EXACT != 0>
 __device__ __forceinline__ GammaPair sample_gamma_pair_inl(double a0, double a1, Rng rng, const uint4* first = nullptr) {
     constexpr bool FLOOR32 = FLOOR != 0;  // (the code below calls either floor FLOOR32; the thresholds differ)
     constexpr double kLogFloor = FLOOR == 2 ? -716.5 : -92.5, kScaleFloor = FLOOR == 2 ? 1e-311 : 9.18e-41;
@@ -755,7 +811,7 @@ __device__ __forceinline__ GammaPair sample_gamma_pair_inl(double a0, double a1,
             const double y = 1.0 + c0 * q.na;
             if (y > 0.0) {
                 const double v = y * y * y, xx = q.na * q.na;
-                if (q.ua < 1.0 - 0.0331 * xx * xx || accept_log(q.ua) < 0.5 * xx + d0 * (1.0 - v + accept_log(v))) {
+                if (q.ua < 1.0 - 0.0331 * xx * xx || mt_accept<EXACT>(q.ua, xx, d0, v)) {
                     g0 = d0 * v;
                     done0 = true;
                 }
@@ -765,7 +821,7 @@ __device__ __forceinline__ GammaPair sample_gamma_pair_inl(double a0, double a1,
             const double y = 1.0 + c1 * q.nb;
             if (y > 0.0) {
                 const double v = y * y * y, xx = q.nb * q.nb;
-                if (q.ub < 1.0 - 0.0331 * xx * xx || accept_log(q.ub) < 0.5 * xx + d1 * (1.0 - v + accept_log(v))) {
+                if (q.ub < 1.0 - 0.0331 * xx * xx || mt_accept<EXACT>(q.ub, xx, d1, v)) {
                     g1 = d1 * v;
                     done1 = true;
                 }
@@ -781,13 +837,13 @@ __device__ __forceinline__ GammaPair sample_gamma_pair_inl(double a0, double a1,
 
 // out-of-line copy for the kernels whose call sites have many live registers
 __device__ BEAN_NOINLINE GammaPair sample_gamma_pair(double a0, double a1, Rng rng) {
-    return sample_gamma_pair_inl(a0, a1, rng);
+    return sample_gamma_pair_inl<0, true>(a0, a1, rng);
 }
 __device__ BEAN_NOINLINE GammaPair sample_gamma_pair_floor32(double a0, double a1, Rng rng) {
-    return sample_gamma_pair_inl<1>(a0, a1, rng);
+    return sample_gamma_pair_inl<1, true>(a0, a1, rng);
 }
 __device__ BEAN_NOINLINE GammaPair sample_gamma_pair_floord(double a0, double a1, Rng rng) {
-    return sample_gamma_pair_inl<2>(a0, a1, rng);
+    return sample_gamma_pair_inl<2, true>(a0, a1, rng);
 }
 
 // single draw (second component unused)

@@ -709,7 +709,13 @@ int bean_hip_get_profile(bean_hip_ctx* ctx, double* avg_ms, uint64_t* launches);
  *   op 9: the same from the double-floor sampler of the wide tiling kernel (must equal op 8 draw for draw)
  *   op 10: as op 2 through dirichlet_grad_one_pre with digamma(a), digamma(b) supplied (must equal op 2 bit for bit)
  *   op 11: as op 10 through dirichlet_grad_one_tab, its x-free factors tabulated in the kernel as the finish tabulates
- *          them (must equal op 10 bit for bit) */
+ *          them (must equal op 10 bit for bit)
+ *   op 12 - 14: out0, out1 = Gamma(a), Gamma(b), unfloored, from the inlined pair sampler whose acceptance test is
+ *          settled in float32 where it can be, FLOOR form 0, 1, 2 (seed = x[0] bits, element index)
+ *   op 15 - 17: the same from the out-of-line samplers with the float64 test (must equal 12 - 14 draw for draw)
+ *   op 18 - 23: as 12 - 17 with out0 = the generator position after the draw
+ *   op 24: the acceptance test alone at (d, n, u) = (a, x, b): out0 = the float64 decision (-1: 1 + c n <= 0),
+ *          out1 = the float32 form's decision + 2 where float32 settled it */
 int bean_hip_test_special(int32_t op, uint64_t n, const double* a, const double* x,
                           const double* b, double* out0, double* out1, void* stream);
 
