@@ -92,9 +92,11 @@ ENSEMBLE_SYMBOLS = ("bean_hip_ensemble_supported", "bean_hip_set_members", "bean
                     "bean_hip_set_particles", "bean_hip_svi_run_particles",
                     "bean_hip_predictive_supported", "bean_hip_simulate", "bean_hip_simulate_members",
                     "bean_hip_simulate_design", "bean_hip_simulate_power", "bean_hip_log_weights",
-                    "bean_hip_log_weights_marginal", "bean_hip_marginal_grid")
+                    "bean_hip_log_weights_marginal", "bean_hip_marginal_grid",
+                    "bean_hip_marginal_grid_tail", "bean_hip_marginal_tail_nodes")
 MAX_LOGW_DRAWS = 4096  # BEAN_HIP_MAX_LOGW_DRAWS
 MARGINAL_NODES = (16, 32, 64)  # n_nodes of bean_hip_log_weights_marginal
+TAIL_NODES = 64 + 48  # kTailNodes + kTailCheckNodes: the nodes bean_hip_marginal_tail_nodes returns per tail pair
 PARAM_ORDER = ("mu_loc", "mu_scale", "sd_loc", "sd_scale", "alpha_pi", "noise_loc", "noise_scale", "q0")
 
 # every symbol include/bean_hip.h declares: (name, restype, argtypes)
@@ -135,6 +137,11 @@ SYMBOLS = [
     ("bean_hip_marginal_grid", c_int32,
      [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64,
       c_void_p, c_uint64, c_void_p]),
+    ("bean_hip_marginal_grid_tail", c_int32,
+     [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64,
+      c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
+    ("bean_hip_marginal_tail_nodes", c_int32,
+     [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
     ("bean_hip_sharded_begin", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
     ("bean_hip_sharded_sums", c_int32, [c_void_p, c_void_p]),
     ("bean_hip_sharded_guide", c_int32, [c_void_p, c_void_p]),

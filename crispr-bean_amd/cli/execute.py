@@ -162,6 +162,15 @@ def get_parser():
                           "the other tables do not change.  Sorting variant screens only; not with --scale-by-acc.")
     own.add_argument("--grid-nodes", dest="grid_nodes", type=int, default=32, metavar="Q",
                      help="Quadrature nodes per integral of --grid-posterior: 16, 32 or 64 (default 32).")
+    own.add_argument("--grid-tail-rule", dest="grid_tail_rule", action="store_true",
+                     help="With --grid-posterior: integrate the (replicate, guide) pairs its quadrature rule does not "
+                          "resolve - an essentially unedited guide is one - by a 64-node Gauss-Jacobi rule that carries "
+                          "the pair's endpoint singularity in its weight, and check it against the 48-node rule.  A "
+                          "target with such pairs then gets numbers where the two rules agree within 1e-3 nat per pair "
+                          "over the nodes that hold its posterior, and stays empty otherwise (prior-data conflict in the "
+                          "editing rate is the case the rule does not cover).  Adds the columns n_pairs_tail and "
+                          "grid_tail_err behind the grid columns; n_pairs_unresolved stays what it is.  Refused without "
+                          "--grid-posterior.")
     own.add_argument("--bootstrap", dest="bootstrap", type=_non_negative_int, default=0, metavar="K",
                      help="Parametric bootstrap: after the fit of the screen, draw K screens from the fitted model on the "
                           "GPU (mu, sd and the guide noise at their fitted locations; fresh pi, Dirichlet and count draws; "
@@ -217,7 +226,8 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    from .run import grid_nodes, importance_draws, importance_nodes, member_mode, particle_count, predictive_draws
+    from .run import (grid_nodes, grid_tail_rule, importance_draws, importance_nodes, member_mode, particle_count,
+                      predictive_draws)
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
@@ -226,6 +236,7 @@ def check_run_switches(parser, args):
     importance_draws(args, parser.error)
     importance_nodes(args, parser.error)
     grid_nodes(args, parser.error)
+    grid_tail_rule(args, parser.error)
 
 
 def main(argv=None):

@@ -253,6 +253,16 @@ def grid_nodes(args, fail=_refuse):
     return nodes
 
 
+def grid_tail_rule(args, fail=_refuse) -> bool:
+    """``--grid-tail-rule``: the Gauss-Jacobi rule for the pairs the grid posterior's quadrature does not resolve.
+    Refused without ``--grid-posterior``; every other refusal is that flag's own (``grid_nodes``)."""
+    if not getattr(args, "grid_tail_rule", False):
+        return False
+    if not getattr(args, "grid_posterior", False):
+        fail("--grid-tail-rule sets the rule --grid-posterior uses for the pairs it does not resolve and needs that flag.")
+    return True
+
+
 def check_guide_jackknife_switches(args) -> bool:
     """Whether --jackknife-guides is set; the combinations it is refused with raise (the parser refuses them first)."""
     return member_mode(args, only=("jackknife_guides",)) == "guides"
@@ -525,10 +535,21 @@ def main(args, return_data=False):
         import torch
 
         info(f"Grid posterior: the log joint of (mu, sd) per target on its own grid, pi integrated out ({n_grid} nodes)...")
-        summary = model_run.run_grid_posterior(model, guide, ndata, param_history_dict, nodes=n_grid)
+        tail = grid_tail_rule(args)
+        summary = model_run.run_grid_posterior(model, guide, ndata, param_history_dict, nodes=n_grid,
+                                               **({"tail_rule": True} if tail else {}))
         grid = {k: v.detach().cpu() for k, v in summary.items()}
         table_columns = {**table_columns, "grid": grid}
         out_of = ~grid["grid_ok"] | (grid["n_pairs_unresolved"] > 0)
+        if tail:
+            had = grid["n_pairs_tail"] > 0
+            out_of = ~grid["grid_ok"]
+            pct = lambda m, of: 100.0 * float(m.sum()) / max(int(of), 1)  # noqa: E731
+            got, barred = had & grid["grid_ok"], had & ~grid["grid_tail_ok"]
+            info(f"Grid posterior, tail rule: {int(had.sum())} of {had.numel()} targets ({pct(had, had.numel()):.1f} %) had "
+                 f"tail pairs; {int(got.sum())} of those ({pct(got, had.sum()):.1f} %) now have numbers; {int(barred.sum())} "
+                 f"of {had.numel()} targets ({pct(barred, had.numel()):.1f} %) refused by the tail bar "
+                 "(grid_tail_err > 1e-3 n_pairs_tail).")
         fitted_sd = torch.as_tensor(param_history_dict["mu_scale"]).detach().cpu().double().reshape(-1)
         ratio = (fitted_sd / grid["mu_sd_grid"])[~out_of]
         info(f"Grid posterior: {int(out_of.sum())} of {out_of.numel()} targets "

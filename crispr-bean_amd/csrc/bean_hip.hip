@@ -32,6 +32,7 @@
 #include "bean_importance.hpp"  // per-target log importance weights (bean_hip_log_weights)
 #include "bean_importance_marg.hpp"  // ... with pi integrated out (bean_hip_log_weights_marginal)
 #include "bean_grid.hpp"  // the same log joint at given (mu, y) per target and node (bean_hip_marginal_grid)
+#include "bean_jacobi.hpp"  // ... with a Gauss-Jacobi rule for the pairs the predicate leaves out (bean_hip_marginal_grid_tail)
 
 using namespace bean;
 
@@ -158,6 +159,10 @@ struct bean_hip_ctx {
     float* particle_grad = nullptr;   // per parameter array a (P, n) float32 block, the arrays end to end (particle_arrays)
     double* particle_loss = nullptr;  // (P, loss_capacity) losses of the particles; the caller's loss_hist holds their mean
     ArgSet particles;                 // particle_args of the P particles; ladder of particle steps (four launches each)
+    // bean_hip_marginal_grid_tail (bean_jacobi.hpp): grown on demand, never read by a fit
+    int* tail_off = nullptr;          // (T + 1) list offsets, then (T) counts for bean_hip_marginal_tail_nodes
+    void* tail_ws = nullptr;          // nodes, log weights, tail_pair_err, pair indices, sides of the last call
+    uint64_t tail_ws_bytes = 0;
 };
 
 extern "C" const char* bean_hip_version(void) {
@@ -740,6 +745,8 @@ extern "C" int bean_hip_destroy(bean_hip_ctx* c) {
     (void)bean_hip_comm_destroy(c);
     for (hipEvent_t e : c->ev) (void)hipEventDestroy(e);
     if (c->workspace) (void)hipFree(c->workspace);
+    if (c->tail_off) (void)hipFree(c->tail_off);
+    if (c->tail_ws) (void)hipFree(c->tail_ws);
     if (c->tile_tab) (void)hipFree(c->tile_tab);
     if (c->live_slots) (void)hipFree(c->live_slots);
     if (c->tsum_buf) (void)hipFree(c->tsum_buf);
@@ -3012,23 +3019,74 @@ extern "C" int bean_hip_log_weights_marginal(bean_hip_ctx* c, uint64_t seed, uin
 // (bean_grid.hpp) lj of n_mu * n_y given nodes per target, pi integrated out: four launches per call whatever the grid
 // (the pairs' constants, the unresolved pairs per target, the pairs' terms, the targets).  No seed, no draw, no term of
 // q; nothing of the handle is written.
-extern "C" int bean_hip_marginal_grid(bean_hip_ctx* c, int32_t n_nodes, int32_t n_mu, int32_t n_y, const void* centre_mu,
-                                      const void* centre_y, const void* step_mu, const void* step_y, void* lj_out,
-                                      uint64_t lj_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
-                                      uint64_t unresolved_bytes, void* stream_) {
-    if (!c) return fail("bean_hip_marginal_grid: null handle");
+// ------------------------------------------------------------------ the log joint on a grid of (mu, y) per target
+// (bean_grid.hpp) lj of n_mu * n_y given nodes per target, pi integrated out: four launches per call whatever the grid
+// (the pairs' constants, the unresolved pairs per target, the pairs' terms, the targets).  No seed, no draw, no term of
+// q; nothing of the handle is written.
+//
+// With tail_err_out (bean_hip_marginal_grid_tail, bean_jacobi.hpp) the pairs the predicate leaves out get a Gauss-Jacobi
+// rule: the unresolved count comes first, its scan gives the compact list's offsets and - one host synchronisation per
+// call - the number of tail pairs; with none, the launches are those of bean_hip_marginal_grid and tail_err_out is
+// zeroed; otherwise k_tail_list and k_tail_nodes follow, then k_logw_consts and k_grid_pairs as they are,
+// k_grid_pairs_tail over the tail pairs' slots, k_grid_targets as it is, and k_grid_targets_tail.
+static int tail_reserve(bean_hip_ctx* c, uint64_t bytes) {
+    if (!c->tail_off) HIP_OK(hipMalloc((void**)&c->tail_off, sizeof(int) * (2 * (size_t)c->d.T + 1)));
+    if (bytes > c->tail_ws_bytes) {
+        if (c->tail_ws) (void)hipFree(c->tail_ws);
+        c->tail_ws = nullptr;
+        c->tail_ws_bytes = 0;
+        HIP_OK(hipMalloc(&c->tail_ws, bytes));
+        c->tail_ws_bytes = bytes;
+    }
+    return 0;
+}
+
+// the unresolved count (into `unresolved`, (T) int32 on the device), its scan, and the number of tail pairs on the host
+static int tail_count(bean_hip_ctx* c, int* unresolved, TailArgs& ta, hipStream_t stream) {
+    const DevArgs& d = c->d;
+    if (tail_reserve(c, 0)) return -1;
+    MargArgs ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.unresolved_out = unresolved;
+    hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
+                       stream, d, ma);
+    memset(&ta, 0, sizeof(ta));
+    ta.unresolved = unresolved;
+    ta.toff = c->tail_off;
+    hipLaunchKernelGGL(k_tail_offsets, dim3(1), dim3(kTailScanBlock), 0, stream, d.T, ta);
+    int n = 0;
+    HIP_OK(hipMemcpyAsync(&n, c->tail_off + d.T, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    ta.n_tail = n;
+    return 0;
+}
+
+// the compact list and the 64 + 48 nodes and log weights of every tail pair, into ta's arrays
+static void tail_nodes_launch(const DevArgs& d, const TailArgs& ta, hipStream_t stream) {
+    hipLaunchKernelGGL(k_tail_list, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
+                       ta);
+    const uint64_t nn = (uint64_t)ta.n_tail * kTailAll;
+    hipLaunchKernelGGL(k_tail_nodes, dim3((unsigned)((nn + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
+                       ta);
+}
+
+static int grid_run(bean_hip_ctx* c, const std::string& name, bool tail, int32_t n_nodes, int32_t n_mu, int32_t n_y,
+                    const void* centre_mu, const void* centre_y, const void* step_mu, const void* step_y, void* lj_out,
+                    uint64_t lj_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
+                    uint64_t unresolved_bytes, void* tail_err_out, uint64_t tail_err_bytes, void* stream_) {
+    if (!c) return fail(name + ": null handle");
     if (!predictive_shape_ok(c))
-        return fail("bean_hip_marginal_grid: the grid posterior does not take this handle "
+        return fail(name + ": the grid posterior does not take this handle "
                     "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
                     "covariates, one member, one particle");
-    if (!c->prepared) return fail("bean_hip_marginal_grid: call bean_hip_prepare first");
+    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
     if (c->shape.flags & BEAN_FLAG_SCALE_BY_ACC)
-        return fail("bean_hip_marginal_grid: a handle with accessibility (BEAN_FLAG_SCALE_BY_ACC) is refused: the guide "
+        return fail(name + ": a handle with accessibility (BEAN_FLAG_SCALE_BY_ACC) is refused: the guide "
                     "noise is a further latent per guide, so the posterior of a target is not 2-D");
     if (n_nodes != 16 && n_nodes != 32 && n_nodes != 64)
-        return fail("bean_hip_marginal_grid: n_nodes must be 16, 32 or 64, got " + std::to_string(n_nodes));
+        return fail(name + ": n_nodes must be 16, 32 or 64, got " + std::to_string(n_nodes));
     if (n_mu < 1 || n_y < 1 || (int64_t)n_mu * n_y > BEAN_HIP_MAX_LOGW_DRAWS)
-        return fail("bean_hip_marginal_grid: n_mu >= 1, n_y >= 1 and n_mu * n_y <= " +
+        return fail(name + ": n_mu >= 1, n_y >= 1 and n_mu * n_y <= " +
                     std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) + ", got " + std::to_string(n_mu) + " x " +
                     std::to_string(n_y) + " = " + std::to_string((int64_t)n_mu * n_y));
     if (check_bound(c, false, false)) return -1;
@@ -3036,17 +3094,19 @@ extern "C" int bean_hip_marginal_grid(bean_hip_ctx* c, int32_t n_nodes, int32_t 
     const int N = n_mu * n_y;
     const uint64_t nt = (uint64_t)N * d.T, np = (uint64_t)N * d.R * d.G;
     if (!centre_mu || !centre_y || !step_mu || !step_y)
-        return fail("bean_hip_marginal_grid: centre_mu, centre_y, step_mu and step_y must each hold (T) float64 on the "
+        return fail(name + ": centre_mu, centre_y, step_mu and step_y must each hold (T) float64 on the "
                     "device; one of them is null");
     const std::string sn = " float64 with N = n_mu * n_y = " + std::to_string(N) + ", ";
     if (!lj_out || lj_bytes != 8 * nt)
-        return fail("bean_hip_marginal_grid: lj_out must hold (N, T)" + sn + std::to_string(8 * nt) + " bytes");
+        return fail(name + ": lj_out must hold (N, T)" + sn + std::to_string(8 * nt) + " bytes");
     if (!pair_out || pair_bytes != 8 * np)
-        return fail("bean_hip_marginal_grid: pair_out (caller-owned scratch) must hold (N, R, G)" + sn +
+        return fail(name + ": pair_out (caller-owned scratch) must hold (N, R, G)" + sn +
                     std::to_string(8 * np) + " bytes");
     if (!unresolved_out || unresolved_bytes != 4 * (uint64_t)d.T)
-        return fail("bean_hip_marginal_grid: unresolved_out must hold (T) int32 (N = " + std::to_string(N) + "), " +
+        return fail(name + ": unresolved_out must hold (T) int32 (N = " + std::to_string(N) + "), " +
                     std::to_string(4 * (uint64_t)d.T) + " bytes");
+    if (tail && (!tail_err_out || tail_err_bytes != 8 * nt))
+        return fail(name + ": tail_err_out must hold (N, T)" + sn + std::to_string(8 * nt) + " bytes");
     hipStream_t stream = (hipStream_t)stream_;
     LogwArgs la;
     la.first_draw = 0;
@@ -3073,12 +3133,44 @@ extern "C" int bean_hip_marginal_grid(bean_hip_ctx* c, int32_t n_nodes, int32_t 
         block(64);
     const size_t lds = logw_marg_lds(d.B);
     const uint64_t rg = (uint64_t)d.R * d.G;
+    TailArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    if (tail && d.family == kMixture) {
+        if (tail_count(c, (int*)unresolved_out, ta, stream)) return -1;
+        if (ta.n_tail > 0) {
+            const uint64_t n = (uint64_t)ta.n_tail, need = n * (kTailPairBytes + 8 * (uint64_t)N);
+            if (need > kTailMaxBytes)
+                return fail(name + ": " + std::to_string(ta.n_tail) + " tail pairs at N = " + std::to_string(N) +
+                            " grid nodes need a workspace of " + std::to_string(need) + " bytes (" +
+                            std::to_string(kTailPairBytes) + " + 8 N per pair), above the cap of " +
+                            std::to_string(kTailMaxBytes) + "; send fewer nodes per call");
+            if (logw_tail_lds(d.R, d.B) > 65536)
+                return fail(name + ": " + std::to_string(ta.n_tail) + " tail pairs, and k_grid_pairs_tail needs " +
+                            std::to_string(logw_tail_lds(d.R, d.B)) + " bytes of LDS at R = " + std::to_string(d.R) +
+                            ", B = " + std::to_string(d.B) + ", above 65536");
+            if (tail_reserve(c, need)) return -1;
+            ta.N = N;
+            ta.z = (double*)c->tail_ws;
+            ta.lw = ta.z + n * kTailAll;
+            ta.pair_err = ta.lw + n * kTailAll;
+            ta.pair = (int*)(ta.pair_err + n * (uint64_t)N);
+            ta.side = ta.pair + n;
+            ta.tail_err_out = (double*)tail_err_out;
+            HIP_OK(hipMemsetAsync(ta.pair, 0, 2 * n * sizeof(int), stream));  // (an entry never names a pair out of range)
+            tail_nodes_launch(d, ta, stream);
+        }
+    }
     hipLaunchKernelGGL(k_logw_consts, dim3((unsigned)((rg + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
                        la);
     if (d.family == kMixture) {
-        hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
-                           stream, d, ma);
+        if (!tail)
+            hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock),
+                               0, stream, d, ma);
         hipLaunchKernelGGL(k_grid_pairs<kMixture>, grid, block, lds, stream, d, ga, ma);
+        if (ta.n_tail > 0)
+            hipLaunchKernelGGL(k_grid_pairs_tail, dim3((unsigned)((ta.n_tail + 63) / 64),
+                                                       (unsigned)((N + kTailChunk - 1) / kTailChunk)),
+                               block, logw_tail_lds(d.R, d.B), stream, d, ga, ta);
     } else {
         // no pi to integrate out, and no pair is unresolved
         HIP_OK(hipMemsetAsync(unresolved_out, 0, unresolved_bytes, stream));
@@ -3086,6 +3178,74 @@ extern "C" int bean_hip_marginal_grid(bean_hip_ctx* c, int32_t n_nodes, int32_t 
     }
     hipLaunchKernelGGL(k_grid_targets, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream,
                        d, ga);
+    if (tail) {
+        if (ta.n_tail > 0)
+            hipLaunchKernelGGL(k_grid_targets_tail, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock),
+                               0, stream, d, ta);
+        else
+            HIP_OK(hipMemsetAsync(tail_err_out, 0, tail_err_bytes, stream));
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int bean_hip_marginal_grid(bean_hip_ctx* c, int32_t n_nodes, int32_t n_mu, int32_t n_y, const void* centre_mu,
+                                      const void* centre_y, const void* step_mu, const void* step_y, void* lj_out,
+                                      uint64_t lj_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
+                                      uint64_t unresolved_bytes, void* stream_) {
+    return grid_run(c, "bean_hip_marginal_grid", false, n_nodes, n_mu, n_y, centre_mu, centre_y, step_mu, step_y, lj_out,
+                    lj_bytes, pair_out, pair_bytes, unresolved_out, unresolved_bytes, nullptr, 0, stream_);
+}
+
+extern "C" int bean_hip_marginal_grid_tail(bean_hip_ctx* c, int32_t n_nodes, int32_t n_mu, int32_t n_y,
+                                           const void* centre_mu, const void* centre_y, const void* step_mu,
+                                           const void* step_y, void* lj_out, uint64_t lj_bytes, void* pair_out,
+                                           uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
+                                           void* tail_err_out, uint64_t tail_err_bytes, void* stream_) {
+    return grid_run(c, "bean_hip_marginal_grid_tail", true, n_nodes, n_mu, n_y, centre_mu, centre_y, step_mu, step_y,
+                    lj_out, lj_bytes, pair_out, pair_bytes, unresolved_out, unresolved_bytes, tail_err_out, tail_err_bytes,
+                    stream_);
+}
+
+// the compact list of tail pairs with its nodes, for the tests: *n_tail_out (host) is the number of tail pairs; with
+// capacity = 0 nothing else is written (the count query); otherwise capacity >= that number and the first n_tail
+// entries of pair_index_out (int32, r * G + g in the handle's guide order), z_out and lw_out ((capacity, 112) float64:
+// the 64 nodes ascending, then the 48) and side_out (int32) are written
+extern "C" int bean_hip_marginal_tail_nodes(bean_hip_ctx* c, int32_t capacity, void* pair_index_out, void* z_out,
+                                            void* lw_out, void* side_out, int32_t* n_tail_out, void* stream_) {
+    const std::string name = "bean_hip_marginal_tail_nodes";
+    if (!c) return fail(name + ": null handle");
+    if (!predictive_shape_ok(c))
+        return fail(name + ": the grid posterior does not take this handle "
+                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
+                    "covariates, one member, one particle");
+    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
+    if (c->shape.flags & BEAN_FLAG_SCALE_BY_ACC)
+        return fail(name + ": a handle with accessibility (BEAN_FLAG_SCALE_BY_ACC) is refused: the guide "
+                    "noise is a further latent per guide, so the posterior of a target is not 2-D");
+    if (!n_tail_out) return fail(name + ": n_tail_out is null");
+    if (capacity < 0) return fail(name + ": capacity must not be negative, got " + std::to_string(capacity));
+    if (capacity > 0 && (!pair_index_out || !z_out || !lw_out || !side_out))
+        return fail(name + ": with capacity > 0, pair_index_out, z_out, lw_out and side_out must not be null");
+    if (check_bound(c, false, false)) return -1;
+    const DevArgs& d = c->d;
+    *n_tail_out = 0;
+    if (d.family != kMixture) return 0;
+    hipStream_t stream = (hipStream_t)stream_;
+    TailArgs ta;
+    if (tail_reserve(c, 0)) return -1;
+    if (tail_count(c, c->tail_off + d.T + 1, ta, stream)) return -1;
+    *n_tail_out = ta.n_tail;
+    if (capacity == 0 || ta.n_tail == 0) return 0;
+    if (capacity < ta.n_tail)
+        return fail(name + ": capacity " + std::to_string(capacity) + " is below the " + std::to_string(ta.n_tail) +
+                    " tail pairs of the handle");
+    ta.pair = (int*)pair_index_out;
+    ta.side = (int*)side_out;
+    ta.z = (double*)z_out;
+    ta.lw = (double*)lw_out;
+    HIP_OK(hipMemsetAsync(ta.pair, 0, (size_t)ta.n_tail * sizeof(int), stream));
+    tail_nodes_launch(d, ta, stream);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -1024,7 +1024,7 @@ class HipSVI:
         return out
 
     def marginal_grid(self, centre_mu, centre_y, step_mu, step_y, n_mu: int, n_y: int, nodes: int = 32,
-                      pairs: bool = False) -> Dict[str, torch.Tensor]:
+                      pairs: bool = False, tail_rule: bool = False) -> Dict[str, torch.Tensor]:
         """The log joint of every target on its own ``n_mu x n_y`` grid of given ``(mu_t, y_t = log sd_t)``, ``pi``
         integrated out of the model by ``nodes``-point quadrature (``bean_hip_marginal_grid``): node (i, k) of target t
         is ``mu = centre_mu[t] + (i - (n_mu - 1) / 2) step_mu[t]``, ``y = centre_y[t] + (k - (n_y - 1) / 2) step_y[t]``
@@ -1036,9 +1036,17 @@ class HipSVI:
         Nodes go to the library in chunks whose pair plane stays at or below ``LOGW_PAIR_BYTES``: the whole grid, or
         one line of ``mu`` per call, or one node per call.  A line or node is sent as a grid of one with its coordinate
         as the centre, which the library's formula returns as it is, so a node's value is the same bits whatever the
-        chunking.  Nothing of the fit is written; ``run(resume=True)`` continues its window."""
+        chunking.  Nothing of the fit is written; ``run(resume=True)`` continues its window.
+
+        ``tail_rule=True`` (``bean_hip_marginal_grid_tail``): the pairs ``n_unresolved`` counts get a Gauss-Jacobi rule
+        of 64 nodes in place of the ``nodes``-point rule, and ``tail_err`` (n_mu, n_y, T) is added: per node and target
+        the sum over those pairs of the difference to the 48-node rule.  Same chunking, same bits per node; the slots
+        of every other pair, and with no such pair ``lj`` itself, are those of ``tail_rule=False`` bit for bit.  Each
+        library call then synchronises the engine's stream once (the number of such pairs)."""
         if getattr(self.lib, "bean_hip_marginal_grid", None) is None:
             raise PredictiveUnsupported("this library build has no bean_hip_marginal_grid")
+        if tail_rule and getattr(self.lib, "bean_hip_marginal_grid_tail", None) is None:
+            raise PredictiveUnsupported("this library build has no bean_hip_marginal_grid_tail")
         if not self.predictive_supported or self.scale_by_accessibility:
             raise PredictiveUnsupported(f"the grid posterior does not take this engine ({self.family}"
                                         f"{', survival' if self.survival else ''}"
@@ -1073,29 +1081,75 @@ class HipSVI:
         n_chunk = N if whole else (n_y if by_line else 1)
         plane = torch.empty((n_mu, n_y, R, G) if pairs else (n_chunk, R, G), dtype=torch.float64, device=dev)
         unresolved = torch.empty(T, dtype=torch.int32, device=dev)
+        tail_err = torch.empty((n_mu, n_y, T), dtype=torch.float64, device=dev) if tail_rule else None
         # the library's coordinates of a line or node, two roundings each (a product, a sum)
         mus = [] if whole else [c_mu + s_mu * (i - (n_mu - 1) / 2.0) for i in range(n_mu)]
         ys = [] if whole or by_line else [c_y + s_y * (k - (n_y - 1) / 2.0) for k in range(n_y)]
 
-        def call(cm, cy, nm, ny, out, pl):
-            self._check(self.lib.bean_hip_marginal_grid(self._h, int(nodes), nm, ny, ptr(cm), ptr(cy), ptr(s_mu),
-                                                        ptr(s_y), ptr(out), nb(out), ptr(pl), nb(pl), ptr(unresolved),
-                                                        nb(unresolved), self._sptr()), "marginal_grid")
+        def call(cm, cy, nm, ny, out, pl, te=None):
+            if te is None:
+                self._check(self.lib.bean_hip_marginal_grid(self._h, int(nodes), nm, ny, ptr(cm), ptr(cy), ptr(s_mu),
+                                                            ptr(s_y), ptr(out), nb(out), ptr(pl), nb(pl), ptr(unresolved),
+                                                            nb(unresolved), self._sptr()), "marginal_grid")
+            else:
+                self._check(self.lib.bean_hip_marginal_grid_tail(
+                    self._h, int(nodes), nm, ny, ptr(cm), ptr(cy), ptr(s_mu), ptr(s_y), ptr(out), nb(out), ptr(pl), nb(pl),
+                    ptr(unresolved), nb(unresolved), ptr(te), nb(te), self._sptr()), "marginal_grid_tail")
 
         with self._on_stream():
             if whole:
-                call(c_mu, c_y, n_mu, n_y, lj, plane)
+                call(c_mu, c_y, n_mu, n_y, lj, plane, tail_err)
             else:
                 for i in range(n_mu):
                     if by_line:
-                        call(mus[i], c_y, 1, n_y, lj[i], plane[i] if pairs else plane)
+                        call(mus[i], c_y, 1, n_y, lj[i], plane[i] if pairs else plane, tail_err[i] if tail_rule else None)
                     else:
                         for k in range(n_y):
-                            call(mus[i], ys[k], 1, 1, lj[i, k:k + 1], plane[i, k:k + 1] if pairs else plane)
+                            call(mus[i], ys[k], 1, 1, lj[i, k:k + 1], plane[i, k:k + 1] if pairs else plane,
+                                 tail_err[i, k:k + 1] if tail_rule else None)
         out = {"lj": lj, "n_unresolved": unresolved}
+        if tail_rule:
+            out["tail_err"] = tail_err
         if pairs:
             out["pairs"] = self._to_screen_order(plane, 3)
         return out
+
+    def marginal_tail_nodes(self) -> Dict[str, torch.Tensor]:
+        """The pairs ``marginal_grid(tail_rule=True)`` gives the Gauss-Jacobi rule, at the current parameters
+        (``bean_hip_marginal_tail_nodes``), as device tensors: ``replicate`` and ``guide`` (n,) int64 - the guide in screen
+        order; the list is ordered by target, guide, replicate in the engine's guide order - ``side`` (n,) int32, 1 where
+        the smaller exponent of the pair's Beta-shaped factor is ``pi_1``'s, and ``z``, ``lw`` (n, 112) float64: the 64
+        nodes, ascending, and log weights (normalised to sum 1) of the rule, then those of the 48-node rule.  Nothing of
+        the fit is written."""
+        if getattr(self.lib, "bean_hip_marginal_tail_nodes", None) is None:
+            raise PredictiveUnsupported("this library build has no bean_hip_marginal_tail_nodes")
+        if not self.predictive_supported or self.scale_by_accessibility:
+            raise PredictiveUnsupported(f"the grid posterior does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ''}"
+                                        f"{', accessibility' if self.scale_by_accessibility else ''}): sorting variant "
+                                        "Normal / MixtureNormal, unsharded, no sample covariates, one member, one "
+                                        "particle, no accessibility")
+        dev, G = self.device, self.data.n_guides
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        count = ctypes.c_int32(0)
+        with self._on_stream():
+            self._check(self.lib.bean_hip_marginal_tail_nodes(self._h, 0, None, None, None, None, ctypes.byref(count),
+                                                              self._sptr()), "marginal_tail_nodes")
+        n = int(count.value)
+        # (formed on the caller's stream, before the engine's stream is made to wait for it: marginal_grid)
+        pair = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        side = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        z = torch.zeros((max(n, 1), _lib.TAIL_NODES), dtype=torch.float64, device=dev)
+        lw = torch.zeros((max(n, 1), _lib.TAIL_NODES), dtype=torch.float64, device=dev)
+        if n:
+            with self._on_stream():
+                self._check(self.lib.bean_hip_marginal_tail_nodes(self._h, n, ptr(pair), ptr(z), ptr(lw), ptr(side),
+                                                                  ctypes.byref(count), self._sptr()), "marginal_tail_nodes")
+        pair = pair[:n].long()
+        g = pair % G
+        if self.guide_order is not None:
+            g = self.guide_order[g]
+        return {"replicate": pair // G, "guide": g, "side": side[:n], "z": z[:n], "lw": lw[:n]}
 
     def run_ensemble(self, n_steps: int, seeds, graph_chunk: int = 50, first_step: Optional[int] = None):
         """Enqueue ``n_steps`` SVI steps of all ``n_members`` fits, member k with ``seeds[k]`` (no host

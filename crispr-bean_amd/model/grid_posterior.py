@@ -25,6 +25,8 @@ import torch
 BORDER_MAX = 1e-6      # the bar tests/marginal_reference.py::assert_marginal_claim sets for its reference grid
 STEP_SHIFT_MAX = 1e-3  # |mean - mean from every second grid line| / sd
 START_HALF_WIDTH = (4.0, 1.0)  # of the first zoom box, in mu and in y
+TAIL_BOUND = 1e-3      # nat per tail pair: the bound section 21 sets for a pair's log integral
+TAIL_KEYS = ("n_pairs_tail", "grid_tail_err")  # the columns --grid-tail-rule adds behind GRID_KEYS
 GRID_KEYS = ("mu_grid", "mu_sd_grid", "sd_grid", "p_mu_pos_grid", "log_evidence_grid", "log_bf10_grid", "grid_ok")
 
 
@@ -44,7 +46,14 @@ def _as_t(v, like: torch.Tensor) -> torch.Tensor:
     return torch.as_tensor(v, dtype=torch.float64).to(like.device).reshape(-1)
 
 
-def grid_summary(lj: torch.Tensor, centre_mu, centre_y, step_mu, step_y) -> Dict[str, torch.Tensor]:
+def _tail_err_where_it_counts(lj: torch.Tensor, tail_err: torch.Tensor) -> torch.Tensor:
+    """(T,): the largest ``tail_err`` over the nodes whose density is at least ``BORDER_MAX`` of the target's peak;
+    ``lj`` and ``tail_err`` are (nodes, T)."""
+    counts = (lj - lj.max(0).values) >= math.log(BORDER_MAX)
+    return torch.where(counts, tail_err, torch.zeros_like(tail_err)).max(0).values
+
+
+def grid_summary(lj: torch.Tensor, centre_mu, centre_y, step_mu, step_y, tail_err=None) -> Dict[str, torch.Tensor]:
     """Per target, from ``lj`` (n_mu, n_y, T) - ``HipSVI.marginal_grid`` on the grid of these centres and steps:
 
     * ``mu_grid``, ``mu_sd_grid``: posterior mean and sd of ``mu``; ``sd_grid``: the posterior mean of ``exp(y)``;
@@ -57,7 +66,10 @@ def grid_summary(lj: torch.Tensor, centre_mu, centre_y, step_mu, step_y) -> Dict
     * ``grid_border``: the largest density on the border of the grid relative to the peak (an axis of one node has no
       border); ``grid_step_shift``: ``|mu_grid - the same from every second grid line| / mu_sd_grid`` (0 where the sd
       is 0), with ``mu_grid_coarse`` / ``mu_sd_grid_coarse`` the moments behind it;
-    * ``grid_ok``: ``grid_border < 1e-6`` and ``grid_step_shift < 1e-3``.
+    * ``grid_ok``: ``grid_border < 1e-6`` and ``grid_step_shift < 1e-3``;
+    * with ``tail_err`` (n_mu, n_y, T) - ``HipSVI.marginal_grid(tail_rule=True)`` - ``grid_tail_err``: the largest
+      ``tail_err`` over the nodes whose density is at least 1e-6 of the target's peak (the bar of ``grid_border``: what
+      lies below it does not enter the summary at that precision either).
 
     Every value of a target is a function of that target's ``lj`` alone."""
     lj = torch.as_tensor(lj).double()
@@ -90,7 +102,14 @@ def grid_summary(lj: torch.Tensor, centre_mu, centre_y, step_mu, step_y) -> Dict
     edges = ([lj[0], lj[-1]] if n_mu > 1 else []) + ([lj[:, 0], lj[:, -1]] if n_y > 1 else [])
     border = ((torch.cat(edges).max(0).values - peak).exp() if edges else torch.zeros_like(peak))
     shift = torch.where(some, (mean - mean2).abs() / safe, torch.zeros_like(sd))
+    extra = {}
+    if tail_err is not None:
+        te = torch.as_tensor(tail_err).double().to(lj.device)
+        if te.shape != lj.shape:
+            raise ValueError(f"grid_summary: tail_err has shape {tuple(te.shape)}, lj {tuple(lj.shape)}")
+        extra["grid_tail_err"] = _tail_err_where_it_counts(lj.reshape(-1, T), te.reshape(-1, T))
     return {
+        **extra,
         "mu_grid": mean,
         "mu_sd_grid": sd,
         "sd_grid": (w.sum(0) * ys.exp()).sum(0),
@@ -104,7 +123,7 @@ def grid_summary(lj: torch.Tensor, centre_mu, centre_y, step_mu, step_y) -> Dict
     }
 
 
-def _zoom(engine, c_mu, c_y, h_mu, h_y, n_zoom: int, n_zm: int, n_zy: int, zoom_nodes: int, width: float):
+def _zoom(engine, c_mu, c_y, h_mu, h_y, n_zoom: int, n_zm: int, n_zy: int, zoom_nodes: int, width: float, **kw):
     """``n_zoom`` passes of an ``n_zm x n_zy`` grid over the box ``centre +- half-width``; each axis on its own: where its
     moment sd is at least one step the axis is resolved - the new centre is the moment mean, the new half-width
     ``width`` sds - otherwise the new centre is the coordinate of the largest node and the new half-width two steps.
@@ -115,7 +134,7 @@ def _zoom(engine, c_mu, c_y, h_mu, h_y, n_zoom: int, n_zm: int, n_zy: int, zoom_
     for _ in range(int(n_zoom)):
         s_mu = 2.0 * h_mu / (n_zm - 1) if n_zm > 1 else h_mu
         s_y = 2.0 * h_y / (n_zy - 1) if n_zy > 1 else h_y
-        lj = engine.marginal_grid(c_mu, c_y, s_mu, s_y, n_zm, n_zy, nodes=zoom_nodes)["lj"].double()
+        lj = engine.marginal_grid(c_mu, c_y, s_mu, s_y, n_zm, n_zy, nodes=zoom_nodes, **kw)["lj"].double()
         flat = lj.reshape(-1, T)
         w = torch.softmax(flat, 0).reshape(n_zm, n_zy, T)
         top = flat.argmax(0)
@@ -160,7 +179,7 @@ def log_prior_mu_at_zero(engine, like: torch.Tensor) -> torch.Tensor:
 
 
 def grid_posterior(engine, nodes: int = 32, zoom_nodes: int = 16, n_zoom: int = 5, n_z: int = 17, n_mu: int = 41,
-                   n_y: int = 21, width: float = 6.5) -> Dict[str, torch.Tensor]:
+                   n_y: int = 21, width: float = 6.5, tail_rule: bool = False) -> Dict[str, torch.Tensor]:
     """The grid posterior of every target of ``engine`` (anything with ``unconstrained`` and ``marginal_grid``):
 
     1. start at ``(mu_loc_t, sd_loc_t)`` of the engine's parameters with half-widths (4, 1);
@@ -174,23 +193,32 @@ def grid_posterior(engine, nodes: int = 32, zoom_nodes: int = 16, n_zoom: int = 
     ``grid_step_shift < 1e-3``; the Bayes factor also needs the same of the null line.  The values of a target that is
     not, or that has ``n_unresolved > 0``, are NaN; the diagnostics (``grid_border``, ``grid_step_shift``,
     ``grid_resolved``, ``n_pairs_unresolved``, the box) are kept.  Device tensors of length T; no host
-    synchronisation."""
+    synchronisation.
+
+    ``tail_rule=True``: every pass - the zooms and the null line included - is ``marginal_grid(tail_rule=True)``, the
+    Gauss-Jacobi rule for the pairs ``n_unresolved`` counts (``n_pairs_tail``).  A target with such pairs then gets
+    numbers if it passes the three checks above and ``grid_tail_err <= 1e-3 n_pairs_tail`` - section 21's bound of 1e-3
+    nat per pair, times the target's tail pairs; ``log_bf10_grid`` needs the null line to pass the same bar
+    (``grid_null_tail_err``).  Otherwise its values are NaN and the diagnostics are kept.  (Each library call then
+    synchronises the engine's stream once.)"""
+    kw = {"tail_rule": True} if tail_rule else {}
     P = engine.unconstrained
     c_mu = P["mu_loc"].detach().double().reshape(-1)
     c_y = P["sd_loc"].detach().double().reshape(-1).to(c_mu.device)
     h_mu = torch.full_like(c_mu, START_HALF_WIDTH[0])
     h_y = torch.full_like(c_mu, START_HALF_WIDTH[1])
-    c_mu, c_y2, h_mu, h_y2, resolved = _zoom(engine, c_mu, c_y, h_mu, h_y, n_zoom, n_z, n_z, zoom_nodes, width)
+    c_mu, c_y2, h_mu, h_y2, resolved = _zoom(engine, c_mu, c_y, h_mu, h_y, n_zoom, n_z, n_z, zoom_nodes, width, **kw)
     s_mu, s_y = 2.0 * h_mu / max(n_mu - 1, 1), 2.0 * h_y2 / max(n_y - 1, 1)
-    out = engine.marginal_grid(c_mu, c_y2, s_mu, s_y, n_mu, n_y, nodes=nodes)
-    summary = grid_summary(out["lj"], c_mu, c_y2, s_mu, s_y)
+    out = engine.marginal_grid(c_mu, c_y2, s_mu, s_y, n_mu, n_y, nodes=nodes, **kw)
+    summary = grid_summary(out["lj"], c_mu, c_y2, s_mu, s_y, tail_err=out["tail_err"] if tail_rule else None)
     n_un = torch.as_tensor(out["n_unresolved"]).to(c_mu.device)
 
     # the null line: mu = 0
     zero, one = torch.zeros_like(c_mu), torch.ones_like(c_mu)
-    _, c_y0, _, h_y0, resolved0 = _zoom(engine, zero, c_y, one, h_y, n_zoom, 1, n_z, zoom_nodes, width)
+    _, c_y0, _, h_y0, resolved0 = _zoom(engine, zero, c_y, one, h_y, n_zoom, 1, n_z, zoom_nodes, width, **kw)
     s_y0 = 2.0 * h_y0 / max(n_y - 1, 1)
-    lj0 = engine.marginal_grid(zero, c_y0, one, s_y0, 1, n_y, nodes=nodes)["lj"].double().reshape(n_y, -1)
+    out0 = engine.marginal_grid(zero, c_y0, one, s_y0, 1, n_y, nodes=nodes, **kw)
+    lj0 = out0["lj"].double().reshape(n_y, -1)
     peak0 = lj0.max(0).values
     border0 = (torch.maximum(lj0[0], lj0[-1]) - peak0).exp()
     line = lambda l, s: torch.logsumexp(l, 0) + s.log()  # noqa: E731
@@ -199,7 +227,14 @@ def grid_posterior(engine, nodes: int = 32, zoom_nodes: int = 16, n_zoom: int = 
     log_p0 = log_prior_mu_at_zero(engine, c_mu)
     null_ok = resolved0 & (border0 < BORDER_MAX) & ((ev0 - ev0_coarse).abs() < STEP_SHIFT_MAX)
 
-    ok = resolved & summary["grid_ok"] & (n_un == 0)
+    if tail_rule:
+        bar = TAIL_BOUND * n_un.to(torch.float64)
+        tail_err0 = _tail_err_where_it_counts(lj0, torch.as_tensor(out0["tail_err"]).double().to(lj0.device).reshape(n_y, -1))
+        tail_ok = summary["grid_tail_err"] <= bar
+        null_ok = null_ok & (tail_err0 <= bar)
+        ok = resolved & summary["grid_ok"] & tail_ok
+    else:
+        ok = resolved & summary["grid_ok"] & (n_un == 0)
     nan = torch.full_like(c_mu, math.nan)
     res = {k: torch.where(ok, summary[k], nan) for k in ("mu_grid", "mu_sd_grid", "sd_grid", "p_mu_pos_grid",
                                                          "log_evidence_grid")}
@@ -212,4 +247,7 @@ def grid_posterior(engine, nodes: int = 32, zoom_nodes: int = 16, n_zoom: int = 
                 "log_evidence_null_step_move": (ev0 - ev0_coarse).abs(), "grid_null_centre_y": c_y0,
                 "grid_null_step_y": s_y0,
                 "grid_centre_mu": c_mu, "grid_centre_y": c_y2, "grid_step_mu": s_mu, "grid_step_y": s_y})
+    if tail_rule:
+        res.update({"n_pairs_tail": n_un.to(torch.float64), "grid_tail_err": summary["grid_tail_err"],
+                    "grid_tail_ok": tail_ok, "grid_null_tail_err": tail_err0})
     return res

@@ -248,7 +248,9 @@ def write_result_table(
     ``mu_grid``, ``mu_sd_grid``, ``sd_grid``, ``p_mu_pos_grid``, ``log_evidence_grid``, ``log_bf10_grid`` (on the scale of
     ``mu``, not rescaled; empty where ``grid_ok`` is 0 or the target has unresolved pairs), ``grid_ok`` (0 / 1) and, unless
     the marginal importance check has already written it, ``n_pairs_unresolved`` - behind the importance columns; with
-    ``None`` every file is byte for byte what it was."""
+    ``None`` every file is byte for byte what it was.  A grid posterior with the tail rule
+    (``grid_posterior(tail_rule=True)``: it holds ``n_pairs_tail``) adds ``n_pairs_tail`` and ``grid_tail_err`` behind
+    those; without them in ``grid`` nothing changes."""
     fitted = _fitted_columns(param_hist_dict, sd_is_fitted, sample_covariates)
     if negctrl_params is not None:
         _rescale_by_control_fit(fitted, negctrl_params, sd_is_fitted, sample_covariates)
@@ -307,6 +309,11 @@ def write_result_table(
                              None, "grid_ok", count_per_target=True)
         if "n_pairs_unresolved" not in element.columns:
             element["n_pairs_unresolved"] = _flat(grid["n_pairs_unresolved"]).astype(np.int64)
+        if "n_pairs_tail" in grid:
+            # the Gauss-Jacobi rule for the unresolved pairs: how many pairs of the target took it, and the largest
+            # disagreement of its two node counts where the posterior has mass
+            element["n_pairs_tail"] = _flat(grid["n_pairs_tail"]).astype(np.int64)
+            element["grid_tail_err"] = _flat(grid["grid_tail_err"]).astype(np.float64)
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None
         # (the reference asks the PARAMETER STORE for a "negctrl" key, which it never has: the `_adj` columns always

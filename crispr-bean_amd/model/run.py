@@ -495,12 +495,14 @@ def run_importance_check(model, guide, data, param_store, n_draws: int = 1000, s
     return summary
 
 
-def run_grid_posterior(model, guide, data, param_store, nodes: int = 32):
+def run_grid_posterior(model, guide, data, param_store, nodes: int = 32, tail_rule: bool = False):
     """Grid posterior of ``(mu, sd)`` per target (``model/grid_posterior.py``): an engine for ``data`` with the fitted
     parameters of ``param_store`` loaded - they place the first zoom box and nothing else - and the summary of the log
     joint on every target's own grid, ``pi`` integrated out by ``nodes``-point quadrature: ``mu_grid``, ``mu_sd_grid``,
     ``sd_grid``, ``p_mu_pos_grid``, ``log_evidence_grid``, ``log_bf10_grid`` (NaN where ``grid_ok`` is false),
-    ``grid_ok``, ``n_pairs_unresolved`` and the diagnostics (a dict of device tensors).  No refit.
+    ``grid_ok``, ``n_pairs_unresolved`` and the diagnostics (a dict of device tensors).  No refit.  ``tail_rule``: the
+    Gauss-Jacobi rule for the unresolved pairs in every pass (``grid_posterior(tail_rule=True)``), which adds
+    ``n_pairs_tail`` and ``grid_tail_err``.
 
     Raises ``PredictiveUnsupported`` - the message names the reason - for tiling and survival screens,
     ``ControlNormal``, sample covariates, several ranks and accessibility scaling."""
@@ -522,7 +524,7 @@ def run_grid_posterior(model, guide, data, param_store, nodes: int = 32):
     eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
     try:
         load_parameters(eng, param_store)
-        summary = grid_posterior(eng, nodes=int(nodes))
+        summary = grid_posterior(eng, nodes=int(nodes), **({"tail_rule": True} if tail_rule else {}))
         torch.cuda.synchronize(device)
     finally:
         eng.close()

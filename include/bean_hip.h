@@ -615,6 +615,41 @@ int bean_hip_marginal_grid(bean_hip_ctx* ctx, int32_t n_nodes, int32_t n_mu, int
                            void* pair_out, uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
                            void* stream);
 
+/* bean_hip_marginal_grid with a Gauss-Jacobi rule for the pairs its predicate leaves out.
+ *
+ *   bean_hip_marginal_grid_tail   bean_hip_marginal_grid's arguments, refusals and state contract, plus tail_err_out,
+ *                                 (N, T) float64.  A tail pair is a pair under the repguide mask that fails the
+ *                                 predicate min(a0', a1') >= 2; unresolved_out keeps its meaning and is now also the
+ *                                 number of tail pairs of the target.  A tail pair's log integral is
+ *                                     lbeta(a0', a1') + logsumexp_i(lw_i + lg(z_i))
+ *                                 over the 64 Gauss-Jacobi nodes of the weight z^(min a' - 1) (1 - z)^(max a' - 1), z the
+ *                                 share of the smaller exponent's side; its slot of pair_out holds the pair's constant
+ *                                 plus that.  The 48-node rule gives a second value: tail_err_out[n, t] is the sum over
+ *                                 the target's tail pairs of |J64 - J48| at node n.  Slots of resolved pairs are bit for
+ *                                 bit those of bean_hip_marginal_grid; with no tail pair so are lj_out and pair_out, and
+ *                                 tail_err_out is zero (BEAN_FAMILY_NORMAL: always).
+ *                                 Launches (MixtureNormal): k_logw_unresolved, k_tail_offsets, one host synchronisation
+ *                                 of the stream (the number of tail pairs), with tail pairs k_tail_list and k_tail_nodes,
+ *                                 k_logw_consts, k_grid_pairs, with tail pairs k_grid_pairs_tail, k_grid_targets, with
+ *                                 tail pairs k_grid_targets_tail.
+ *                                 Workspace, owned by the handle and read by nothing else: 1 800 + 8 N bytes per tail
+ *                                 pair.  A call that would need more than 256 MiB is refused after the count (only
+ *                                 unresolved_out has been written); the message names the number of tail pairs.
+ *   bean_hip_marginal_tail_nodes  the compact list of tail pairs - ordered by target, guide, replicate - and its nodes.
+ *                                 *n_tail_out (HOST int32) receives the number of tail pairs; with capacity = 0 nothing
+ *                                 else is written.  Otherwise capacity must be at least that number, and the first
+ *                                 n_tail entries are written of pair_index_out (capacity) int32, r * G + g in the
+ *                                 handle's guide order; z_out and lw_out (capacity, 112) float64, the 64 nodes
+ *                                 ascending and then the 48, log weights normalised to sum 1; side_out (capacity) int32,
+ *                                 1 where the smaller exponent is pi_1's (ties included), 0 where it is pi_0's.  Device
+ *                                 arrays.  BEAN_FAMILY_NORMAL: 0 pairs.  Same handles, same state contract. */
+int bean_hip_marginal_grid_tail(bean_hip_ctx* ctx, int32_t n_nodes, int32_t n_mu, int32_t n_y, const void* centre_mu,
+                                const void* centre_y, const void* step_mu, const void* step_y, void* lj_out,
+                                uint64_t lj_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
+                                uint64_t unresolved_bytes, void* tail_err_out, uint64_t tail_err_bytes, void* stream);
+int bean_hip_marginal_tail_nodes(bean_hip_ctx* ctx, int32_t capacity, void* pair_index_out, void* z_out, void* lw_out,
+                                 void* side_out, int32_t* n_tail_out, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
