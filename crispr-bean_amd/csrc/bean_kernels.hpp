@@ -3451,6 +3451,15 @@ __global__ __launch_bounds__(256) void k_test_special(int op, long n, const doub
             o0[i] = mt_accept_exact(u, xx, d, v) ? 1.0 : 0.0;
             o1[i] = (mt_accept<false>(u, xx, d, v) ? 1.0 : 0.0) + (settled ? 2.0 : 0.0);
         }
+    } else if (op == 25) {
+        // the raw words of one Philox block: seed, subsequence and offset are 64-bit patterns carried in the doubles
+        // (x[0], a[i], b[i]), and so are the outputs - moved as integers, never through a float64 operation
+        const unsigned long long* ua = reinterpret_cast<const unsigned long long*>(a);
+        const unsigned long long* ux = reinterpret_cast<const unsigned long long*>(x);
+        const unsigned long long* ub = reinterpret_cast<const unsigned long long*>(b);
+        const uint4 v = philox_block(ux[0], ua[i], ub[i]);
+        reinterpret_cast<unsigned long long*>(o0)[i] = ((unsigned long long)v.y << 32) | v.x;
+        reinterpret_cast<unsigned long long*>(o1)[i] = ((unsigned long long)v.w << 32) | v.z;
     }
 }
 

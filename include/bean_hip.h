@@ -750,7 +750,10 @@ int bean_hip_get_profile(bean_hip_ctx* ctx, double* avg_ms, uint64_t* launches);
  *   op 15 - 17: the same from the out-of-line samplers with the float64 test (must equal 12 - 14 draw for draw)
  *   op 18 - 23: as 12 - 17 with out0 = the generator position after the draw
  *   op 24: the acceptance test alone at (d, n, u) = (a, x, b): out0 = the float64 decision (-1: 1 + c n <= 0),
- *          out1 = the float32 form's decision + 2 where float32 settled it */
+ *          out1 = the float32 form's decision + 2 where float32 settled it
+ *   op 25: the four words (x, y, z, w) of the Philox4x32-10 block at (seed = x[0] bits, subsequence = a[i] bits,
+ *          offset = b[i] bits, in 32-bit words): out0 bits = (y << 32) | x, out1 bits = (w << 32) | z.  All five are
+ *          64-bit patterns carried in the doubles, loaded and stored as integers */
 int bean_hip_test_special(int32_t op, uint64_t n, const double* a, const double* x,
                           const double* b, double* out0, double* out1, void* stream);
 
