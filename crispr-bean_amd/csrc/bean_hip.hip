@@ -2681,32 +2681,81 @@ extern "C" int bean_hip_predictive_supported(const bean_hip_ctx* c) {
     return predictive_shape_ok(c) ? 1 : 0;
 }
 
-extern "C" int bean_hip_simulate(bean_hip_ctx* c, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
-                                 void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes,
-                                 void* stream_) {
-    if (!c) return fail("bean_hip_simulate: null handle");
+// ---- what the post-fit entry points share.  Each composes these in its own order: a call that is wrong twice is
+// refused for the first reason the entry point tests.
+// A null handle, a handle predictive_shape_ok() does not take, an unprepared one; `stem` is the entry point's own
+// sentence ("the count simulator does not take this handle").
+static int postfit_admit(const bean_hip_ctx* c, const std::string& name, const char* stem) {
+    if (!c) return fail(name + ": null handle");
     if (!predictive_shape_ok(c))
-        return fail("bean_hip_simulate: the count simulator does not take this handle (bean_hip_predictive_supported): "
-                    "sorting variant Normal / MixtureNormal, unsharded, no sample covariates, one member, one particle");
-    if (!c->prepared) return fail("bean_hip_simulate: call bean_hip_prepare first");
-    if (check_bound(c, false, false)) return -1;
-    const DevArgs& d0 = c->d;
-    const uint64_t n = (uint64_t)d0.R * d0.B * d0.G;
-    const bool use_bc = (d0.flags & kUseBc) != 0;
-    if (!x_out || x_bytes != 4 * n)
-        return fail("bean_hip_simulate: x_out must hold (R, B, G) float32, " + std::to_string(4 * n) + " bytes");
-    if (use_bc && (!xbc_out || xbc_bytes != 4 * n))
-        return fail("bean_hip_simulate: this handle uses the barcode-matched counts: xbc_out must hold (R, B, G) float32, " +
-                    std::to_string(4 * n) + " bytes");
-    if (!use_bc && (xbc_out || xbc_bytes))
-        return fail("bean_hip_simulate: xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
-    if (alpha_out ? alpha_bytes != 16 * n : alpha_bytes != 0)
-        return fail("bean_hip_simulate: alpha_out must be null or hold (2, R, B, G) float64, " + std::to_string(16 * n) +
-                    " bytes");
-    hipStream_t stream = (hipStream_t)stream_;
+        return fail(name + ": " + stem + " (bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, "
+                    "unsharded, no sample covariates, one member, one particle");
+    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
+    return 0;
+}
+// ... and, for the grid posterior, a handle with accessibility
+static int grid_admit(const bean_hip_ctx* c, const std::string& name) {
+    if (postfit_admit(c, name, "the grid posterior does not take this handle")) return -1;
+    if (c->shape.flags & BEAN_FLAG_SCALE_BY_ACC)
+        return fail(name + ": a handle with accessibility (BEAN_FLAG_SCALE_BY_ACC) is refused: the guide "
+                    "noise is a further latent per guide, so the posterior of a target is not 2-D");
+    return 0;
+}
+
+// A caller's buffer `what` of the given shape: there, with exactly n bytes ...
+static int buf_exact(const std::string& name, const char* what, const std::string& shape, const void* p, uint64_t bytes,
+                     uint64_t n) {
+    if (!p || bytes != n) return fail(name + ": " + what + " must hold " + shape + ", " + std::to_string(n) + " bytes");
+    return 0;
+}
+// ... or null with 0 bytes
+static int buf_optional(const std::string& name, const char* what, const std::string& shape, const void* p,
+                        uint64_t bytes, uint64_t n) {
+    if (p ? bytes != n : bytes != 0)
+        return fail(name + ": " + what + " must be null or hold " + shape + ", " + std::to_string(n) + " bytes");
+    return 0;
+}
+// the simulators' counts: `planes` x (R, B, G) float32 in x_out, and in xbc_out exactly where the handle uses them
+static int sim_buffers(const bean_hip_ctx* c, const std::string& name, const std::string& shape, uint64_t planes,
+                       const void* x_out, uint64_t x_bytes, const void* xbc_out, uint64_t xbc_bytes) {
+    const DevArgs& d = c->d;
+    const uint64_t n = 4 * planes * d.R * d.B * d.G;
+    if (buf_exact(name, "x_out", shape, x_out, x_bytes, n)) return -1;
+    if (d.flags & kUseBc)
+        return buf_exact(name, "this handle uses the barcode-matched counts: xbc_out", shape, xbc_out, xbc_bytes, n);
+    if (xbc_out || xbc_bytes) return fail(name + ": xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
+    return 0;
+}
+// the importance weights' outputs: (n_draws, T) float64 in logw_out, mu_out and - optional - y_out, (n_draws, R, G) in
+// pair_out
+static int logw_buffers(const bean_hip_ctx* c, const std::string& name, int32_t n_draws, const void* logw_out,
+                        uint64_t logw_bytes, const void* mu_out, uint64_t mu_bytes, const void* y_out, uint64_t y_bytes,
+                        const void* pair_out, uint64_t pair_bytes) {
+    const DevArgs& d = c->d;
+    const uint64_t nt = 8 * (uint64_t)n_draws * d.T, np = 8 * (uint64_t)n_draws * d.R * d.G;
+    const std::string of = " float64 with n_draws = " + std::to_string(n_draws);
+    if (buf_exact(name, "logw_out", "(n_draws, T)" + of, logw_out, logw_bytes, nt)) return -1;
+    if (buf_exact(name, "mu_out", "(n_draws, T)" + of, mu_out, mu_bytes, nt)) return -1;
+    if (buf_optional(name, "y_out", "(n_draws, T)" + of, y_out, y_bytes, nt)) return -1;
+    return buf_exact(name, "pair_out (caller-owned scratch)", "(n_draws, R, G)" + of, pair_out, pair_bytes, np);
+}
+
+// launch geometry: kLogwBlock lanes per block over n items ...
+static dim3 logw_blocks(uint64_t n) { return dim3((unsigned)((n + kLogwBlock - 1) / kLogwBlock)); }
+// ... and one wave per (tile, replicate), the tiles rounded up to a multiple of 8, times `planes` in grid.y
+static dim3 pair_grid(const DevArgs& d, unsigned planes = 1) {
+    return dim3((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, planes);
+}
+
+// What every simulator does once its arguments are checked: the seed, draw `draw` as bean_hip_elbo_grad(seed, step =
+// draw) prepares it (no loss slot is cleared: n = 0), then one launch of `planes` member planes.  `launch(fam, acc,
+// grid, lds, sa)` names the kernel and its further argument struct.  (`auto`: instantiated where it is called, so the
+// kernels keep their place in the code object.)
+template <typename Launch>
+static auto simulate_run(bean_hip_ctx* c, uint64_t seed, uint64_t draw, unsigned planes, void* x_out, void* xbc_out,
+                         void* alpha_out, hipStream_t stream, Launch&& launch) {
     c->d.seed = seed;
     c->resume_ok = false;  // the workspace now holds this draw and its tables
-    // draw `draw` as bean_hip_elbo_grad(seed, step = draw) prepares it; no loss slot is cleared (n = 0)
     launch_set_step(c, stream, draw, 0, 0);
     launch_param<false, false, true>(c, stream);
     const DevArgs& d = c->d;
@@ -2714,13 +2763,46 @@ extern "C" int bean_hip_simulate(bean_hip_ctx* c, uint64_t seed, uint64_t draw, 
     sa.x_out = (float*)x_out;
     sa.xbc_out = (float*)xbc_out;
     sa.alpha_out = (double*)alpha_out;
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R), block(64);
+    const dim3 grid = pair_grid(d, planes);
     const size_t lds = simulate_wave2_lds(d.B);
-    with_family_acc(d, [&](auto fam, auto acc) {
-        hipLaunchKernelGGL((k_simulate_wave2<fam(), acc()>), grid, block, lds, stream, d, sa);
-    });
+    with_family_acc(d, [&](auto fam, auto acc) { launch(fam, acc, grid, lds, sa); });
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+// The D values of a study (`what`: "depths" / "effects") with n_draws screens each: D x K members at most, every value
+// passing `ok` (`bad` ends the refusal of one that does not).  They are copied into the 64 slots of the launch's
+// argument struct, the rest set to `pad`: the caller's array is not read after the call returns.
+static int study_values(const std::string& name, const std::string& what, bool (*ok)(double), const char* bad,
+                        const double* v, int32_t n_v, int32_t n_draws, double pad, double* slots) {
+    if (!v) return fail(name + ": " + what + " is null");
+    if (n_v < 1 || n_draws < 1 || (int64_t)n_v * n_draws > BEAN_HIP_MAX_MEMBERS)
+        return fail(name + ": n_" + what + " >= 1, n_draws >= 1 and n_" + what + " * n_draws <= " +
+                    std::to_string(BEAN_HIP_MAX_MEMBERS) + ", got " + std::to_string(n_v) + " x " +
+                    std::to_string(n_draws) + " = " + std::to_string((int64_t)n_v * n_draws));
+    for (int i = 0; i < n_v; ++i)
+        if (!ok(v[i])) return fail(name + ": " + what + "[" + std::to_string(i) + "] = " + std::to_string(v[i]) + bad);
+    for (int i = 0; i < kEnsembleMaxMembers; ++i) slots[i] = i < n_v ? v[i] : pad;
+    return 0;
+}
+
+static const char* const kSimStem = "the count simulator does not take this handle";
+
+extern "C" int bean_hip_simulate(bean_hip_ctx* c, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
+                                 void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes,
+                                 void* stream_) {
+    const std::string name = "bean_hip_simulate";
+    if (postfit_admit(c, name, kSimStem)) return -1;
+    if (check_bound(c, false, false)) return -1;
+    if (sim_buffers(c, name, "(R, B, G) float32", 1, x_out, x_bytes, xbc_out, xbc_bytes)) return -1;
+    if (buf_optional(name, "alpha_out", "(2, R, B, G) float64", alpha_out, alpha_bytes,
+                     16 * (uint64_t)c->d.R * c->d.B * c->d.G))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    return simulate_run(c, seed, draw, 1, x_out, xbc_out, alpha_out, stream,
+                        [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
+                            hipLaunchKernelGGL((k_simulate_wave2<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa);
+                        });
 }
 
 // K replicate screens in one launch (k_simulate_members: a parametric bootstrap's screens, member-major - what
@@ -2729,157 +2811,76 @@ extern "C" int bean_hip_simulate(bean_hip_ctx* c, uint64_t seed, uint64_t draw, 
 extern "C" int bean_hip_simulate_members(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
                                          void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes,
                                          void* stream_) {
-    if (!c) return fail("bean_hip_simulate_members: null handle");
-    if (!predictive_shape_ok(c))
-        return fail("bean_hip_simulate_members: the count simulator does not take this handle "
-                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
-                    "covariates, one member, one particle");
-    if (!c->prepared) return fail("bean_hip_simulate_members: call bean_hip_prepare first");
+    const std::string name = "bean_hip_simulate_members";
+    if (postfit_admit(c, name, kSimStem)) return -1;
     if (n_draws < 1 || n_draws > BEAN_HIP_MAX_MEMBERS)
-        return fail("bean_hip_simulate_members: n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) +
-                    "], got " + std::to_string(n_draws));
+        return fail(name + ": n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) + "], got " +
+                    std::to_string(n_draws));
     if (check_bound(c, false, false)) return -1;
-    const DevArgs& d0 = c->d;
-    const uint64_t n = (uint64_t)n_draws * d0.R * d0.B * d0.G;
-    const bool use_bc = (d0.flags & kUseBc) != 0;
-    const std::string shape = "(K, R, B, G) float32 with K = " + std::to_string(n_draws) + ", " + std::to_string(4 * n) +
-                              " bytes";
-    if (!x_out || x_bytes != 4 * n) return fail("bean_hip_simulate_members: x_out must hold " + shape);
-    if (use_bc && (!xbc_out || xbc_bytes != 4 * n))
-        return fail("bean_hip_simulate_members: this handle uses the barcode-matched counts: xbc_out must hold " + shape);
-    if (!use_bc && (xbc_out || xbc_bytes))
-        return fail("bean_hip_simulate_members: xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
+    if (sim_buffers(c, name, "(K, R, B, G) float32 with K = " + std::to_string(n_draws), (uint64_t)n_draws, x_out,
+                    x_bytes, xbc_out, xbc_bytes))
+        return -1;
     hipStream_t stream = (hipStream_t)stream_;
-    c->d.seed = seed;
-    c->resume_ok = false;  // the workspace now holds draw first_draw and its tables
-    launch_set_step(c, stream, first_draw, 0, 0);
-    launch_param<false, false, true>(c, stream);
-    const DevArgs& d = c->d;
-    SimArgs sa;
-    sa.x_out = (float*)x_out;
-    sa.xbc_out = (float*)xbc_out;
-    sa.alpha_out = nullptr;
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)n_draws), block(64);
-    const size_t lds = simulate_wave2_lds(d.B);
-    with_family_acc(d, [&](auto fam, auto acc) {
-        hipLaunchKernelGGL((k_simulate_members<fam(), acc()>), grid, block, lds, stream, d, sa);
-    });
-    HIP_OK(hipGetLastError());
-    return 0;
+    return simulate_run(c, seed, first_draw, (unsigned)n_draws, x_out, xbc_out, nullptr, stream,
+                        [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
+                            hipLaunchKernelGGL((k_simulate_members<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa);
+                        });
 }
 
 // K replicate screens at each of D read depths in one launch (k_simulate_design: a depth study's screens, (D, K)
 // member-major - D * K members of bean_hip_bind_member_counts).  Everything of member (i, j) but its totals is member j
-// of bean_hip_simulate_members(seed, first_draw, K); its pairs draw floor(depths[i] * n_obs + 0.5) reads.  The depths
-// are copied into the launch's argument struct here: the caller's array is not read after the call returns.
+// of bean_hip_simulate_members(seed, first_draw, K); its pairs draw floor(depths[i] * n_obs + 0.5) reads.
 extern "C" int bean_hip_simulate_design(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
                                         const double* depths, int32_t n_depths, void* x_out, uint64_t x_bytes,
                                         void* xbc_out, uint64_t xbc_bytes, void* stream_) {
-    if (!c) return fail("bean_hip_simulate_design: null handle");
-    if (!predictive_shape_ok(c))
-        return fail("bean_hip_simulate_design: the count simulator does not take this handle "
-                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
-                    "covariates, one member, one particle");
-    if (!c->prepared) return fail("bean_hip_simulate_design: call bean_hip_prepare first");
-    if (!depths) return fail("bean_hip_simulate_design: depths is null");
-    if (n_depths < 1 || n_draws < 1 || (int64_t)n_depths * n_draws > BEAN_HIP_MAX_MEMBERS)
-        return fail("bean_hip_simulate_design: n_depths >= 1, n_draws >= 1 and n_depths * n_draws <= " +
-                    std::to_string(BEAN_HIP_MAX_MEMBERS) + ", got " + std::to_string(n_depths) + " x " +
-                    std::to_string(n_draws) + " = " + std::to_string((int64_t)n_depths * n_draws));
-    for (int i = 0; i < n_depths; ++i)
-        if (!(depths[i] > 0.0) || !(depths[i] <= 1.7976931348623157e308))
-            return fail("bean_hip_simulate_design: depths[" + std::to_string(i) + "] = " + std::to_string(depths[i]) +
-                        " is not a finite factor > 0");
-    if (check_bound(c, false, false)) return -1;
-    const DevArgs& d0 = c->d;
-    const uint64_t n = (uint64_t)n_depths * n_draws * d0.R * d0.B * d0.G;
-    const bool use_bc = (d0.flags & kUseBc) != 0;
-    const std::string shape = "(D, K, R, B, G) float32 with D = " + std::to_string(n_depths) + ", K = " +
-                              std::to_string(n_draws) + ", " + std::to_string(4 * n) + " bytes";
-    if (!x_out || x_bytes != 4 * n) return fail("bean_hip_simulate_design: x_out must hold " + shape);
-    if (use_bc && (!xbc_out || xbc_bytes != 4 * n))
-        return fail("bean_hip_simulate_design: this handle uses the barcode-matched counts: xbc_out must hold " + shape);
-    if (!use_bc && (xbc_out || xbc_bytes))
-        return fail("bean_hip_simulate_design: xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
-    hipStream_t stream = (hipStream_t)stream_;
-    c->d.seed = seed;
-    c->resume_ok = false;  // the workspace now holds draw first_draw and its tables
-    launch_set_step(c, stream, first_draw, 0, 0);
-    launch_param<false, false, true>(c, stream);
-    const DevArgs& d = c->d;
-    SimArgs sa;
-    sa.x_out = (float*)x_out;
-    sa.xbc_out = (float*)xbc_out;
-    sa.alpha_out = nullptr;
+    const std::string name = "bean_hip_simulate_design";
+    if (postfit_admit(c, name, kSimStem)) return -1;
     DesignArgs dz;
     dz.K = n_draws;
     dz.D = n_depths;
-    for (int i = 0; i < kEnsembleMaxMembers; ++i) dz.depth[i] = i < n_depths ? depths[i] : 1.0;
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)(n_depths * n_draws)), block(64);
-    const size_t lds = simulate_wave2_lds(d.B);
-    with_family_acc(d, [&](auto fam, auto acc) {
-        hipLaunchKernelGGL((k_simulate_design<fam(), acc()>), grid, block, lds, stream, d, sa, dz);
-    });
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (study_values(name, "depths", [](double v) { return v > 0.0 && v <= 1.7976931348623157e308; },
+                     " is not a finite factor > 0", depths, n_depths, n_draws, 1.0, dz.depth))
+        return -1;
+    if (check_bound(c, false, false)) return -1;
+    const uint64_t planes = (uint64_t)n_depths * n_draws;
+    if (sim_buffers(c, name, "(D, K, R, B, G) float32 with D = " + std::to_string(n_depths) + ", K = " +
+                    std::to_string(n_draws), planes, x_out, x_bytes, xbc_out, xbc_bytes))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    return simulate_run(c, seed, first_draw, (unsigned)planes, x_out, xbc_out, nullptr, stream,
+                        [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
+                            hipLaunchKernelGGL((k_simulate_design<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa,
+                                               dz);
+                        });
 }
 
 // K replicate screens at each of D planted effects in one launch (k_simulate_power: a power study's screens, (D, K)
 // member-major - D * K members of bean_hip_bind_member_counts).  Everything of member (i, j) is member j of
 // bean_hip_simulate_members(seed, first_draw, K) but the table entries of the planted targets, which its lanes form at
-// mu = effects[i].  The effects are copied into the launch's argument struct here: the caller's array is not read after
-// the call returns; `plant` is the caller's device array and is read by the kernel.
+// mu = effects[i].  `plant` is the caller's device array and is read by the kernel.
 extern "C" int bean_hip_simulate_power(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
                                        const double* effects, int32_t n_effects, const void* plant, void* x_out,
                                        uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes, void* stream_) {
-    if (!c) return fail("bean_hip_simulate_power: null handle");
-    if (!predictive_shape_ok(c))
-        return fail("bean_hip_simulate_power: the count simulator does not take this handle "
-                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
-                    "covariates, one member, one particle");
-    if (!c->prepared) return fail("bean_hip_simulate_power: call bean_hip_prepare first");
-    if (!effects) return fail("bean_hip_simulate_power: effects is null");
-    if (n_effects < 1 || n_draws < 1 || (int64_t)n_effects * n_draws > BEAN_HIP_MAX_MEMBERS)
-        return fail("bean_hip_simulate_power: n_effects >= 1, n_draws >= 1 and n_effects * n_draws <= " +
-                    std::to_string(BEAN_HIP_MAX_MEMBERS) + ", got " + std::to_string(n_effects) + " x " +
-                    std::to_string(n_draws) + " = " + std::to_string((int64_t)n_effects * n_draws));
-    for (int i = 0; i < n_effects; ++i)
-        if (!(effects[i] >= -1.7976931348623157e308 && effects[i] <= 1.7976931348623157e308))
-            return fail("bean_hip_simulate_power: effects[" + std::to_string(i) + "] = " + std::to_string(effects[i]) +
-                        " is not a finite number");
-    if (check_bound(c, false, false)) return -1;
-    const DevArgs& d0 = c->d;
-    const uint64_t n = (uint64_t)n_effects * n_draws * d0.R * d0.B * d0.G;
-    const bool use_bc = (d0.flags & kUseBc) != 0;
-    const std::string shape = "(D, K, R, B, G) float32 with D = " + std::to_string(n_effects) + ", K = " +
-                              std::to_string(n_draws) + ", " + std::to_string(4 * n) + " bytes";
-    if (!x_out || x_bytes != 4 * n) return fail("bean_hip_simulate_power: x_out must hold " + shape);
-    if (use_bc && (!xbc_out || xbc_bytes != 4 * n))
-        return fail("bean_hip_simulate_power: this handle uses the barcode-matched counts: xbc_out must hold " + shape);
-    if (!use_bc && (xbc_out || xbc_bytes))
-        return fail("bean_hip_simulate_power: xbc_out on a handle without BEAN_FLAG_USE_BCMATCH");
-    hipStream_t stream = (hipStream_t)stream_;
-    c->d.seed = seed;
-    c->resume_ok = false;  // the workspace now holds draw first_draw and its tables
-    launch_set_step(c, stream, first_draw, 0, 0);
-    launch_param<false, false, true>(c, stream);
-    const DevArgs& d = c->d;
-    SimArgs sa;
-    sa.x_out = (float*)x_out;
-    sa.xbc_out = (float*)xbc_out;
-    sa.alpha_out = nullptr;
+    const std::string name = "bean_hip_simulate_power";
+    if (postfit_admit(c, name, kSimStem)) return -1;
     PowerArgs pw;
     pw.K = n_draws;
     pw.D = n_effects;
     pw.plant = (const uint8_t*)plant;
-    for (int i = 0; i < kEnsembleMaxMembers; ++i) pw.effect[i] = i < n_effects ? effects[i] : 0.0;
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)(n_effects * n_draws)), block(64);
-    const size_t lds = simulate_wave2_lds(d.B);
-    with_family_acc(d, [&](auto fam, auto acc) {
-        hipLaunchKernelGGL((k_simulate_power<fam(), acc()>), grid, block, lds, stream, d, sa, pw);
-    });
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (study_values(name, "effects", [](double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; },
+                     " is not a finite number", effects, n_effects, n_draws, 0.0, pw.effect))
+        return -1;
+    if (check_bound(c, false, false)) return -1;
+    const uint64_t planes = (uint64_t)n_effects * n_draws;
+    if (sim_buffers(c, name, "(D, K, R, B, G) float32 with D = " + std::to_string(n_effects) + ", K = " +
+                    std::to_string(n_draws), planes, x_out, x_bytes, xbc_out, xbc_bytes))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    return simulate_run(c, seed, first_draw, (unsigned)planes, x_out, xbc_out, nullptr, stream,
+                        [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
+                            hipLaunchKernelGGL((k_simulate_power<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa,
+                                               pw);
+                        });
 }
 
 // ------------------------------------------------------------------ per-target log importance weights
@@ -2888,36 +2889,12 @@ extern "C" int bean_hip_simulate_power(bean_hip_ctx* c, uint64_t seed, uint64_t 
 // draw bean_hip_elbo_grad(seed, step = d) evaluates, formed by the lanes themselves - three launches per call whatever
 // n_draws (the pairs' data-only constants, the pairs, the targets), no k_set_step, no PREP launch, nothing of the
 // workspace written.
-extern "C" int bean_hip_log_weights(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws, void* logw_out,
-                                    uint64_t logw_bytes, void* mu_out, uint64_t mu_bytes, void* y_out, uint64_t y_bytes,
-                                    void* pair_out, uint64_t pair_bytes, void* stream_) {
-    if (!c) return fail("bean_hip_log_weights: null handle");
-    if (!predictive_shape_ok(c))
-        return fail("bean_hip_log_weights: the importance weights do not take this handle "
-                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
-                    "covariates, one member, one particle");
-    if (!c->prepared) return fail("bean_hip_log_weights: call bean_hip_prepare first");
-    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_LOGW_DRAWS)
-        return fail("bean_hip_log_weights: n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) +
-                    "], got " + std::to_string(n_draws));
-    if (check_bound(c, false, false)) return -1;
-    const DevArgs& d0 = c->d;
-    const uint64_t nt = (uint64_t)n_draws * d0.T, np = (uint64_t)n_draws * d0.R * d0.G;
-    const std::string sn = " float64 with n_draws = " + std::to_string(n_draws) + ", ";
-    if (!logw_out || logw_bytes != 8 * nt)
-        return fail("bean_hip_log_weights: logw_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) + " bytes");
-    if (!mu_out || mu_bytes != 8 * nt)
-        return fail("bean_hip_log_weights: mu_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) + " bytes");
-    if (y_out ? y_bytes != 8 * nt : y_bytes != 0)
-        return fail("bean_hip_log_weights: y_out must be null or hold (n_draws, T)" + sn + std::to_string(8 * nt) +
-                    " bytes");
-    if (!pair_out || pair_bytes != 8 * np)
-        return fail("bean_hip_log_weights: pair_out (caller-owned scratch) must hold (n_draws, R, G)" + sn +
-                    std::to_string(8 * np) + " bytes");
-    hipStream_t stream = (hipStream_t)stream_;
-    c->d.seed = seed;
-    c->resume_ok = false;  // (the seed of the handle has changed)
-    const DevArgs& d = c->d;
+//
+// ... with pi integrated out of the model (`marginal`, bean_importance_marg.hpp): logw_marg of the same draws, the
+// weight of (mu_t, sd_t) alone.  MixtureNormal: four launches per call whatever n_draws (the pairs' constants, the
+// unresolved pairs per target, the pairs' integrals, the targets); Normal has no pi: exactly the launches of
+// bean_hip_log_weights and unresolved_out zeroed.
+static LogwArgs logw_args(uint64_t first_draw, int n_draws, void* logw_out, void* mu_out, void* y_out, void* pair_out) {
     LogwArgs la;
     la.first_draw = first_draw;
     la.n_draws = n_draws;
@@ -2925,100 +2902,78 @@ extern "C" int bean_hip_log_weights(bean_hip_ctx* c, uint64_t seed, uint64_t fir
     la.mu_out = (double*)mu_out;
     la.y_out = (double*)y_out;
     la.pair_out = (double*)pair_out;
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)n_draws), block(64);
-    const size_t lds = simulate_wave2_lds(d.B);
-    const uint64_t rg = (uint64_t)d.R * d.G;
-    hipLaunchKernelGGL(k_logw_consts, dim3((unsigned)((rg + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
-                       la);
-    with_family_acc(d, [&](auto fam, auto acc) {
-        hipLaunchKernelGGL((k_logw_pairs<fam(), acc()>), grid, block, lds, stream, d, la);
-    });
-    hipLaunchKernelGGL(k_logw_targets, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream,
-                       d, la);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return la;
 }
 
-// ------------------------------------------------------------------ ... with pi integrated out of the model
-// (bean_importance_marg.hpp) logw_marg of the same draws: the weight of (mu_t, sd_t) alone.  MixtureNormal: four launches
-// per call whatever n_draws (the pairs' constants, the unresolved pairs per target, the pairs' integrals, the targets);
-// Normal has no pi: exactly the launches of bean_hip_log_weights and unresolved_out zeroed.
-extern "C" int bean_hip_log_weights_marginal(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
-                                             int32_t n_nodes, void* logw_out, uint64_t logw_bytes, void* mu_out,
-                                             uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out,
-                                             uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
-                                             void* stream_) {
-    if (!c) return fail("bean_hip_log_weights_marginal: null handle");
-    if (!predictive_shape_ok(c))
-        return fail("bean_hip_log_weights_marginal: the importance weights do not take this handle "
-                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
-                    "covariates, one member, one particle");
-    if (!c->prepared) return fail("bean_hip_log_weights_marginal: call bean_hip_prepare first");
-    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_LOGW_DRAWS)
-        return fail("bean_hip_log_weights_marginal: n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) +
-                    "], got " + std::to_string(n_draws));
-    if (n_nodes != 16 && n_nodes != 32 && n_nodes != 64)
-        return fail("bean_hip_log_weights_marginal: n_nodes must be 16, 32 or 64, got " + std::to_string(n_nodes));
-    if (check_bound(c, false, false)) return -1;
-    const DevArgs& d0 = c->d;
-    const uint64_t nt = (uint64_t)n_draws * d0.T, np = (uint64_t)n_draws * d0.R * d0.G;
-    const std::string sn = " float64 with n_draws = " + std::to_string(n_draws) + ", ";
-    if (!logw_out || logw_bytes != 8 * nt)
-        return fail("bean_hip_log_weights_marginal: logw_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) +
-                    " bytes");
-    if (!mu_out || mu_bytes != 8 * nt)
-        return fail("bean_hip_log_weights_marginal: mu_out must hold (n_draws, T)" + sn + std::to_string(8 * nt) +
-                    " bytes");
-    if (y_out ? y_bytes != 8 * nt : y_bytes != 0)
-        return fail("bean_hip_log_weights_marginal: y_out must be null or hold (n_draws, T)" + sn +
-                    std::to_string(8 * nt) + " bytes");
-    if (!pair_out || pair_bytes != 8 * np)
-        return fail("bean_hip_log_weights_marginal: pair_out (caller-owned scratch) must hold (n_draws, R, G)" + sn +
-                    std::to_string(8 * np) + " bytes");
-    if (!unresolved_out || unresolved_bytes != 4 * (uint64_t)d0.T)
-        return fail("bean_hip_log_weights_marginal: unresolved_out must hold (T) int32, " +
-                    std::to_string(4 * (uint64_t)d0.T) + " bytes");
-    hipStream_t stream = (hipStream_t)stream_;
-    if (d0.family != kMixture) {
-        // no pi to integrate out: the joint weights are the marginal ones, and no pair is unresolved
-        HIP_OK(hipMemsetAsync(unresolved_out, 0, unresolved_bytes, stream));
-        return bean_hip_log_weights(c, seed, first_draw, n_draws, logw_out, logw_bytes, mu_out, mu_bytes, y_out, y_bytes,
-                                    pair_out, pair_bytes, stream_);
-    }
-    c->d.seed = seed;
-    c->resume_ok = false;  // (the seed of the handle has changed)
-    const DevArgs& d = c->d;
-    LogwArgs la;
-    la.first_draw = first_draw;
-    la.n_draws = n_draws;
-    la.logw_out = (double*)logw_out;
-    la.mu_out = (double*)mu_out;
-    la.y_out = (double*)y_out;
-    la.pair_out = (double*)pair_out;
+static MargArgs marg_args(int32_t n_nodes, void* unresolved_out) {
     MargArgs ma;
     memset(&ma, 0, sizeof(ma));
     ma.n_nodes = n_nodes;
     ma.unresolved_out = (int*)unresolved_out;
     gauss_hermite_half(n_nodes, ma.x, ma.lw);
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)n_draws), block(64);
-    const size_t lds = logw_marg_lds(d.B);
-    const uint64_t rg = (uint64_t)d.R * d.G;
-    hipLaunchKernelGGL(k_logw_consts, dim3((unsigned)((rg + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
-                       la);
-    hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
-                       stream, d, ma);
-    if (d.flags & kAcc) hipLaunchKernelGGL(k_logw_pairs_marg<true>, grid, block, lds, stream, d, la, ma);
-    else hipLaunchKernelGGL(k_logw_pairs_marg<false>, grid, block, lds, stream, d, la, ma);
-    hipLaunchKernelGGL(k_logw_targets_marg, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
-                       stream, d, la);
+    return ma;
+}
+
+static int logw_run(bean_hip_ctx* c, const std::string& name, bool marginal, uint64_t seed, uint64_t first_draw,
+                    int32_t n_draws, int32_t n_nodes, void* logw_out, uint64_t logw_bytes, void* mu_out,
+                    uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out, uint64_t pair_bytes,
+                    void* unresolved_out, uint64_t unresolved_bytes, void* stream_) {
+    if (postfit_admit(c, name, "the importance weights do not take this handle")) return -1;
+    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_LOGW_DRAWS)
+        return fail(name + ": n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) + "], got " +
+                    std::to_string(n_draws));
+    if (marginal && n_nodes != 16 && n_nodes != 32 && n_nodes != 64)
+        return fail(name + ": n_nodes must be 16, 32 or 64, got " + std::to_string(n_nodes));
+    if (check_bound(c, false, false)) return -1;
+    if (logw_buffers(c, name, n_draws, logw_out, logw_bytes, mu_out, mu_bytes, y_out, y_bytes, pair_out, pair_bytes))
+        return -1;
+    if (marginal && buf_exact(name, "unresolved_out", "(T) int32", unresolved_out, unresolved_bytes, 4 * (uint64_t)c->d.T))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    const bool integrate = marginal && c->d.family == kMixture;
+    // no pi to integrate out: the joint weights are the marginal ones, and no pair is unresolved
+    if (marginal && !integrate) HIP_OK(hipMemsetAsync(unresolved_out, 0, unresolved_bytes, stream));
+    c->d.seed = seed;
+    c->resume_ok = false;  // (the seed of the handle has changed)
+    const DevArgs& d = c->d;
+    const LogwArgs la = logw_args(first_draw, n_draws, logw_out, mu_out, y_out, pair_out);
+    const dim3 grid = pair_grid(d, (unsigned)n_draws), block(64);
+    const uint64_t nt = (uint64_t)n_draws * d.T;
+    hipLaunchKernelGGL(k_logw_consts, logw_blocks((uint64_t)d.R * d.G), dim3(kLogwBlock), 0, stream, d, la);
+    if (!integrate) {
+        const size_t lds = simulate_wave2_lds(d.B);
+        with_family_acc(d, [&](auto fam, auto acc) {
+            hipLaunchKernelGGL((k_logw_pairs<fam(), acc()>), grid, block, lds, stream, d, la);
+        });
+        hipLaunchKernelGGL(k_logw_targets, logw_blocks(nt), dim3(kLogwBlock), 0, stream, d, la);
+    } else {
+        const MargArgs ma = marg_args(n_nodes, unresolved_out);
+        const size_t lds = logw_marg_lds(d.B);
+        hipLaunchKernelGGL(k_logw_unresolved, logw_blocks(d.T), dim3(kLogwBlock), 0, stream, d, ma);
+        if (d.flags & kAcc) hipLaunchKernelGGL(k_logw_pairs_marg<true>, grid, block, lds, stream, d, la, ma);
+        else hipLaunchKernelGGL(k_logw_pairs_marg<false>, grid, block, lds, stream, d, la, ma);
+        hipLaunchKernelGGL(k_logw_targets_marg, logw_blocks(nt), dim3(kLogwBlock), 0, stream, d, la);
+    }
     HIP_OK(hipGetLastError());
     return 0;
 }
 
-// ------------------------------------------------------------------ the log joint on a grid of (mu, y) per target
-// (bean_grid.hpp) lj of n_mu * n_y given nodes per target, pi integrated out: four launches per call whatever the grid
-// (the pairs' constants, the unresolved pairs per target, the pairs' terms, the targets).  No seed, no draw, no term of
-// q; nothing of the handle is written.
+extern "C" int bean_hip_log_weights(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws, void* logw_out,
+                                    uint64_t logw_bytes, void* mu_out, uint64_t mu_bytes, void* y_out, uint64_t y_bytes,
+                                    void* pair_out, uint64_t pair_bytes, void* stream_) {
+    return logw_run(c, "bean_hip_log_weights", false, seed, first_draw, n_draws, 0, logw_out, logw_bytes, mu_out, mu_bytes,
+                    y_out, y_bytes, pair_out, pair_bytes, nullptr, 0, stream_);
+}
+
+extern "C" int bean_hip_log_weights_marginal(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                             int32_t n_nodes, void* logw_out, uint64_t logw_bytes, void* mu_out,
+                                             uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out,
+                                             uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
+                                             void* stream_) {
+    return logw_run(c, "bean_hip_log_weights_marginal", true, seed, first_draw, n_draws, n_nodes, logw_out, logw_bytes,
+                    mu_out, mu_bytes, y_out, y_bytes, pair_out, pair_bytes, unresolved_out, unresolved_bytes, stream_);
+}
+
 // ------------------------------------------------------------------ the log joint on a grid of (mu, y) per target
 // (bean_grid.hpp) lj of n_mu * n_y given nodes per target, pi integrated out: four launches per call whatever the grid
 // (the pairs' constants, the unresolved pairs per target, the pairs' terms, the targets).  No seed, no draw, no term of
@@ -3041,15 +2996,16 @@ static int tail_reserve(bean_hip_ctx* c, uint64_t bytes) {
     return 0;
 }
 
-// the unresolved count (into `unresolved`, (T) int32 on the device), its scan, and the number of tail pairs on the host
+// the unresolved count (into `unresolved`, (T) int32 on the device; null: the T slots the handle keeps behind its
+// offsets), its scan, and the number of tail pairs on the host
 static int tail_count(bean_hip_ctx* c, int* unresolved, TailArgs& ta, hipStream_t stream) {
     const DevArgs& d = c->d;
     if (tail_reserve(c, 0)) return -1;
+    if (!unresolved) unresolved = c->tail_off + d.T + 1;  // (there only once tail_reserve has run)
     MargArgs ma;
     memset(&ma, 0, sizeof(ma));
     ma.unresolved_out = unresolved;
-    hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0,
-                       stream, d, ma);
+    hipLaunchKernelGGL(k_logw_unresolved, logw_blocks(d.T), dim3(kLogwBlock), 0, stream, d, ma);
     memset(&ta, 0, sizeof(ta));
     ta.unresolved = unresolved;
     ta.toff = c->tail_off;
@@ -3063,26 +3019,15 @@ static int tail_count(bean_hip_ctx* c, int* unresolved, TailArgs& ta, hipStream_
 
 // the compact list and the 64 + 48 nodes and log weights of every tail pair, into ta's arrays
 static void tail_nodes_launch(const DevArgs& d, const TailArgs& ta, hipStream_t stream) {
-    hipLaunchKernelGGL(k_tail_list, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
-                       ta);
-    const uint64_t nn = (uint64_t)ta.n_tail * kTailAll;
-    hipLaunchKernelGGL(k_tail_nodes, dim3((unsigned)((nn + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
-                       ta);
+    hipLaunchKernelGGL(k_tail_list, logw_blocks(d.T), dim3(kLogwBlock), 0, stream, d, ta);
+    hipLaunchKernelGGL(k_tail_nodes, logw_blocks((uint64_t)ta.n_tail * kTailAll), dim3(kLogwBlock), 0, stream, d, ta);
 }
 
 static int grid_run(bean_hip_ctx* c, const std::string& name, bool tail, int32_t n_nodes, int32_t n_mu, int32_t n_y,
                     const void* centre_mu, const void* centre_y, const void* step_mu, const void* step_y, void* lj_out,
                     uint64_t lj_bytes, void* pair_out, uint64_t pair_bytes, void* unresolved_out,
                     uint64_t unresolved_bytes, void* tail_err_out, uint64_t tail_err_bytes, void* stream_) {
-    if (!c) return fail(name + ": null handle");
-    if (!predictive_shape_ok(c))
-        return fail(name + ": the grid posterior does not take this handle "
-                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
-                    "covariates, one member, one particle");
-    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
-    if (c->shape.flags & BEAN_FLAG_SCALE_BY_ACC)
-        return fail(name + ": a handle with accessibility (BEAN_FLAG_SCALE_BY_ACC) is refused: the guide "
-                    "noise is a further latent per guide, so the posterior of a target is not 2-D");
+    if (grid_admit(c, name)) return -1;
     if (n_nodes != 16 && n_nodes != 32 && n_nodes != 64)
         return fail(name + ": n_nodes must be 16, 32 or 64, got " + std::to_string(n_nodes));
     if (n_mu < 1 || n_y < 1 || (int64_t)n_mu * n_y > BEAN_HIP_MAX_LOGW_DRAWS)
@@ -3096,25 +3041,15 @@ static int grid_run(bean_hip_ctx* c, const std::string& name, bool tail, int32_t
     if (!centre_mu || !centre_y || !step_mu || !step_y)
         return fail(name + ": centre_mu, centre_y, step_mu and step_y must each hold (T) float64 on the "
                     "device; one of them is null");
-    const std::string sn = " float64 with N = n_mu * n_y = " + std::to_string(N) + ", ";
-    if (!lj_out || lj_bytes != 8 * nt)
-        return fail(name + ": lj_out must hold (N, T)" + sn + std::to_string(8 * nt) + " bytes");
-    if (!pair_out || pair_bytes != 8 * np)
-        return fail(name + ": pair_out (caller-owned scratch) must hold (N, R, G)" + sn +
-                    std::to_string(8 * np) + " bytes");
-    if (!unresolved_out || unresolved_bytes != 4 * (uint64_t)d.T)
-        return fail(name + ": unresolved_out must hold (T) int32 (N = " + std::to_string(N) + "), " +
-                    std::to_string(4 * (uint64_t)d.T) + " bytes");
-    if (tail && (!tail_err_out || tail_err_bytes != 8 * nt))
-        return fail(name + ": tail_err_out must hold (N, T)" + sn + std::to_string(8 * nt) + " bytes");
+    const std::string of = " float64 with N = n_mu * n_y = " + std::to_string(N);
+    if (buf_exact(name, "lj_out", "(N, T)" + of, lj_out, lj_bytes, 8 * nt)) return -1;
+    if (buf_exact(name, "pair_out (caller-owned scratch)", "(N, R, G)" + of, pair_out, pair_bytes, 8 * np)) return -1;
+    if (buf_exact(name, "unresolved_out", "(T) int32 (N = " + std::to_string(N) + ")", unresolved_out, unresolved_bytes,
+                  4 * (uint64_t)d.T))
+        return -1;
+    if (tail && buf_exact(name, "tail_err_out", "(N, T)" + of, tail_err_out, tail_err_bytes, 8 * nt)) return -1;
     hipStream_t stream = (hipStream_t)stream_;
-    LogwArgs la;
-    la.first_draw = 0;
-    la.n_draws = N;
-    la.logw_out = nullptr;
-    la.mu_out = nullptr;
-    la.y_out = nullptr;
-    la.pair_out = (double*)pair_out;
+    const LogwArgs la = logw_args(0, N, nullptr, nullptr, nullptr, pair_out);
     GridArgs ga;
     ga.n_mu = n_mu;
     ga.n_y = n_y;
@@ -3124,15 +3059,9 @@ static int grid_run(bean_hip_ctx* c, const std::string& name, bool tail, int32_t
     ga.step_y = (const double*)step_y;
     ga.lj_out = (double*)lj_out;
     ga.pair_out = (double*)pair_out;
-    MargArgs ma;
-    memset(&ma, 0, sizeof(ma));
-    ma.n_nodes = n_nodes;
-    ma.unresolved_out = (int*)unresolved_out;
-    gauss_hermite_half(n_nodes, ma.x, ma.lw);
-    const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)((N + kGridChunk - 1) / kGridChunk)),
-        block(64);
+    const MargArgs ma = marg_args(n_nodes, unresolved_out);
+    const dim3 grid = pair_grid(d, (unsigned)((N + kGridChunk - 1) / kGridChunk)), block(64);
     const size_t lds = logw_marg_lds(d.B);
-    const uint64_t rg = (uint64_t)d.R * d.G;
     TailArgs ta;
     memset(&ta, 0, sizeof(ta));
     if (tail && d.family == kMixture) {
@@ -3160,12 +3089,9 @@ static int grid_run(bean_hip_ctx* c, const std::string& name, bool tail, int32_t
             tail_nodes_launch(d, ta, stream);
         }
     }
-    hipLaunchKernelGGL(k_logw_consts, dim3((unsigned)((rg + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream, d,
-                       la);
+    hipLaunchKernelGGL(k_logw_consts, logw_blocks((uint64_t)d.R * d.G), dim3(kLogwBlock), 0, stream, d, la);
     if (d.family == kMixture) {
-        if (!tail)
-            hipLaunchKernelGGL(k_logw_unresolved, dim3((unsigned)((d.T + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock),
-                               0, stream, d, ma);
+        if (!tail) hipLaunchKernelGGL(k_logw_unresolved, logw_blocks(d.T), dim3(kLogwBlock), 0, stream, d, ma);
         hipLaunchKernelGGL(k_grid_pairs<kMixture>, grid, block, lds, stream, d, ga, ma);
         if (ta.n_tail > 0)
             hipLaunchKernelGGL(k_grid_pairs_tail, dim3((unsigned)((ta.n_tail + 63) / 64),
@@ -3176,14 +3102,10 @@ static int grid_run(bean_hip_ctx* c, const std::string& name, bool tail, int32_t
         HIP_OK(hipMemsetAsync(unresolved_out, 0, unresolved_bytes, stream));
         hipLaunchKernelGGL(k_grid_pairs<kNormal>, grid, block, lds, stream, d, ga, ma);
     }
-    hipLaunchKernelGGL(k_grid_targets, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock), 0, stream,
-                       d, ga);
+    hipLaunchKernelGGL(k_grid_targets, logw_blocks(nt), dim3(kLogwBlock), 0, stream, d, ga);
     if (tail) {
-        if (ta.n_tail > 0)
-            hipLaunchKernelGGL(k_grid_targets_tail, dim3((unsigned)((nt + kLogwBlock - 1) / kLogwBlock)), dim3(kLogwBlock),
-                               0, stream, d, ta);
-        else
-            HIP_OK(hipMemsetAsync(tail_err_out, 0, tail_err_bytes, stream));
+        if (ta.n_tail > 0) hipLaunchKernelGGL(k_grid_targets_tail, logw_blocks(nt), dim3(kLogwBlock), 0, stream, d, ta);
+        else HIP_OK(hipMemsetAsync(tail_err_out, 0, tail_err_bytes, stream));
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -3214,15 +3136,7 @@ extern "C" int bean_hip_marginal_grid_tail(bean_hip_ctx* c, int32_t n_nodes, int
 extern "C" int bean_hip_marginal_tail_nodes(bean_hip_ctx* c, int32_t capacity, void* pair_index_out, void* z_out,
                                             void* lw_out, void* side_out, int32_t* n_tail_out, void* stream_) {
     const std::string name = "bean_hip_marginal_tail_nodes";
-    if (!c) return fail(name + ": null handle");
-    if (!predictive_shape_ok(c))
-        return fail(name + ": the grid posterior does not take this handle "
-                    "(bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, unsharded, no sample "
-                    "covariates, one member, one particle");
-    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
-    if (c->shape.flags & BEAN_FLAG_SCALE_BY_ACC)
-        return fail(name + ": a handle with accessibility (BEAN_FLAG_SCALE_BY_ACC) is refused: the guide "
-                    "noise is a further latent per guide, so the posterior of a target is not 2-D");
+    if (grid_admit(c, name)) return -1;
     if (!n_tail_out) return fail(name + ": n_tail_out is null");
     if (capacity < 0) return fail(name + ": capacity must not be negative, got " + std::to_string(capacity));
     if (capacity > 0 && (!pair_index_out || !z_out || !lw_out || !side_out))
@@ -3233,8 +3147,7 @@ extern "C" int bean_hip_marginal_tail_nodes(bean_hip_ctx* c, int32_t capacity, v
     if (d.family != kMixture) return 0;
     hipStream_t stream = (hipStream_t)stream_;
     TailArgs ta;
-    if (tail_reserve(c, 0)) return -1;
-    if (tail_count(c, c->tail_off + d.T + 1, ta, stream)) return -1;
+    if (tail_count(c, nullptr, ta, stream)) return -1;
     *n_tail_out = ta.n_tail;
     if (capacity == 0 || ta.n_tail == 0) return 0;
     if (capacity < ta.n_tail)

@@ -44,6 +44,16 @@ class PredictiveUnsupported(ValueError):
     """A posterior predictive check on a shape the count simulator does not take (``bean_hip_predictive_supported``)."""
 
 
+def _ptr(t):
+    """A tensor's device address as the library takes it; ``None`` is a null pointer."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _nbytes(t):
+    """The bytes a tensor holds; 0 for ``None``."""
+    return 0 if t is None else t.numel() * t.element_size()
+
+
 def particle_mean(values):
     """Mean of P tensors as a particle step forms it (``include/bean_hip.h``): a float64 accumulator that starts from the
     first and adds the others in order, ONE multiply by ``1.0 / P``, then one rounding to the inputs' dtype."""
@@ -814,6 +824,32 @@ class HipSVI:
         fn = getattr(self.lib, "bean_hip_predictive_supported", None)
         return fn is not None and fn(self._h) == 1
 
+    def _require_predictive(self, what: str, grid: bool = False, have: bool = True):
+        """Raise ``PredictiveUnsupported`` unless the post-fit kernels take this engine; ``what`` begins the sentence
+        ("the count simulator does not take"), ``grid`` also refuses accessibility, ``have`` is whether the library has
+        the entry point."""
+        acc = grid and self.scale_by_accessibility
+        if self.predictive_supported and have and not acc:
+            return
+        raise PredictiveUnsupported(f"{what} this engine ({self.family}{', survival' if self.survival else ''}"
+                                    f"{', accessibility' if acc else ''}): sorting variant Normal / MixtureNormal, "
+                                    "unsharded, no sample covariates, one member, one particle"
+                                    f"{', no accessibility' if grid else ''}")
+
+    def _simulated(self, lead, call) -> Dict[str, torch.Tensor]:
+        """What the simulators end with: ``X`` and, where the fit uses the barcode-matched counts, ``X_bcmatch`` -
+        ``lead + (R, B, G)`` float32 - filled by ``call(x, xbc)`` on the engine's stream, and the resume invalidated."""
+        shape = tuple(lead) + (self.data.n_reps, self.data.n_condits, self.data.n_guides)
+        x = torch.empty(shape, dtype=torch.float32, device=self.device)
+        xbc = torch.empty(shape, dtype=torch.float32, device=self.device) if self.use_bcmatch else None
+        with self._on_stream():
+            call(x, xbc)
+        self.invalidate_resume()
+        out = {"X": x}
+        if xbc is not None:
+            out["X_bcmatch"] = xbc
+        return out
+
     def simulate(self, draw: int, seed: int = 101, alphas: bool = False) -> Dict[str, torch.Tensor]:
         """Replicate counts of one posterior draw (``bean_hip_simulate``): the latent sites of
         ``elbo_grad(step=draw, seed=seed)`` at the current parameters, then ``p ~ Dirichlet(alpha)`` and
@@ -821,24 +857,12 @@ class HipSVI:
         float32, ``X_bcmatch`` where the fit uses the barcode-matched counts, and with ``alphas`` the floored
         concentrations ``alpha`` (2, R, B, G) float64.  Parameters, moments, gradients and the loss history are left as
         they are; the next ``run(resume=True)`` is a plain run."""
-        if not self.predictive_supported:
-            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
-                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
-                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        self._require_predictive("the count simulator does not take")
         R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
-        dev = self.device
-        x = torch.empty((R, B, G), dtype=torch.float32, device=dev)
-        xbc = torch.empty((R, B, G), dtype=torch.float32, device=dev) if self.use_bcmatch else None
-        al = torch.zeros((2, R, B, G), dtype=torch.float64, device=dev) if alphas else None
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
-        with self._on_stream():
-            self._check(self.lib.bean_hip_simulate(self._h, int(seed), int(draw), ptr(x), nb(x), ptr(xbc), nb(xbc),
-                                                   ptr(al), nb(al), self._sptr()), "simulate")
-        self.invalidate_resume()
-        out = {"X": x}
-        if xbc is not None:
-            out["X_bcmatch"] = xbc
+        al = torch.zeros((2, R, B, G), dtype=torch.float64, device=self.device) if alphas else None
+        out = self._simulated((), lambda x, xbc: self._check(self.lib.bean_hip_simulate(
+            self._h, int(seed), int(draw), _ptr(x), _nbytes(x), _ptr(xbc), _nbytes(xbc), _ptr(al), _nbytes(al),
+            self._sptr()), "simulate"))
         if al is not None:
             out["alpha"] = al
         return out
@@ -851,25 +875,11 @@ class HipSVI:
         those of draw ``first_draw + k``: plane 0 is ``simulate(first_draw)``, and with every Normal site injected plane
         k is ``simulate(first_draw + k)``, bit for bit.  Leaves the fit alone as ``simulate`` does; the next
         ``run(resume=True)`` is a plain run."""
-        if not self.predictive_supported:
-            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
-                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
-                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        self._require_predictive("the count simulator does not take")
         K = int(n_draws)
-        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
-        shape = (max(K, 0), R, B, G)
-        x = torch.empty(shape, dtype=torch.float32, device=self.device)
-        xbc = torch.empty(shape, dtype=torch.float32, device=self.device) if self.use_bcmatch else None
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
-        with self._on_stream():
-            self._check(self.lib.bean_hip_simulate_members(self._h, int(seed), int(first_draw), K, ptr(x), nb(x), ptr(xbc),
-                                                           nb(xbc), self._sptr()), "simulate_members")
-        self.invalidate_resume()
-        out = {"X": x}
-        if xbc is not None:
-            out["X_bcmatch"] = xbc
-        return out
+        return self._simulated((max(K, 0),), lambda x, xbc: self._check(self.lib.bean_hip_simulate_members(
+            self._h, int(seed), int(first_draw), K, _ptr(x), _nbytes(x), _ptr(xbc), _nbytes(xbc), self._sptr()),
+            "simulate_members"))
 
     def simulate_design(self, first_draw: int, n_draws: int, depths, seed: int = 101) -> Dict[str, torch.Tensor]:
         """``n_draws`` replicate screens at each of the read depths ``depths`` in one launch
@@ -881,10 +891,7 @@ class HipSVI:
         observed total would reach 2^24 reads (the categorical window, and the limit of exact float32 counts) is a
         ``ValueError`` before any launch.  Leaves the fit alone as ``simulate`` does; the next ``run(resume=True)`` is a
         plain run."""
-        if not self.predictive_supported:
-            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
-                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
-                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        self._require_predictive("the count simulator does not take")
         K = int(n_draws)
         fs = [float(f) for f in depths]
         D = len(fs)
@@ -898,21 +905,10 @@ class HipSVI:
                 raise ValueError(f"simulate_design: depth {max(finite):g} times the largest observed total {most:.0f} is "
                                  f"{max(finite) * most:.0f} reads, not below 2^24 = {1 << 24} (the categorical window of "
                                  "a pair, and the limit of exact float32 counts)")
-        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
-        shape = (D, max(K, 0), R, B, G)
-        x = torch.empty(shape, dtype=torch.float32, device=self.device)
-        xbc = torch.empty(shape, dtype=torch.float32, device=self.device) if self.use_bcmatch else None
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
         arr = (ctypes.c_double * max(D, 1))(*fs)
-        with self._on_stream():
-            self._check(self.lib.bean_hip_simulate_design(self._h, int(seed), int(first_draw), K, arr, D, ptr(x), nb(x),
-                                                          ptr(xbc), nb(xbc), self._sptr()), "simulate_design")
-        self.invalidate_resume()
-        out = {"X": x}
-        if xbc is not None:
-            out["X_bcmatch"] = xbc
-        return out
+        return self._simulated((D, max(K, 0)), lambda x, xbc: self._check(self.lib.bean_hip_simulate_design(
+            self._h, int(seed), int(first_draw), K, arr, D, _ptr(x), _nbytes(x), _ptr(xbc), _nbytes(xbc), self._sptr()),
+            "simulate_design"))
 
     def simulate_power(self, first_draw: int, n_draws: int, effects, plant=None, seed: int = 101) -> Dict[str, torch.Tensor]:
         """``n_draws`` replicate screens at each of the planted effects ``effects`` in one launch
@@ -925,10 +921,7 @@ class HipSVI:
         any other length is a ``ValueError``.  With nothing planted the planes are those of ``simulate_members`` bit for
         bit, and the guides of unplanted targets are in every plane.  Leaves the fit alone as ``simulate`` does; the next
         ``run(resume=True)`` is a plain run."""
-        if not self.predictive_supported:
-            raise PredictiveUnsupported(f"the count simulator does not take this engine ({self.family}"
-                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
-                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        self._require_predictive("the count simulator does not take")
         K = int(n_draws)
         es = [float(e) for e in effects]
         D = len(es)
@@ -939,24 +932,16 @@ class HipSVI:
             if mask.dim() != 1 or int(mask.numel()) != T or mask.dtype not in (torch.bool, torch.uint8):
                 raise ValueError(f"simulate_power: plant must be None or {T} booleans / uint8 (one per target), got "
                                  f"{mask.dtype} of shape {tuple(mask.shape)}")
-        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
-        shape = (D, max(K, 0), R, B, G)
-        x = torch.empty(shape, dtype=torch.float32, device=self.device)
-        xbc = torch.empty(shape, dtype=torch.float32, device=self.device) if self.use_bcmatch else None
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        nb = lambda t: 0 if t is None else t.numel() * t.element_size()
         arr = (ctypes.c_double * max(D, 1))(*es)
-        with self._on_stream():
-            if mask is not None:
-                mask = mask.to(self.device).to(torch.uint8).contiguous()
-            self._plant = mask  # the launch reads it: kept alive until the next call or close()
-            self._check(self.lib.bean_hip_simulate_power(self._h, int(seed), int(first_draw), K, arr, D, ptr(mask), ptr(x),
-                                                         nb(x), ptr(xbc), nb(xbc), self._sptr()), "simulate_power")
-        self.invalidate_resume()
-        out = {"X": x}
-        if xbc is not None:
-            out["X_bcmatch"] = xbc
-        return out
+
+        def call(x, xbc):
+            # the launch reads the mask: kept alive until the next call or close()
+            self._plant = None if mask is None else mask.to(self.device).to(torch.uint8).contiguous()
+            self._check(self.lib.bean_hip_simulate_power(self._h, int(seed), int(first_draw), K, arr, D, _ptr(self._plant),
+                                                         _ptr(x), _nbytes(x), _ptr(xbc), _nbytes(xbc), self._sptr()),
+                        "simulate_power")
+
+        return self._simulated((D, max(K, 0)), call)
 
     LOGW_PAIR_BYTES = 256 << 20  # the pair plane of one bean_hip_log_weights call stays at or below this
 
@@ -983,10 +968,8 @@ class HipSVI:
             if int(integrate_pi) not in _lib.MARGINAL_NODES:
                 raise ValueError(f"log_weights: integrate_pi must be one of {_lib.MARGINAL_NODES} quadrature nodes, got "
                                  f"{integrate_pi!r}")
-        if not self.predictive_supported or getattr(self.lib, "bean_hip_log_weights", None) is None:
-            raise PredictiveUnsupported(f"the importance weights do not take this engine ({self.family}"
-                                        f"{', survival' if self.survival else ''}): sorting variant Normal / "
-                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        self._require_predictive("the importance weights do not take",
+                                 have=getattr(self.lib, "bean_hip_log_weights", None) is not None)
         S = int(n_draws)
         if S < 1:
             raise ValueError(f"log_weights: n_draws must be at least 1, got {S}")
@@ -999,22 +982,19 @@ class HipSVI:
         plane = torch.empty((S if pairs else chunk, R, G), dtype=torch.float64, device=dev)
         # (a draw-independent count: every chunk writes the same values)
         unresolved = None if integrate_pi is None else torch.empty(T, dtype=torch.int32, device=dev)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-        nb = lambda t: t.numel() * t.element_size()
         with self._on_stream():
             for j0 in range(0, S, chunk):
                 n = min(chunk, S - j0)
                 pl = plane[j0:j0 + n] if pairs else plane[:n]
                 lw, m, yy = logw[j0:j0 + n], mu[j0:j0 + n], y[j0:j0 + n]
+                outs = (_ptr(lw), _nbytes(lw), _ptr(m), _nbytes(m), _ptr(yy), _nbytes(yy), _ptr(pl), _nbytes(pl))
                 if integrate_pi is None:
-                    self._check(self.lib.bean_hip_log_weights(self._h, int(seed), int(first_draw) + j0, n, ptr(lw), nb(lw),
-                                                              ptr(m), nb(m), ptr(yy), nb(yy), ptr(pl), nb(pl),
+                    self._check(self.lib.bean_hip_log_weights(self._h, int(seed), int(first_draw) + j0, n, *outs,
                                                               self._sptr()), "log_weights")
                 else:
                     self._check(self.lib.bean_hip_log_weights_marginal(
-                        self._h, int(seed), int(first_draw) + j0, n, int(integrate_pi), ptr(lw), nb(lw), ptr(m), nb(m),
-                        ptr(yy), nb(yy), ptr(pl), nb(pl), ptr(unresolved), nb(unresolved), self._sptr()),
-                        "log_weights_marginal")
+                        self._h, int(seed), int(first_draw) + j0, n, int(integrate_pi), *outs, _ptr(unresolved),
+                        _nbytes(unresolved), self._sptr()), "log_weights_marginal")
         self.invalidate_resume()
         out = {"logw": logw, "mu": mu, "y": y}
         if unresolved is not None:
@@ -1047,12 +1027,7 @@ class HipSVI:
             raise PredictiveUnsupported("this library build has no bean_hip_marginal_grid")
         if tail_rule and getattr(self.lib, "bean_hip_marginal_grid_tail", None) is None:
             raise PredictiveUnsupported("this library build has no bean_hip_marginal_grid_tail")
-        if not self.predictive_supported or self.scale_by_accessibility:
-            raise PredictiveUnsupported(f"the grid posterior does not take this engine ({self.family}"
-                                        f"{', survival' if self.survival else ''}"
-                                        f"{', accessibility' if self.scale_by_accessibility else ''}): sorting variant "
-                                        "Normal / MixtureNormal, unsharded, no sample covariates, one member, one "
-                                        "particle, no accessibility")
+        self._require_predictive("the grid posterior does not take", grid=True)
         if int(nodes) not in _lib.MARGINAL_NODES:
             raise ValueError(f"marginal_grid: nodes must be one of {_lib.MARGINAL_NODES} quadrature nodes, got {nodes!r}")
         n_mu, n_y = int(n_mu), int(n_y)
@@ -1061,8 +1036,6 @@ class HipSVI:
                              f"{n_mu} x {n_y}")
         R, G, T = self.data.n_reps, self.data.n_guides, int(self.T)
         dev = self.device
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-        nb = lambda t: t.numel() * t.element_size()
         # Every tensor a library call reads or writes is formed HERE, on the caller's current stream: _on_stream() makes
         # the engine's stream wait for what is queued on the current stream when the scope is entered, and nothing else
         # orders torch's work before the library's launches.
@@ -1087,14 +1060,13 @@ class HipSVI:
         ys = [] if whole or by_line else [c_y + s_y * (k - (n_y - 1) / 2.0) for k in range(n_y)]
 
         def call(cm, cy, nm, ny, out, pl, te=None):
+            args = (self._h, int(nodes), nm, ny, _ptr(cm), _ptr(cy), _ptr(s_mu), _ptr(s_y), _ptr(out), _nbytes(out),
+                    _ptr(pl), _nbytes(pl), _ptr(unresolved), _nbytes(unresolved))
             if te is None:
-                self._check(self.lib.bean_hip_marginal_grid(self._h, int(nodes), nm, ny, ptr(cm), ptr(cy), ptr(s_mu),
-                                                            ptr(s_y), ptr(out), nb(out), ptr(pl), nb(pl), ptr(unresolved),
-                                                            nb(unresolved), self._sptr()), "marginal_grid")
+                self._check(self.lib.bean_hip_marginal_grid(*args, self._sptr()), "marginal_grid")
             else:
-                self._check(self.lib.bean_hip_marginal_grid_tail(
-                    self._h, int(nodes), nm, ny, ptr(cm), ptr(cy), ptr(s_mu), ptr(s_y), ptr(out), nb(out), ptr(pl), nb(pl),
-                    ptr(unresolved), nb(unresolved), ptr(te), nb(te), self._sptr()), "marginal_grid_tail")
+                self._check(self.lib.bean_hip_marginal_grid_tail(*args, _ptr(te), _nbytes(te), self._sptr()),
+                            "marginal_grid_tail")
 
         with self._on_stream():
             if whole:
@@ -1123,14 +1095,8 @@ class HipSVI:
         the fit is written."""
         if getattr(self.lib, "bean_hip_marginal_tail_nodes", None) is None:
             raise PredictiveUnsupported("this library build has no bean_hip_marginal_tail_nodes")
-        if not self.predictive_supported or self.scale_by_accessibility:
-            raise PredictiveUnsupported(f"the grid posterior does not take this engine ({self.family}"
-                                        f"{', survival' if self.survival else ''}"
-                                        f"{', accessibility' if self.scale_by_accessibility else ''}): sorting variant "
-                                        "Normal / MixtureNormal, unsharded, no sample covariates, one member, one "
-                                        "particle, no accessibility")
+        self._require_predictive("the grid posterior does not take", grid=True)
         dev, G = self.device, self.data.n_guides
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
         count = ctypes.c_int32(0)
         with self._on_stream():
             self._check(self.lib.bean_hip_marginal_tail_nodes(self._h, 0, None, None, None, None, ctypes.byref(count),
@@ -1143,7 +1109,7 @@ class HipSVI:
         lw = torch.zeros((max(n, 1), _lib.TAIL_NODES), dtype=torch.float64, device=dev)
         if n:
             with self._on_stream():
-                self._check(self.lib.bean_hip_marginal_tail_nodes(self._h, n, ptr(pair), ptr(z), ptr(lw), ptr(side),
+                self._check(self.lib.bean_hip_marginal_tail_nodes(self._h, n, _ptr(pair), _ptr(z), _ptr(lw), _ptr(side),
                                                                   ctypes.byref(count), self._sptr()), "marginal_tail_nodes")
         pair = pair[:n].long()
         g = pair % G
