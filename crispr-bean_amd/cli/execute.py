@@ -149,6 +149,15 @@ def get_parser():
                           "the joint ones.")
     own.add_argument("--importance-nodes", dest="importance_nodes", type=int, default=32, metavar="Q",
                      help="Quadrature nodes per integral of --importance-integrate-pi: 16, 32 or 64 (default 32).")
+    own.add_argument("--importance-tail-rule", dest="importance_tail_rule", action="store_true",
+                     help="With --importance-integrate-pi: integrate the (replicate, guide) pairs its quadrature rule does "
+                          "not resolve - an essentially unedited guide is one - by the 64-node Gauss-Jacobi rule of "
+                          "--grid-tail-rule, per draw, and check it against the 48-node rule.  A target with such pairs "
+                          "then gets its marginal columns where the two rules agree within 1e-3 nat per pair over the "
+                          "draws that carry its weight (raw weight at least 1e-6 of the largest), and stays empty "
+                          "otherwise.  Adds the columns n_pairs_tail and is_tail_err behind the marginal columns; "
+                          "n_pairs_unresolved stays what it is.  Works with --scale-by-acc.  Refused without "
+                          "--importance-integrate-pi.")
     own.add_argument("--grid-posterior", dest="grid_posterior", action="store_true",
                      help="After the fit, evaluate every target's posterior of (mu, sd) itself on the GPU - its log joint on "
                           "a grid of (mu, log sd) placed by zoom passes from the fitted values, the editing rates pi "
@@ -226,8 +235,8 @@ def get_parser():
 
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
-    from .run import (grid_nodes, grid_tail_rule, importance_draws, importance_nodes, member_mode, particle_count,
-                      predictive_draws)
+    from .run import (grid_nodes, grid_tail_rule, importance_draws, importance_nodes, importance_tail_rule, member_mode,
+                      particle_count, predictive_draws)
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
@@ -235,6 +244,7 @@ def check_run_switches(parser, args):
     predictive_draws(args, parser.error)
     importance_draws(args, parser.error)
     importance_nodes(args, parser.error)
+    importance_tail_rule(args, parser.error)
     grid_nodes(args, parser.error)
     grid_tail_rule(args, parser.error)
 

@@ -229,6 +229,17 @@ def importance_nodes(args, fail=_refuse):
     return nodes
 
 
+def importance_tail_rule(args, fail=_refuse) -> bool:
+    """``--importance-tail-rule``: the Gauss-Jacobi rule for the pairs the marginal check's quadrature does not resolve.
+    Refused without ``--importance-integrate-pi``; every other refusal is that flag's own (``importance_nodes``)."""
+    if not getattr(args, "importance_tail_rule", False):
+        return False
+    if not getattr(args, "importance_integrate_pi", False):
+        fail("--importance-tail-rule sets the rule --importance-integrate-pi uses for the pairs it does not resolve and "
+             "needs that flag.")
+    return True
+
+
 _GRID_FAMILY = ("--grid-posterior evaluates the posterior of (mu, sd) per target of the sorting variant models (Normal, "
                 "MixtureNormal) and is not available for {what}.")
 _GRID_ACC = ("--grid-posterior is not available with --scale-by-acc: the guide noise is a further latent per guide, so the "
@@ -454,6 +465,7 @@ def main(args, return_data=False):
             raise PredictiveUnsupported(_PREDICTIVE_FAMILY.format(what=why))
     n_importance = importance_draws(args)
     n_nodes = importance_nodes(args)
+    is_tail = importance_tail_rule(args)
     if n_importance:
         from ..engine import PredictiveUnsupported
 
@@ -518,7 +530,8 @@ def main(args, return_data=False):
         info(f"Importance-sampling check: {n_importance} draws from the fitted guide, weighted per target...")
         summary = model_run.run_importance_check(model, guide, ndata, param_history_dict, n_draws=n_importance,
                                                  seed=int(getattr(args, "importance_seed", model_run.SEED)),
-                                                 **({"integrate_pi": n_nodes} if n_nodes else {}))
+                                                 **({"integrate_pi": n_nodes} if n_nodes else {}),
+                                                 **({"tail_rule": True} if is_tail else {}))
         table_columns = {**table_columns, "importance": {k: v.detach().cpu() for k, v in summary.items()}}
         k = table_columns["importance"]["psis_k"]
         info(f"Importance-sampling check: psis_k > 0.7 on {int((k > 0.7).sum())} of {k.numel()} targets "
@@ -531,6 +544,16 @@ def main(args, return_data=False):
             info(f"Importance-sampling check, pi integrated out ({n_nodes} nodes): psis_k_marg > 0.7 on "
                  f"{int((km > 0.7).sum())} of {km.numel()} targets ({share(km > 0.7):.1f} %); {int(left_out.sum())} of "
                  f"{km.numel()} targets ({share(left_out):.1f} %) left out as unresolved.")
+        if is_tail:
+            imp = table_columns["importance"]
+            had = imp["n_pairs_tail"] > 0
+            got = had & ~imp["psis_k_marg"].isnan()
+            barred = had & ~(imp["is_tail_err"] <= 1e-3 * imp["n_pairs_tail"])
+            pct = lambda m, of: 100.0 * float(m.sum()) / max(int(of), 1)  # noqa: E731
+            info(f"Importance-sampling check, tail rule: {int(had.sum())} of {had.numel()} targets "
+                 f"({pct(had, had.numel()):.1f} %) had tail pairs; {int(got.sum())} of those ({pct(got, had.sum()):.1f} %) "
+                 f"now have numbers; {int(barred.sum())} of {had.numel()} targets ({pct(barred, had.numel()):.1f} %) refused "
+                 "by the tail bar (is_tail_err > 1e-3 n_pairs_tail).")
     if n_grid:
         import torch
 

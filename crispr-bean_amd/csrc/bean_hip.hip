@@ -33,6 +33,7 @@
 #include "bean_importance_marg.hpp"  // ... with pi integrated out (bean_hip_log_weights_marginal)
 #include "bean_grid.hpp"  // the same log joint at given (mu, y) per target and node (bean_hip_marginal_grid)
 #include "bean_jacobi.hpp"  // ... with a Gauss-Jacobi rule for the pairs the predicate leaves out (bean_hip_marginal_grid_tail)
+#include "bean_importance_tail.hpp"  // that rule for the marginal importance weights (bean_hip_log_weights_marginal_tail)
 
 using namespace bean;
 
@@ -2914,10 +2915,22 @@ static MargArgs marg_args(int32_t n_nodes, void* unresolved_out) {
     return ma;
 }
 
-static int logw_run(bean_hip_ctx* c, const std::string& name, bool marginal, uint64_t seed, uint64_t first_draw,
-                    int32_t n_draws, int32_t n_nodes, void* logw_out, uint64_t logw_bytes, void* mu_out,
-                    uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out, uint64_t pair_bytes,
-                    void* unresolved_out, uint64_t unresolved_bytes, void* stream_) {
+// ... and with `tail` (bean_hip_log_weights_marginal_tail, bean_importance_tail.hpp) the pairs the predicate leaves out
+// get bean_jacobi.hpp's Gauss-Jacobi rule per draw.  MixtureNormal: the unresolved count comes first, with its scan and
+// - one host synchronisation per call - the number of tail pairs; with tail pairs k_tail_list and k_tail_nodes follow;
+// then k_logw_consts and k_logw_pairs_marg as they are, k_logw_pairs_marg_tail over the tail pairs' slots,
+// k_logw_targets_marg as it is, and k_grid_targets_tail with N = n_draws.  With no tail pair, and for Normal, the
+// launches are those of bean_hip_log_weights_marginal and tail_err_out is zeroed.  (The tail helpers are defined with
+// the grid posterior below.)
+static int tail_reserve(bean_hip_ctx* c, uint64_t bytes);
+static int tail_count(bean_hip_ctx* c, int* unresolved, TailArgs& ta, hipStream_t stream);
+static void tail_nodes_launch(const DevArgs& d, const TailArgs& ta, hipStream_t stream);
+
+static int logw_run(bean_hip_ctx* c, const std::string& name, bool marginal, bool tail, uint64_t seed,
+                    uint64_t first_draw, int32_t n_draws, int32_t n_nodes, void* logw_out, uint64_t logw_bytes,
+                    void* mu_out, uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out, uint64_t pair_bytes,
+                    void* unresolved_out, uint64_t unresolved_bytes, void* tail_err_out, uint64_t tail_err_bytes,
+                    void* stream_) {
     if (postfit_admit(c, name, "the importance weights do not take this handle")) return -1;
     if (n_draws < 1 || n_draws > BEAN_HIP_MAX_LOGW_DRAWS)
         return fail(name + ": n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_LOGW_DRAWS) + "], got " +
@@ -2929,8 +2942,38 @@ static int logw_run(bean_hip_ctx* c, const std::string& name, bool marginal, uin
         return -1;
     if (marginal && buf_exact(name, "unresolved_out", "(T) int32", unresolved_out, unresolved_bytes, 4 * (uint64_t)c->d.T))
         return -1;
+    if (tail && buf_exact(name, "tail_err_out", "(n_draws, T) float64 with n_draws = " + std::to_string(n_draws),
+                          tail_err_out, tail_err_bytes, 8 * (uint64_t)n_draws * c->d.T))
+        return -1;
     hipStream_t stream = (hipStream_t)stream_;
     const bool integrate = marginal && c->d.family == kMixture;
+    TailArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    if (tail && integrate) {
+        if (tail_count(c, (int*)unresolved_out, ta, stream)) return -1;
+        if (ta.n_tail > 0) {
+            const uint64_t n = (uint64_t)ta.n_tail, need = n * (kTailPairBytes + 8 * (uint64_t)n_draws);
+            if (need > kTailMaxBytes)
+                return fail(name + ": " + std::to_string(ta.n_tail) + " tail pairs at n_draws = " +
+                            std::to_string(n_draws) + " need a workspace of " + std::to_string(need) + " bytes (" +
+                            std::to_string(kTailPairBytes) + " + 8 n_draws per pair), above the cap of " +
+                            std::to_string(kTailMaxBytes) + "; send fewer draws per call");
+            if (logw_tail_lds(c->d.R, c->d.B) > 65536)
+                return fail(name + ": " + std::to_string(ta.n_tail) + " tail pairs, and k_logw_pairs_marg_tail needs " +
+                            std::to_string(logw_tail_lds(c->d.R, c->d.B)) + " bytes of LDS at R = " +
+                            std::to_string(c->d.R) + ", B = " + std::to_string(c->d.B) + ", above 65536");
+            if (tail_reserve(c, need)) return -1;
+            ta.N = n_draws;
+            ta.z = (double*)c->tail_ws;
+            ta.lw = ta.z + n * kTailAll;
+            ta.pair_err = ta.lw + n * kTailAll;
+            ta.pair = (int*)(ta.pair_err + n * (uint64_t)n_draws);
+            ta.side = ta.pair + n;
+            ta.tail_err_out = (double*)tail_err_out;
+            HIP_OK(hipMemsetAsync(ta.pair, 0, 2 * n * sizeof(int), stream));  // (an entry never names a pair out of range)
+            tail_nodes_launch(c->d, ta, stream);
+        }
+    }
     // no pi to integrate out: the joint weights are the marginal ones, and no pair is unresolved
     if (marginal && !integrate) HIP_OK(hipMemsetAsync(unresolved_out, 0, unresolved_bytes, stream));
     c->d.seed = seed;
@@ -2949,10 +2992,21 @@ static int logw_run(bean_hip_ctx* c, const std::string& name, bool marginal, uin
     } else {
         const MargArgs ma = marg_args(n_nodes, unresolved_out);
         const size_t lds = logw_marg_lds(d.B);
-        hipLaunchKernelGGL(k_logw_unresolved, logw_blocks(d.T), dim3(kLogwBlock), 0, stream, d, ma);
+        // (with `tail` the count is tail_count's, already in unresolved_out)
+        if (!tail) hipLaunchKernelGGL(k_logw_unresolved, logw_blocks(d.T), dim3(kLogwBlock), 0, stream, d, ma);
         if (d.flags & kAcc) hipLaunchKernelGGL(k_logw_pairs_marg<true>, grid, block, lds, stream, d, la, ma);
         else hipLaunchKernelGGL(k_logw_pairs_marg<false>, grid, block, lds, stream, d, la, ma);
+        if (ta.n_tail > 0) {
+            const dim3 tgrid((unsigned)(((uint64_t)ta.n_tail * n_draws + 63) / 64));
+            const size_t tlds = logw_tail_lds(d.R, d.B);
+            if (d.flags & kAcc) hipLaunchKernelGGL(k_logw_pairs_marg_tail<true>, tgrid, block, tlds, stream, d, la, ta);
+            else hipLaunchKernelGGL(k_logw_pairs_marg_tail<false>, tgrid, block, tlds, stream, d, la, ta);
+        }
         hipLaunchKernelGGL(k_logw_targets_marg, logw_blocks(nt), dim3(kLogwBlock), 0, stream, d, la);
+    }
+    if (tail) {
+        if (ta.n_tail > 0) hipLaunchKernelGGL(k_grid_targets_tail, logw_blocks(nt), dim3(kLogwBlock), 0, stream, d, ta);
+        else HIP_OK(hipMemsetAsync(tail_err_out, 0, tail_err_bytes, stream));
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -2961,8 +3015,8 @@ static int logw_run(bean_hip_ctx* c, const std::string& name, bool marginal, uin
 extern "C" int bean_hip_log_weights(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws, void* logw_out,
                                     uint64_t logw_bytes, void* mu_out, uint64_t mu_bytes, void* y_out, uint64_t y_bytes,
                                     void* pair_out, uint64_t pair_bytes, void* stream_) {
-    return logw_run(c, "bean_hip_log_weights", false, seed, first_draw, n_draws, 0, logw_out, logw_bytes, mu_out, mu_bytes,
-                    y_out, y_bytes, pair_out, pair_bytes, nullptr, 0, stream_);
+    return logw_run(c, "bean_hip_log_weights", false, false, seed, first_draw, n_draws, 0, logw_out, logw_bytes, mu_out,
+                    mu_bytes, y_out, y_bytes, pair_out, pair_bytes, nullptr, 0, nullptr, 0, stream_);
 }
 
 extern "C" int bean_hip_log_weights_marginal(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
@@ -2970,8 +3024,19 @@ extern "C" int bean_hip_log_weights_marginal(bean_hip_ctx* c, uint64_t seed, uin
                                              uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out,
                                              uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
                                              void* stream_) {
-    return logw_run(c, "bean_hip_log_weights_marginal", true, seed, first_draw, n_draws, n_nodes, logw_out, logw_bytes,
-                    mu_out, mu_bytes, y_out, y_bytes, pair_out, pair_bytes, unresolved_out, unresolved_bytes, stream_);
+    return logw_run(c, "bean_hip_log_weights_marginal", true, false, seed, first_draw, n_draws, n_nodes, logw_out,
+                    logw_bytes, mu_out, mu_bytes, y_out, y_bytes, pair_out, pair_bytes, unresolved_out, unresolved_bytes,
+                    nullptr, 0, stream_);
+}
+
+extern "C" int bean_hip_log_weights_marginal_tail(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                                  int32_t n_nodes, void* logw_out, uint64_t logw_bytes, void* mu_out,
+                                                  uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out,
+                                                  uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
+                                                  void* tail_err_out, uint64_t tail_err_bytes, void* stream_) {
+    return logw_run(c, "bean_hip_log_weights_marginal_tail", true, true, seed, first_draw, n_draws, n_nodes, logw_out,
+                    logw_bytes, mu_out, mu_bytes, y_out, y_bytes, pair_out, pair_bytes, unresolved_out, unresolved_bytes,
+                    tail_err_out, tail_err_bytes, stream_);
 }
 
 // ------------------------------------------------------------------ the log joint on a grid of (mu, y) per target

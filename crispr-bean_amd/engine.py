@@ -946,7 +946,7 @@ class HipSVI:
     LOGW_PAIR_BYTES = 256 << 20  # the pair plane of one bean_hip_log_weights call stays at or below this
 
     def log_weights(self, first_draw: int, n_draws: int, seed: int = 101, pairs: bool = False,
-                    integrate_pi: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                    integrate_pi: Optional[int] = None, tail_rule: bool = False) -> Dict[str, torch.Tensor]:
         """Per-target log importance weights of ``n_draws`` draws from the guide at the current parameters
         (``bean_hip_log_weights``): draw ``first_draw + j`` is the draw ``elbo_grad(step=first_draw + j, seed=seed)``
         evaluates (or, with ``set_noise``, the injected draw every time).  Returns float64 device tensors ``logw``
@@ -961,7 +961,20 @@ class HipSVI:
         ``q(pi)``; ``mu`` and ``y`` are the same bits; ``pairs`` then holds the pairs' constants plus the logs of their
         integrals; and ``n_unresolved`` (T, int32) counts, per target, the pairs at which the rule is not valid (the
         weights of such a target are not to be used).  For the ``Normal`` family, which has no ``pi``, ``logw`` is that of
-        the plain call bit for bit."""
+        the plain call bit for bit.
+
+        ``tail_rule=True`` with ``integrate_pi`` (``bean_hip_log_weights_marginal_tail``): the pairs ``n_unresolved``
+        counts get the 64-node Gauss-Jacobi rule of ``marginal_grid(tail_rule=True)`` per draw, and ``tail_err``
+        (n_draws, T) is added: per draw and target the sum over those pairs of the difference to the 48-node rule.
+        Accessibility is admitted.  Same chunking - a chunk's share of the tail workspace, 8 bytes per (draw, tail
+        pair), is at most its pair plane - and the same bits per draw; ``mu``, ``y``, ``n_unresolved``, the slots of
+        every other pair and ``logw`` of the targets without such pairs are those of ``tail_rule=False`` bit for bit.
+        Each library call then synchronises the engine's stream once (the number of such pairs)."""
+        if tail_rule and integrate_pi is None:
+            raise ValueError("log_weights: tail_rule sets the rule integrate_pi uses for the pairs it does not resolve "
+                             "and needs integrate_pi")
+        if tail_rule and getattr(self.lib, "bean_hip_log_weights_marginal_tail", None) is None:
+            raise PredictiveUnsupported("this library build has no bean_hip_log_weights_marginal_tail")
         if integrate_pi is not None:
             if getattr(self.lib, "bean_hip_log_weights_marginal", None) is None:
                 raise PredictiveUnsupported("this library build has no bean_hip_log_weights_marginal")
@@ -982,6 +995,7 @@ class HipSVI:
         plane = torch.empty((S if pairs else chunk, R, G), dtype=torch.float64, device=dev)
         # (a draw-independent count: every chunk writes the same values)
         unresolved = None if integrate_pi is None else torch.empty(T, dtype=torch.int32, device=dev)
+        tail_err = torch.empty((S, T), dtype=torch.float64, device=dev) if tail_rule else None
         with self._on_stream():
             for j0 in range(0, S, chunk):
                 n = min(chunk, S - j0)
@@ -991,14 +1005,21 @@ class HipSVI:
                 if integrate_pi is None:
                     self._check(self.lib.bean_hip_log_weights(self._h, int(seed), int(first_draw) + j0, n, *outs,
                                                               self._sptr()), "log_weights")
-                else:
+                elif not tail_rule:
                     self._check(self.lib.bean_hip_log_weights_marginal(
                         self._h, int(seed), int(first_draw) + j0, n, int(integrate_pi), *outs, _ptr(unresolved),
                         _nbytes(unresolved), self._sptr()), "log_weights_marginal")
+                else:
+                    te = tail_err[j0:j0 + n]
+                    self._check(self.lib.bean_hip_log_weights_marginal_tail(
+                        self._h, int(seed), int(first_draw) + j0, n, int(integrate_pi), *outs, _ptr(unresolved),
+                        _nbytes(unresolved), _ptr(te), _nbytes(te), self._sptr()), "log_weights_marginal_tail")
         self.invalidate_resume()
         out = {"logw": logw, "mu": mu, "y": y}
         if unresolved is not None:
             out["n_unresolved"] = unresolved
+        if tail_rule:
+            out["tail_err"] = tail_err
         if pairs:
             out["pairs"] = self._to_screen_order(plane, 2)
         return out

@@ -14,7 +14,8 @@ torch float64, vectorised over targets, on whatever device the weights live.
   importance-corrected posterior mean and sd of ``mu``.
 * ``marginal_summary``: the same of the weights of ``(mu_t, sd_t)`` alone - ``HipSVI.log_weights(integrate_pi=Q)``, ``pi``
   integrated out of the model by quadrature (``csrc/bean_importance_marg.hpp``) - keys suffixed ``_marg``, NaN for a target
-  with a pair the rule does not resolve.
+  with a pair the rule does not resolve; with ``tail_err`` (``log_weights(..., tail_rule=True)``: a Gauss-Jacobi rule at
+  those pairs, ``csrc/bean_importance_tail.hpp``) such a target is reported where the rule's own check passes.
 
 What ``k`` says (Yao et al. 2018): below 0.5 the guide is a good proposal for this target and the corrected moments can
 be trusted; up to 0.7 they are usable; above it the guide is too light-tailed or misplaced for importance sampling to
@@ -126,28 +127,59 @@ def importance_summary(logw: torch.Tensor, mu: torch.Tensor) -> Dict[str, torch.
 MARGINAL_KEYS = ("psis_k_marg", "mu_is_marg", "mu_sd_is_marg", "is_ess_marg", "n_pairs_unresolved")
 
 
-def marginal_summary(logw_marg: torch.Tensor, mu: torch.Tensor, n_unresolved: torch.Tensor) -> Dict[str, torch.Tensor]:
+TAIL_KEYS = ("n_pairs_tail", "is_tail_err")  # the columns --importance-tail-rule adds behind MARGINAL_KEYS
+TAIL_BOUND = 1e-3       # nat per tail pair: the bound section 21 sets for a pair's log integral
+TAIL_WEIGHT_MIN = 1e-6  # a draw counts for is_tail_err where its raw weight is at least this share of the largest
+
+
+def marginal_summary(logw_marg: torch.Tensor, mu: torch.Tensor, n_unresolved: torch.Tensor, *,
+                     tail_err=None) -> Dict[str, torch.Tensor]:
     """``importance_summary`` of the weights with ``pi`` integrated out (``HipSVI.log_weights(integrate_pi=Q)``), keys
     suffixed ``_marg``, plus ``n_pairs_unresolved``: the (replicate, guide) pairs of the target at which the quadrature
-    rule is not valid.  A target with such a pair has NaN in the four marginal values - its weights are not reported."""
+    rule is not valid.  A target with such a pair has NaN in the four marginal values - its weights are not reported.
+
+    ``tail_err`` (S, T) - ``HipSVI.log_weights(integrate_pi=Q, tail_rule=True)``, whose weights carry the Gauss-Jacobi
+    rule at those pairs - adds ``n_pairs_tail``, the count of the pairs that took the rule (``n_unresolved``), and
+    ``is_tail_err``: the largest ``tail_err[d, t]`` over the draws whose raw ``logw[d, t]`` is within ``log 1e6`` of the
+    target's largest (a draw below that does not enter the sums at that precision either).  A target with such pairs then
+    gets its four values where ``is_tail_err <= 1e-3 n_pairs_tail`` and NaN otherwise; both diagnostics are kept."""
     s = importance_summary(logw_marg, mu)
     n = torch.as_tensor(n_unresolved).to(s["psis_k"].device)
     if n.shape != s["psis_k"].shape:
         raise ValueError(f"marginal_summary: n_unresolved {tuple(n.shape)} is not one count per target "
                          f"{tuple(s['psis_k'].shape)}")
     nan = torch.full_like(s["psis_k"], math.nan)
-    out = {f"{k}_marg": torch.where(n > 0, nan, s[k]) for k in ("psis_k", "mu_is", "mu_sd_is", "is_ess")}
+    left_out = n > 0
+    extra = {}
+    if tail_err is not None:
+        lw = torch.as_tensor(logw_marg).double()
+        te = torch.as_tensor(tail_err).double().to(lw.device)
+        if te.shape != lw.shape:
+            raise ValueError(f"marginal_summary: tail_err has shape {tuple(te.shape)}, logw {tuple(lw.shape)}")
+        counts = (lw - lw.max(0).values) >= math.log(TAIL_WEIGHT_MIN)
+        worst = torch.where(counts, te, torch.zeros_like(te)).max(0).values
+        # (not (worst <= bar): a NaN error refuses)
+        left_out = left_out & ~(worst <= TAIL_BOUND * n.to(worst.dtype))
+        extra = {"n_pairs_tail": n.to(s["psis_k"].dtype), "is_tail_err": worst}
+    out = {f"{k}_marg": torch.where(left_out, nan, s[k]) for k in ("psis_k", "mu_is", "mu_sd_is", "is_ess")}
     out["n_pairs_unresolved"] = n.to(s["psis_k"].dtype)
+    out.update(extra)
     return out
 
 
-def importance_check(engine, n_draws: int = 1000, seed: int = 101, integrate_pi=None) -> Dict[str, torch.Tensor]:
+def importance_check(engine, n_draws: int = 1000, seed: int = 101, integrate_pi=None,
+                     tail_rule: bool = False) -> Dict[str, torch.Tensor]:
     """``importance_summary`` of ``n_draws`` draws (0 .. n_draws - 1) from the guide of ``engine`` at its current
     parameters; device tensors of length T.  ``integrate_pi=Q`` (16, 32 or 64 quadrature nodes): merged with the
-    ``marginal_summary`` of the same draws' weights of ``(mu_t, sd_t)`` alone."""
+    ``marginal_summary`` of the same draws' weights of ``(mu_t, sd_t)`` alone; with ``tail_rule`` those weights take the
+    Gauss-Jacobi rule at the pairs the quadrature does not resolve, and the summary its ``tail_err``."""
+    if tail_rule and integrate_pi is None:
+        raise ValueError("importance_check: tail_rule needs integrate_pi")
     out = engine.log_weights(0, int(n_draws), seed=seed)
     summary = importance_summary(out["logw"], out["mu"])
     if integrate_pi is not None:
-        marg = engine.log_weights(0, int(n_draws), seed=seed, integrate_pi=int(integrate_pi))
-        summary.update(marginal_summary(marg["logw"], marg["mu"], marg["n_unresolved"]))
+        kw = {"tail_rule": True} if tail_rule else {}
+        marg = engine.log_weights(0, int(n_draws), seed=seed, integrate_pi=int(integrate_pi), **kw)
+        summary.update(marginal_summary(marg["logw"], marg["mu"], marg["n_unresolved"],
+                                        **({"tail_err": marg["tail_err"]} if tail_rule else {})))
     return summary

@@ -242,7 +242,9 @@ def write_result_table(
     on the scale of ``mu``, not rescaled), after those of a member set; every other column and the sgRNA table are those
     of the run without it, and with ``None`` every file is byte for byte what it was.  Where the summary also holds the
     marginal check (``marginal_summary``: ``pi`` integrated out), ``psis_k_marg``, ``mu_is_marg``, ``mu_sd_is_marg``,
-    ``is_ess_marg`` (empty for a target with unresolved pairs) and ``n_pairs_unresolved`` follow behind them.
+    ``is_ess_marg`` (empty for a target with unresolved pairs) and ``n_pairs_unresolved`` follow behind them, and where it
+    holds ``is_tail_err`` (the tail rule) ``n_pairs_tail`` and ``is_tail_err`` behind those - ``n_pairs_tail`` once, also
+    where ``grid`` holds it.
 
     ``grid`` (a grid posterior, ``model/grid_posterior.py::grid_posterior``): the element table gets the columns
     ``mu_grid``, ``mu_sd_grid``, ``sd_grid``, ``p_mu_pos_grid``, ``log_evidence_grid``, ``log_bf10_grid`` (on the scale of
@@ -303,6 +305,10 @@ def write_result_table(
             _add_summary_columns(element, importance, "the marginal importance-sampling summary",
                                  ("psis_k_marg", "mu_is_marg", "mu_sd_is_marg", "is_ess_marg"), None,
                                  "n_pairs_unresolved", count_per_target=True)
+        if "is_tail_err" in importance:
+            # ... with the Gauss-Jacobi rule at the unresolved pairs (marginal_summary(tail_err=...)): two more, behind
+            element["n_pairs_tail"] = _flat(importance["n_pairs_tail"]).astype(np.int64)
+            element["is_tail_err"] = _flat(importance["is_tail_err"]).astype(np.float64)
     if grid is not None:
         _add_summary_columns(element, grid, "the grid posterior summary",
                              ("mu_grid", "mu_sd_grid", "sd_grid", "p_mu_pos_grid", "log_evidence_grid", "log_bf10_grid"),
@@ -312,7 +318,8 @@ def write_result_table(
         if "n_pairs_tail" in grid:
             # the Gauss-Jacobi rule for the unresolved pairs: how many pairs of the target took it, and the largest
             # disagreement of its two node counts where the posterior has mass
-            element["n_pairs_tail"] = _flat(grid["n_pairs_tail"]).astype(np.int64)
+            if "n_pairs_tail" not in element.columns:  # (the marginal importance check's tail rule writes the same count)
+                element["n_pairs_tail"] = _flat(grid["n_pairs_tail"]).astype(np.int64)
             element["grid_tail_err"] = _flat(grid["grid_tail_err"]).astype(np.float64)
     if adjust_confidence_by_negative_control:
         assert adjust_confidence_negatives is not None

@@ -463,13 +463,16 @@ def run_posterior_predictive(model, guide, data, param_store, n_draws: int = 200
     return summary
 
 
-def run_importance_check(model, guide, data, param_store, n_draws: int = 1000, seed: int = SEED, integrate_pi=None):
+def run_importance_check(model, guide, data, param_store, n_draws: int = 1000, seed: int = SEED, integrate_pi=None,
+                         tail_rule: bool = False):
     """Importance-sampling check of a fit's mean-field posterior (``model/importance.py``): an engine for ``data`` with
     the fitted parameters of ``param_store`` loaded, ``n_draws`` draws from the guide weighted per target by
     ``p(x, z) / q(z)`` on the device, and their summary - per target ``psis_k``, ``is_ess``, ``mu_is``, ``mu_sd_is``,
     ``n_is`` (a dict of device tensors).  No refit.  ``integrate_pi=Q`` (16, 32 or 64 nodes) merges in the summary of the
     weights of ``(mu_t, sd_t)`` alone, ``pi`` integrated out of the model: ``psis_k_marg``, ``mu_is_marg``,
-    ``mu_sd_is_marg``, ``is_ess_marg`` (NaN where ``n_pairs_unresolved > 0``) and ``n_pairs_unresolved``.
+    ``mu_sd_is_marg``, ``is_ess_marg`` (NaN where ``n_pairs_unresolved > 0``) and ``n_pairs_unresolved``.  ``tail_rule``:
+    the Gauss-Jacobi rule for the unresolved pairs in those weights (``importance_check(tail_rule=True)``), which adds
+    ``n_pairs_tail`` and ``is_tail_err`` and fills the four values where ``is_tail_err <= 1e-3 n_pairs_tail``.
 
     Raises ``PredictiveUnsupported`` - the message names the family - for tiling and survival screens,
     ``ControlNormal``, sample covariates and several ranks."""
@@ -488,7 +491,8 @@ def run_importance_check(model, guide, data, param_store, n_draws: int = 1000, s
     eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
     try:
         load_parameters(eng, param_store)
-        summary = importance_check(eng, n_draws=n_draws, seed=seed, integrate_pi=integrate_pi)
+        summary = importance_check(eng, n_draws=n_draws, seed=seed, integrate_pi=integrate_pi,
+                                   **({"tail_rule": True} if tail_rule else {}))
         torch.cuda.synchronize(device)
     finally:
         eng.close()

@@ -650,6 +650,37 @@ int bean_hip_marginal_grid_tail(bean_hip_ctx* ctx, int32_t n_nodes, int32_t n_mu
 int bean_hip_marginal_tail_nodes(bean_hip_ctx* ctx, int32_t capacity, void* pair_index_out, void* z_out, void* lw_out,
                                  void* side_out, int32_t* n_tail_out, void* stream);
 
+/* bean_hip_log_weights_marginal with that Gauss-Jacobi rule for the pairs its predicate leaves out (DESIGN.md section
+ * 25).  Accessibility is admitted, as for the importance weights: the noise stays a drawn site.
+ *
+ *   bean_hip_log_weights_marginal_tail
+ *                                 bean_hip_log_weights_marginal's arguments, refusals and state contract, plus
+ *                                 tail_err_out, (n_draws, T) float64 on the device.  The tail pairs, their order and
+ *                                 their 64 + 48 nodes are those of bean_hip_marginal_grid_tail; the integrand of draw j
+ *                                 is taken at the drawn (mu_t, y_t) of the pair's target and, with accessibility, at
+ *                                 the guide's drawn noise.  A tail pair's slot of pair_out holds its constant plus
+ *                                 lbeta(a0', a1') + the 64-node log-sum-exp; tail_err_out[j, t] is the sum over the
+ *                                 target's tail pairs of |J64 - J48| at draw j.  mu_out, y_out, unresolved_out, the
+ *                                 slots of resolved pairs and logw_out of targets without tail pairs are bit for bit
+ *                                 those of bean_hip_log_weights_marginal; with no tail pair so is everything, and
+ *                                 tail_err_out is zero (BEAN_FAMILY_NORMAL: always).  Draw first_draw + j has the
+ *                                 same bits whatever n_draws and however the draws are split over calls.
+ *                                 Launches (MixtureNormal): k_logw_unresolved, k_tail_offsets, one host synchronisation
+ *                                 of the stream (the number of tail pairs), with tail pairs k_tail_list and k_tail_nodes,
+ *                                 k_logw_consts, k_logw_pairs_marg, with tail pairs k_logw_pairs_marg_tail (one lane
+ *                                 per (tail pair, draw)), k_logw_targets_marg, with tail pairs k_grid_targets_tail.
+ *                                 Workspace: the handle's, 1 800 + 8 n_draws bytes per tail pair.  A call that would
+ *                                 need more than 256 MiB is refused after the count (only unresolved_out has been
+ *                                 written); the message names the number of tail pairs.
+ *
+ * Errors: those of bean_hip_log_weights_marginal under this function's name; a null tail_err_out or tail_err_bytes
+ * other than 8 n_draws T. */
+int bean_hip_log_weights_marginal_tail(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                       int32_t n_nodes, void* logw_out, uint64_t logw_bytes, void* mu_out,
+                                       uint64_t mu_bytes, void* y_out, uint64_t y_bytes, void* pair_out,
+                                       uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
+                                       void* tail_err_out, uint64_t tail_err_bytes, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
