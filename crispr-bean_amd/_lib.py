@@ -94,7 +94,8 @@ ENSEMBLE_SYMBOLS = ("bean_hip_ensemble_supported", "bean_hip_set_members", "bean
                     "bean_hip_simulate_design", "bean_hip_simulate_power", "bean_hip_log_weights",
                     "bean_hip_log_weights_marginal", "bean_hip_marginal_grid",
                     "bean_hip_marginal_grid_tail", "bean_hip_marginal_tail_nodes",
-                    "bean_hip_log_weights_marginal_tail")
+                    "bean_hip_log_weights_marginal_tail",
+                    "bean_hip_survival_predictive_supported", "bean_hip_simulate_survival")
 MAX_LOGW_DRAWS = 4096  # BEAN_HIP_MAX_LOGW_DRAWS
 MARGINAL_NODES = (16, 32, 64)  # n_nodes of bean_hip_log_weights_marginal
 TAIL_NODES = 64 + 48  # kTailNodes + kTailCheckNodes: the nodes bean_hip_marginal_tail_nodes returns per tail pair
@@ -146,6 +147,9 @@ SYMBOLS = [
       c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
     ("bean_hip_marginal_tail_nodes", c_int32,
      [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_void_p]),
+    ("bean_hip_survival_predictive_supported", c_int32, [c_void_p]),
+    ("bean_hip_simulate_survival", c_int32,
+     [c_void_p, c_uint64, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p]),
     ("bean_hip_sharded_begin", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_void_p]),
     ("bean_hip_sharded_sums", c_int32, [c_void_p, c_void_p]),
     ("bean_hip_sharded_guide", c_int32, [c_void_p, c_void_p]),

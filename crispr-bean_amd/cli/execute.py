@@ -125,7 +125,15 @@ def get_parser():
                           "set (--n-seeds, --jackknife-*) the check is of the fit the tables come from.  Sorting variant "
                           "screens only; the --fit-negctrl control fit is not checked.  Default 0: off.")
     own.add_argument("--predictive-seed", dest="predictive_seed", type=int, default=101,
-                     help="Seed of the draws of --posterior-predictive (default 101).")
+                     help="Seed of the draws of --posterior-predictive and --survival-predictive (default 101).")
+    own.add_argument("--survival-predictive", dest="survival_predictive", type=_non_negative_int, default=0, metavar="S",
+                     help="The posterior predictive check of a survival variant screen: after the fit, draw S replicate "
+                          "screens over the timepoints from the fitted guide and the likelihood on the GPU and compare them "
+                          "with the observed counts.  Writes the tables of --posterior-predictive, "
+                          "bean_predictive_guides.<model>.csv and bean_predictive_samples.<model>.csv, with the guide's "
+                          "score read as its read-weighted mean time: ppc_z_score > 0 is a guide that grows faster than "
+                          "the fitted model says.  The other tables do not change.  Survival variant screens (Normal, "
+                          "MixtureNormal) only; the --fit-negctrl control fit is not checked.  Default 0: off.")
     own.add_argument("--importance-check", dest="importance_check", type=_non_negative_int, default=0, metavar="S",
                      help="After the fit, draw S times from the fitted mean-field guide on the GPU, weight every draw per "
                           "target by p(x, z) / q(z) and report, per target, the Pareto tail index of the weights and the "
@@ -236,12 +244,13 @@ def get_parser():
 def check_run_switches(parser, args):
     """Combinations of this project's own `bean run` switches that are refused (exit status 2, one sentence)."""
     from .run import (grid_nodes, grid_tail_rule, importance_draws, importance_nodes, importance_tail_rule, member_mode,
-                      particle_count, predictive_draws)
+                      particle_count, predictive_draws, survival_predictive_draws)
 
     member_mode(args, parser.error,
                 parser_rules={"jackknife_guides": (("guides_max", "--jackknife-guides-max is at most 63."),)})
     particle_count(args, parser.error)
     predictive_draws(args, parser.error)
+    survival_predictive_draws(args, parser.error)
     importance_draws(args, parser.error)
     importance_nodes(args, parser.error)
     importance_tail_rule(args, parser.error)

@@ -189,6 +189,26 @@ def predictive_draws(args, fail=_refuse) -> int:
     return n
 
 
+_SURVIVAL_PREDICTIVE_FAMILY = ("--survival-predictive simulates the counts of the survival variant models (Normal, "
+                               "MixtureNormal) and is not available for {what}.")
+
+
+def survival_predictive_draws(args, fail=_refuse) -> int:
+    """``--survival-predictive S``: the number of replicate screens of a survival fit to draw after it (0: none).  A
+    family the survival count simulator does not take is refused - ``fail(sentence)``, as ``member_mode`` - with the
+    family named."""
+    n = int(getattr(args, "survival_predictive", 0) or 0)
+    if n < 0:
+        fail(f"--survival-predictive must be >= 0, got {n}.")
+    if n == 0:
+        return 0
+    if getattr(args, "library_design", None) == "tiling":
+        fail(_SURVIVAL_PREDICTIVE_FAMILY.format(what="tiling screens (MultiMixtureNormal)"))
+    if getattr(args, "selection", None) != "survival":
+        fail(_SURVIVAL_PREDICTIVE_FAMILY.format(what="sorting screens (--posterior-predictive serves them)"))
+    return n
+
+
 _IMPORTANCE_FAMILY = ("--importance-check weights draws of the sorting variant models (Normal, MixtureNormal) per target and "
                       "is not available for {what}.")
 IMPORTANCE_MIN_DRAWS = 25  # model/importance.py::MIN_DRAWS: fewer draws have no tail to fit
@@ -463,6 +483,13 @@ def main(args, return_data=False):
         why = model_run._predictive_refusal(model_run._resolve(model), ndata, world)
         if why is not None:
             raise PredictiveUnsupported(_PREDICTIVE_FAMILY.format(what=why))
+    n_survival_predictive = survival_predictive_draws(args)
+    if n_survival_predictive:
+        from ..engine import PredictiveUnsupported
+
+        why = model_run._survival_predictive_refusal(model_run._resolve(model), ndata, world)
+        if why is not None:
+            raise PredictiveUnsupported(_SURVIVAL_PREDICTIVE_FAMILY.format(what=why))
     n_importance = importance_draws(args)
     n_nodes = importance_nodes(args)
     is_tail = importance_tail_rule(args)
@@ -600,6 +627,15 @@ def main(args, return_data=False):
         info(f"Posterior predictive check: {n_predictive} replicate screens...")
         summary = model_run.run_posterior_predictive(model, guide, ndata, param_history_dict, n_draws=n_predictive,
                                                      seed=int(getattr(args, "predictive_seed", model_run.SEED)))
+        paths = write_predictive_tables(summary, guide_info_df, ndata, f"{prefix}/", model_label, args.result_suffix)
+        info(f"Wrote {paths[0]} and {paths[1]}.")
+    if n_survival_predictive:
+        from ..model.predictive import write_predictive_tables
+
+        info(f"Survival predictive check: {n_survival_predictive} replicate screens...")
+        summary = model_run.run_survival_predictive(model, guide, ndata, param_history_dict,
+                                                    n_draws=n_survival_predictive,
+                                                    seed=int(getattr(args, "predictive_seed", model_run.SEED)))
         paths = write_predictive_tables(summary, guide_info_df, ndata, f"{prefix}/", model_label, args.result_suffix)
         info(f"Wrote {paths[0]} and {paths[1]}.")
     info("Done!")

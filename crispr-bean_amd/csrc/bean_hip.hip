@@ -34,6 +34,7 @@
 #include "bean_grid.hpp"  // the same log joint at given (mu, y) per target and node (bean_hip_marginal_grid)
 #include "bean_jacobi.hpp"  // ... with a Gauss-Jacobi rule for the pairs the predicate leaves out (bean_hip_marginal_grid_tail)
 #include "bean_importance_tail.hpp"  // that rule for the marginal importance weights (bean_hip_log_weights_marginal_tail)
+#include "bean_survival_predictive.hpp"  // replicate counts of a survival screen (bean_hip_simulate_survival)
 
 using namespace bean;
 
@@ -3224,6 +3225,63 @@ extern "C" int bean_hip_marginal_tail_nodes(bean_hip_ctx* c, int32_t capacity, v
     ta.lw = (double*)lw_out;
     HIP_OK(hipMemsetAsync(ta.pair, 0, (size_t)ta.n_tail * sizeof(int), stream));
     tail_nodes_launch(d, ta, stream);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ survival screens: posterior predictive replicate counts
+// (bean_survival_predictive.hpp; at the end of the file, so that every other kernel keeps its place in the code object)
+static bool survival_predictive_shape_ok(const bean_hip_ctx* c) {
+    const bean_hip_shape& s = c->shape;
+    return is_survival(s) && !is_tiling(s) && s.n_sample_covariates == 0 &&
+           (s.family == BEAN_FAMILY_NORMAL || s.family == BEAN_FAMILY_MIXTURE_NORMAL) && s.guide_offset == 0 &&
+           s.target_offset == 0 && (s.n_guides_total == 0 || s.n_guides_total == s.n_guides) &&
+           !(s.flags & BEAN_FLAG_NOT_LOSS_OWNER) && c->n_members == 1 && c->n_particles == 1;
+}
+
+extern "C" int bean_hip_survival_predictive_supported(const bean_hip_ctx* c) {
+    if (!c) return fail("bean_hip_survival_predictive_supported: null handle");
+    return survival_predictive_shape_ok(c) ? 1 : 0;
+}
+
+// One replicate screen of a survival fit (k_simulate_survival): the signature and buffer rules of bean_hip_simulate,
+// the launch sequence of simulate_run - the seed, draw `draw` as bean_hip_elbo_grad(seed, step = draw) prepares it (no
+// loss slot is cleared: n = 0), then one launch over the (tile, replicate) waves of k_guide_survival_wave's grid.
+extern "C" int bean_hip_simulate_survival(bean_hip_ctx* c, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
+                                          void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes,
+                                          void* stream_) {
+    const std::string name = "bean_hip_simulate_survival";
+    if (!c) return fail(name + ": null handle");
+    if (!survival_predictive_shape_ok(c))
+        return fail(name + ": the survival count simulator does not take this handle "
+                    "(bean_hip_survival_predictive_supported): survival variant Normal / MixtureNormal, unsharded, no "
+                    "sample covariates, one member, one particle");
+    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
+    if (check_bound(c, false, false)) return -1;
+    if (sim_buffers(c, name, "(R, B, G) float32", 1, x_out, x_bytes, xbc_out, xbc_bytes)) return -1;
+    if (buf_optional(name, "alpha_out", "(2, R, B, G) float64", alpha_out, alpha_bytes,
+                     16 * (uint64_t)c->d.R * c->d.B * c->d.G))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t lds = simulate_survival_lds(c->d.B);
+    if (lds > 65536) {  // beyond 35 timepoints: three columns of doubles and one of floats per lane
+        const void* fn = with_family_acc(c->d, [](auto fam, auto acc) { return (const void*)k_simulate_survival<fam(), acc()>; });
+        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    c->d.seed = seed;
+    c->resume_ok = false;  // the workspace now holds this draw and its tables
+    launch_set_step(c, stream, draw, 0, 0);
+    launch_param<false, false, true>(c, stream);
+    const DevArgs& d = c->d;
+    SimArgs sa;
+    sa.x_out = (float*)x_out;
+    sa.xbc_out = (float*)xbc_out;
+    sa.alpha_out = (double*)alpha_out;
+    const int tiles = (d.G + 63) / 64;
+    const dim3 grid((unsigned)((tiles + 7) / 8 * 8) * (unsigned)d.R);
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_simulate_survival<fam(), acc()>), grid, dim3(64), lds, stream, d, sa);
+    });
     HIP_OK(hipGetLastError());
     return 0;
 }

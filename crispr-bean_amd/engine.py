@@ -867,6 +867,34 @@ class HipSVI:
             out["alpha"] = al
         return out
 
+    @property
+    def survival_predictive_supported(self) -> bool:
+        """Whether the survival count simulator takes this engine (``bean_hip_survival_predictive_supported``): the
+        survival variant Normal / MixtureNormal families, unsharded, no sample covariates, one member, one particle."""
+        fn = getattr(self.lib, "bean_hip_survival_predictive_supported", None)
+        return fn is not None and fn(self._h) == 1
+
+    def simulate_survival(self, draw: int, seed: int = 101, alphas: bool = False) -> Dict[str, torch.Tensor]:
+        """Replicate counts of one posterior draw of a survival screen (``bean_hip_simulate_survival``): the latent
+        sites of ``elbo_grad(step=draw, seed=seed)`` at the current parameters - injected noise honoured, and
+        ``drawn_noise()`` afterwards that of this draw - then ``p ~ Dirichlet(alpha)`` over the timepoints and
+        ``x_rep ~ Multinomial(n_obs, p)`` for every (replicate, guide).  Returns what ``simulate`` returns: ``X``
+        (R, B, G) float32, ``X_bcmatch`` where the fit uses the barcode-matched counts, and with ``alphas`` the floored
+        concentrations ``alpha`` (2, R, B, G) float64.  Parameters, moments, gradients and the loss history are left as
+        they are; the next ``run(resume=True)`` is a plain run."""
+        if not self.survival_predictive_supported:
+            raise PredictiveUnsupported(f"the survival count simulator does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ', sorting'}): survival variant Normal / "
+                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        R, B, G = self.data.n_reps, self.data.n_condits, self.data.n_guides
+        al = torch.zeros((2, R, B, G), dtype=torch.float64, device=self.device) if alphas else None
+        out = self._simulated((), lambda x, xbc: self._check(self.lib.bean_hip_simulate_survival(
+            self._h, int(seed), int(draw), _ptr(x), _nbytes(x), _ptr(xbc), _nbytes(xbc), _ptr(al), _nbytes(al),
+            self._sptr()), "simulate_survival"))
+        if al is not None:
+            out["alpha"] = al
+        return out
+
     def simulate_members(self, first_draw: int, n_draws: int, seed: int = 101) -> Dict[str, torch.Tensor]:
         """``n_draws`` replicate screens in one launch (``bean_hip_simulate_members``): ``X`` (K, R, B, G) float32 and,
         where the fit uses the barcode-matched counts, ``X_bcmatch`` - device tensors, member-major, what

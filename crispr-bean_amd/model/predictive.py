@@ -19,6 +19,14 @@ Definitions, with S draws.  A pair (r, g) is *unmasked* where ``repguide_mask`` 
 * sample (r, b): ``frac_cells_p05`` = share of the unmasked guides whose cell p is <= 0.05, ``mean_z`` = mean cell z over
   them (cells without a z left out).
 * with barcode-matched counts the same quantities of X_bcmatch carry the suffix ``_bcmatch``.
+
+Survival screens (``survival_predictive``, ``HipSVI.simulate_survival``, ``csrc/bean_survival_predictive.hpp``): the
+conditions are the timepoints, and ``mid_b`` is the engine's normalised time ``t_b``.  The pair score is then the
+read-weighted mean time ``T_rg = sum_b t_b x_b / n`` - larger for a guide that grows over the screen, smaller for one that
+drops out - so ``ppc_z_score > 0`` reads "grows faster than the fitted model says" and ``ppc_p_score`` is the two-sided
+p-value of that.  ``V_g`` / ``ppc_p_spread`` compare the replicates' mean times, and the cell and sample quantities are the
+same per (replicate, timepoint, guide) and per (replicate, timepoint).  Every definition and column name above holds
+unchanged.
 """
 from __future__ import annotations
 
@@ -161,6 +169,27 @@ def posterior_predictive(engine, n_draws: int = 200, seed: int = 101) -> Dict[st
     masks = {"repguide": data.repguide_mask, "sample": data.sample_mask, "mask_thres": int(engine._shape.mask_thres)}
     mid = bin_midpoints(data.upper_bounds, data.lower_bounds)
     return predictive_summary(observed, (engine.simulate(d, seed=seed) for d in range(n_draws)), masks, mid)
+
+
+def survival_predictive(engine, n_draws: int = 200, seed: int = 101) -> Dict[str, torch.Tensor]:
+    """Drive ``engine.simulate_survival`` for draws 0 ... ``n_draws`` - 1 at the engine's current parameters and return
+    ``predictive_summary`` with ``bin_mid`` the engine's normalised timepoints (the survival reading in this module's
+    docstring).  Raises ``PredictiveUnsupported`` where the survival count simulator does not take the engine."""
+    from ..engine import PredictiveUnsupported
+
+    n_draws = int(n_draws)
+    if n_draws < 1:
+        raise ValueError(f"n_draws must be >= 1, got {n_draws}")
+    if not engine.survival_predictive_supported:
+        raise PredictiveUnsupported(f"a survival predictive check is not available for this engine ({engine.family}"
+                                    f"{', survival' if engine.survival else ', sorting'})")
+    data = engine.data
+    observed = {"X": engine._keep["X"]}
+    if engine.use_bcmatch:
+        observed["X_bcmatch"] = engine._keep["X_BC"]
+    masks = {"repguide": data.repguide_mask, "sample": data.sample_mask, "mask_thres": int(engine._shape.mask_thres)}
+    mid = torch.as_tensor(engine._keep["TIMEPOINTS"]).double().reshape(-1)
+    return predictive_summary(observed, (engine.simulate_survival(d, seed=seed) for d in range(n_draws)), masks, mid)
 
 
 def write_predictive_tables(summary: Dict[str, torch.Tensor], guide_info_df, data, prefix: str, model_label: str,

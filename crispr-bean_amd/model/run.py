@@ -463,6 +463,53 @@ def run_posterior_predictive(model, guide, data, param_store, n_draws: int = 200
     return summary
 
 
+def _survival_predictive_refusal(spec, data, world: int = 1):
+    """Why the survival count simulator does not take this model / screen, or None
+    (``bean_hip_survival_predictive_supported``)."""
+    design = getattr(data, "library_design", "variant")
+    if spec.family == "MultiMixtureNormal" or design == "tiling":
+        return "tiling screens (MultiMixtureNormal)"
+    if not (spec.selection == "survival" or getattr(data, "selection", "sorting") == "survival"):
+        return f"sorting screens ({spec.family})"
+    if spec.family == "ControlNormal":
+        return "the negative-control model (ControlNormal)"
+    if getattr(data, "sample_covariates", None) is not None:
+        return f"screens with sample covariates ({spec.family})"
+    if world > 1:
+        return f"guide-sharded fits over {world} ranks ({spec.family})"
+    return None
+
+
+def run_survival_predictive(model, guide, data, param_store, n_draws: int = 200, seed: int = SEED):
+    """Posterior predictive check of a survival fit (``model/predictive.py::survival_predictive``): an engine for
+    ``data`` built as ``run_posterior_predictive`` builds it - the same model / guide partials, so the ``mu_negctrl`` of
+    the control fit is the fit's - with the fitted parameters of ``param_store`` loaded, ``n_draws`` replicate screens
+    drawn on the device, and the summary against the observed counts (a dict of device tensors).
+
+    Raises ``PredictiveUnsupported`` - the message names the family - for sorting screens, tiling, ``ControlNormal``
+    and several ranks."""
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+    from .predictive import survival_predictive
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _survival_predictive_refusal(spec, data, world)
+    if why is not None:
+        raise PredictiveUnsupported(f"a survival predictive check is not available for {why}: the survival count "
+                                    "simulator serves the survival variant Normal and MixtureNormal models on one GPU")
+    device = torch.device("cuda", torch.cuda.current_device())
+    eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
+    try:
+        load_parameters(eng, param_store)
+        summary = survival_predictive(eng, n_draws=n_draws, seed=seed)
+        torch.cuda.synchronize(device)
+    finally:
+        eng.close()
+    return summary
+
+
 def run_importance_check(model, guide, data, param_store, n_draws: int = 1000, seed: int = SEED, integrate_pi=None,
                          tail_rule: bool = False):
     """Importance-sampling check of a fit's mean-field posterior (``model/importance.py``): an engine for ``data`` with

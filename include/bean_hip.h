@@ -681,6 +681,35 @@ int bean_hip_log_weights_marginal_tail(bean_hip_ctx* ctx, uint64_t seed, uint64_
                                        uint64_t pair_bytes, void* unresolved_out, uint64_t unresolved_bytes,
                                        void* tail_err_out, uint64_t tail_err_bytes, void* stream);
 
+/* Posterior predictive check of a SURVIVAL screen: replicate counts over the timepoints, drawn on the device from the
+ * handle's current parameters (k_simulate_survival).
+ *
+ *   bean_hip_survival_predictive_supported
+ *                                 1 if the survival count simulator takes this handle, 0 if not: survival selection,
+ *                                 family Normal or MixtureNormal (with or without accessibility scaling / X_bcmatch),
+ *                                 unsharded, no sample covariates, the loss owner, n_members == 1 and n_particles == 1.
+ *                                 Not: sorting screens (bean_hip_simulate serves them), tiling, ControlNormal.
+ *   bean_hip_simulate_survival    the signature, buffer rules and state contract of bean_hip_simulate.  Draws the latent
+ *                                 sites of "draw `draw`" - bit for bit the draws of bean_hip_elbo_grad(seed, step =
+ *                                 draw): the Normal sites, the baseline u_g, pi, the Dirichlet-over-all-guides site;
+ *                                 injected noise (*_IN slots) is honoured the same way, and the *_OUT slots that are bound
+ *                                 hold the draw afterwards - forms the Dirichlet-Multinomial concentrations of every
+ *                                 (replicate, guide) over the timepoints as k_guide_survival_wave does, and draws
+ *                                 p ~ Dirichlet(alpha), x_rep ~ Multinomial(n_obs, p) from the sites and counters
+ *                                 bean_hip_simulate uses.  Masked pairs are simulated like any other.  x_out, xbc_out:
+ *                                 (R, B, G) float32; alpha_out: null (0 bytes) or (2, R, B, G) float64.  The same (seed,
+ *                                 draw) gives the same bits.  The call writes no parameter, moment, gradient, loss_hist
+ *                                 entry or loss accumulator; a following bean_hip_svi_resume does not continue an earlier
+ *                                 window.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched): a null handle; a handle that is not
+ * supported (the message names bean_hip_survival_predictive_supported and what it takes) or not prepared; byte counts
+ * other than 4 R B G (x_out, xbc_out) and 16 R B G (alpha_out); xbc_out on a handle without BEAN_FLAG_USE_BCMATCH or
+ * without it on a handle with the flag.  The handle stays usable. */
+int bean_hip_survival_predictive_supported(const bean_hip_ctx* ctx);
+int bean_hip_simulate_survival(bean_hip_ctx* ctx, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
+                               void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
