@@ -197,7 +197,18 @@ def get_parser():
                           "hold mu_sd against.  K >= 2; sorting variant screens only; not combined with --n-seeds > 1, any "
                           "--jackknife-* flag, --num-particles > 1 or --load-existing.  Default 0: off.")
     own.add_argument("--bootstrap-seed", dest="bootstrap_seed", type=int, default=101,
-                     help="Seed of the simulated screens of --bootstrap (default 101).")
+                     help="Seed of the simulated screens of --bootstrap and --survival-bootstrap (default 101).")
+    own.add_argument("--survival-bootstrap", dest="survival_bootstrap", type=_non_negative_int, default=0, metavar="K",
+                     help="Parametric bootstrap of a survival variant screen: after the fit of the screen, draw K screens "
+                          "over the timepoints from the fitted model in one launch on the GPU (mu and the guide noise "
+                          "at their fitted locations, the Normal model's initial abundance at the mean of its Dirichlet; "
+                          "per screen a fresh baseline of the MixtureNormal model, fresh pi, Dirichlet and count draws; "
+                          "masks, size factors, a0, pi_a0, the observed initial counts, the control fit's mu_negctrl and "
+                          "every guide's total as observed), refit each with the same seed, one after the other, and "
+                          "report the columns of --bootstrap: mu_boot_se / mu_boot_bias / n_boot.  K >= 2; survival "
+                          "variant screens only (--bootstrap serves sorting screens); not combined with --bootstrap, "
+                          "--design-depths, --power-effects, --n-seeds > 1, any --jackknife-* flag, --num-particles > 1 "
+                          "or --load-existing; combines with --survival-predictive.  Default 0: off.")
     own.add_argument("--design-depths", dest="design_depths", type=parse_depths, default=None, metavar="F,F,...",
                      help="Depth study: after the fit of the screen, draw --design-screens screens from the fitted model "
                           "on the GPU at each of these read depths - a comma-separated list of factors > 0 such as "

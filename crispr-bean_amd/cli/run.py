@@ -68,6 +68,8 @@ _SAMPLE_RULES = (("jackknife_replicates", _TWO_RUNS), ("jackknife_guides", _TWO_
                  ("power_effects", _TWO_RUNS))
 _BOOTSTRAP_FAMILY = ("{{flag}} simulates the counts of the sorting variant models (Normal, MixtureNormal) and is not "
                      "available for {}.")
+_SURVIVAL_BOOTSTRAP_FAMILY = ("{{flag}} simulates the counts of the survival variant models (Normal, MixtureNormal) and "
+                              "is not available for {}.")
 # the flags that ask for a member set, in the order their refusals are reported:
 # (attribute, mode, ((what it does not combine with, sentence), ...))
 MEMBER_FLAGS = (
@@ -109,12 +111,23 @@ MEMBER_FLAGS = (
                                 ("load_existing", "{flag} needs the refits of its simulated screens and does not combine "
                                                   "with --load-existing."),
                                 ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS))),
+    ("survival_bootstrap", "survival_bootstrap",
+     (("survival_bootstrap_one", "{flag} needs at least 2 screens."),
+      ("tiling", _SURVIVAL_BOOTSTRAP_FAMILY.format("tiling screens (MultiMixtureNormal)")),
+      ("sorting", _SURVIVAL_BOOTSTRAP_FAMILY.format("sorting screens (--bootstrap serves them)")),
+      ("n_seeds", _SAME_SEED), ("jackknife_replicates", _TWO_RUNS), ("jackknife_guides", _TWO_RUNS),
+      ("jackknife_samples", _TWO_RUNS), ("jackknife_conditions", _TWO_RUNS),
+      ("load_existing", "{flag} needs the refits of its simulated screens and does not combine with --load-existing."),
+      ("bootstrap", _TWO_RUNS), ("design_depths", _TWO_RUNS), ("power_effects", _TWO_RUNS))),
 )
 _IS_SET = {"n_seeds": lambda args: int(getattr(args, "n_seeds", 1) or 1) > 1,
            "bootstrap": lambda args: int(getattr(args, "bootstrap", 0) or 0) > 0,
            "bootstrap_one": lambda args: int(getattr(args, "bootstrap", 0) or 0) == 1,
            "design_one": lambda args: int(getattr(args, "design_screens", 8) or 0) < 2,
            "power_one": lambda args: int(getattr(args, "power_screens", 8) or 0) < 2,
+           "survival_bootstrap": lambda args: int(getattr(args, "survival_bootstrap", 0) or 0) > 0,
+           "survival_bootstrap_one": lambda args: int(getattr(args, "survival_bootstrap", 0) or 0) == 1,
+           "sorting": lambda args: getattr(args, "selection", None) == "sorting",
            "survival": lambda args: getattr(args, "selection", None) == "survival",
            "tiling": lambda args: getattr(args, "library_design", None) == "tiling",
            "guides_max": lambda args: int(getattr(args, "jackknife_guides_max", 63)) > 63}
@@ -327,7 +340,7 @@ def _entries(heads, fits):
     return [{**head, "params": out["params"], "loss": out["loss"]} for head, (_, out) in zip(heads, fits)]
 
 
-def _seed_members(fit, ndata, args, guide_names):
+def _seed_members(fit, ndata, args, guide_names, n_rows):
     from ..model.ensemble import combine_ensemble
 
     members = fit(model_run.run_inference_ensemble, seeds=[model_run.SEED + k for k in range(int(args.n_seeds))])
@@ -336,21 +349,21 @@ def _seed_members(fit, ndata, args, guide_names):
     return combined, _entries([{}] * len(members), members), {"seed_sd": spread["mu_seed_sd"], "n_seeds": len(members)}
 
 
-def _replicate_members(fit, ndata, args, guide_names):
+def _replicate_members(fit, ndata, args, guide_names, n_rows):
     full, loo, left_out = fit(model_run.run_inference_jackknife)
     names = _replicate_names(ndata)
     return (full, _entries([{"left_out": names[r]} for r in left_out], loo),
             {"jackknife": jk.jackknife_summary(full, loo, left_out, names)})
 
 
-def _guide_members(fit, ndata, args, guide_names):
+def _guide_members(fit, ndata, args, guide_names, n_rows):
     full, loo, positions, included = fit(model_run.run_inference_guide_jackknife,
                                          max_positions=int(getattr(args, "jackknife_guides_max", 63)))
     return (full, {"included": included, "positions": _entries([{"position": j} for j in positions], loo)},
             {"guide_jackknife": jk.guide_jackknife_summary(full, loo, positions, included, ndata, guide_names)})
 
 
-def _sample_members(fit, ndata, args, guide_names):
+def _sample_members(fit, ndata, args, guide_names, n_rows):
     by = member_mode(args)
     full, loo, groups, fallback = fit(model_run.run_inference_sample_jackknife, by=by)
     names = _sample_group_names(ndata, groups, fallback, by, args.condition_col)
@@ -358,14 +371,34 @@ def _sample_members(fit, ndata, args, guide_names):
             {"sample_jackknife": jk.sample_jackknife_summary(full, loo, groups, names)})
 
 
-def _bootstrap_members(fit, ndata, args, guide_names):
+def _bootstrap_members(fit, ndata, args, guide_names, n_rows):
     full, boots = fit(model_run.run_inference_bootstrap, n_boot=int(args.bootstrap),
                       boot_seed=int(getattr(args, "bootstrap_seed", model_run.SEED)))
     return (full, _entries([{"screen": j} for j in range(len(boots))], boots),
             {"bootstrap": jk.bootstrap_summary(full, boots)})
 
 
-def _design_members(fit, ndata, args, guide_names):
+def _survival_bootstrap_members(fit, ndata, args, guide_names, n_rows):
+    full, boots = fit(model_run.run_survival_bootstrap, n_boot=int(args.survival_bootstrap),
+                      boot_seed=int(getattr(args, "bootstrap_seed", model_run.SEED)))
+    return (full, _entries([{"screen": j} for j in range(len(boots))], boots),
+            {"bootstrap": _rows_of(jk.bootstrap_summary(full, boots), n_rows)})
+
+
+def _rows_of(summary, n_rows):
+    """A per-target summary for a target table of ``n_rows`` rows.  The table of a screen that lists a target under two
+    groups has more rows than the fit has targets; ``write_result_table`` leaves the fitted columns (``mu`` ...) of the
+    surplus rows empty, and so are the summary's per-target entries.  ``n_boot`` is the run's number of screens, one
+    number for the whole table."""
+    out = dict(summary)
+    for k, v in summary.items():
+        if k != "n_boot":
+            v = np.asarray(v.detach().cpu() if hasattr(v, "detach") else v, dtype=np.float64).reshape(-1)
+            out[k] = np.concatenate([v, np.full(max(n_rows - len(v), 0), np.nan)])
+    return out
+
+
+def _design_members(fit, ndata, args, guide_names, n_rows):
     depths = model_run.design_depths(args.design_depths)
     full, fits = fit(model_run.run_inference_design, depths=depths, n_screens=int(getattr(args, "design_screens", 8)),
                      design_seed=int(getattr(args, "design_seed", model_run.SEED)))
@@ -374,7 +407,7 @@ def _design_members(fit, ndata, args, guide_names):
             {"design": jk.design_summary(full, fits, depths, data=ndata)})
 
 
-def _power_members(fit, ndata, args, guide_names):
+def _power_members(fit, ndata, args, guide_names, n_rows):
     effects = model_run.power_effects(args.power_effects)
     full, fits = fit(model_run.run_inference_power, effects=effects, n_screens=int(getattr(args, "power_screens", 8)),
                      power_seed=int(getattr(args, "power_seed", model_run.SEED)))
@@ -388,7 +421,8 @@ def _power_members(fit, ndata, args, guide_names):
 MEMBER_RUNS = {"seeds": (_seed_members, "ensemble"), "replicates": (_replicate_members, "jackknife"),
                "guides": (_guide_members, "guide_jackknife"), "sample": (_sample_members, "sample_jackknife"),
                "condition": (_sample_members, "sample_jackknife"), "bootstrap": (_bootstrap_members, "bootstrap"),
-               "design": (_design_members, "design"), "power": (_power_members, "power")}
+               "design": (_design_members, "design"), "power": (_power_members, "power"),
+               "survival_bootstrap": (_survival_bootstrap_members, "bootstrap")}
 
 
 def main(args, return_data=False):
@@ -537,7 +571,7 @@ def main(args, return_data=False):
             # a member set: member 0 is the fit a run without the flag does, the set's summary adds columns to its tables
             fit_members, key = MEMBER_RUNS[mode]
             fit = lambda fit_of, **own: fit_of(model, guide, ndata, num_steps=args.n_iter, **own)  # noqa: E731
-            shown, saved, table_columns = fit_members(fit, ndata, args, list(guide_info_df.index))
+            shown, saved, table_columns = fit_members(fit, ndata, args, list(guide_info_df.index), len(target_info_df))
             param_history_dict, save_dict_model = deepcopy(shown)
             save_dict.update(save_dict_model)
             save_dict[key] = saved

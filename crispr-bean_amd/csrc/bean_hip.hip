@@ -35,6 +35,7 @@
 #include "bean_jacobi.hpp"  // ... with a Gauss-Jacobi rule for the pairs the predicate leaves out (bean_hip_marginal_grid_tail)
 #include "bean_importance_tail.hpp"  // that rule for the marginal importance weights (bean_hip_log_weights_marginal_tail)
 #include "bean_survival_predictive.hpp"  // replicate counts of a survival screen (bean_hip_simulate_survival)
+#include "bean_survival_members.hpp"     // K such screens in one launch (bean_hip_simulate_survival_members)
 
 using namespace bean;
 
@@ -3244,6 +3245,18 @@ extern "C" int bean_hip_survival_predictive_supported(const bean_hip_ctx* c) {
     return survival_predictive_shape_ok(c) ? 1 : 0;
 }
 
+// postfit_admit for the survival simulators: a null handle, a handle survival_predictive_shape_ok() does not take, an
+// unprepared one
+static int survival_postfit_admit(const bean_hip_ctx* c, const std::string& name) {
+    if (!c) return fail(name + ": null handle");
+    if (!survival_predictive_shape_ok(c))
+        return fail(name + ": the survival count simulator does not take this handle "
+                    "(bean_hip_survival_predictive_supported): survival variant Normal / MixtureNormal, unsharded, no "
+                    "sample covariates, one member, one particle");
+    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
+    return 0;
+}
+
 // One replicate screen of a survival fit (k_simulate_survival): the signature and buffer rules of bean_hip_simulate,
 // the launch sequence of simulate_run - the seed, draw `draw` as bean_hip_elbo_grad(seed, step = draw) prepares it (no
 // loss slot is cleared: n = 0), then one launch over the (tile, replicate) waves of k_guide_survival_wave's grid.
@@ -3251,12 +3264,7 @@ extern "C" int bean_hip_simulate_survival(bean_hip_ctx* c, uint64_t seed, uint64
                                           void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes,
                                           void* stream_) {
     const std::string name = "bean_hip_simulate_survival";
-    if (!c) return fail(name + ": null handle");
-    if (!survival_predictive_shape_ok(c))
-        return fail(name + ": the survival count simulator does not take this handle "
-                    "(bean_hip_survival_predictive_supported): survival variant Normal / MixtureNormal, unsharded, no "
-                    "sample covariates, one member, one particle");
-    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
+    if (survival_postfit_admit(c, name)) return -1;
     if (check_bound(c, false, false)) return -1;
     if (sim_buffers(c, name, "(R, B, G) float32", 1, x_out, x_bytes, xbc_out, xbc_bytes)) return -1;
     if (buf_optional(name, "alpha_out", "(2, R, B, G) float64", alpha_out, alpha_bytes,
@@ -3284,4 +3292,38 @@ extern "C" int bean_hip_simulate_survival(bean_hip_ctx* c, uint64_t seed, uint64
     });
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+// K replicate screens of a survival fit in one launch (k_simulate_survival_members: the screens of a survival screen's
+// parametric bootstrap, (K, R, B, G) member-major).  The buffer rules and error contract of bean_hip_simulate_members,
+// the admission of bean_hip_simulate_survival, the launch sequence of simulate_run: k_set_step(first_draw, slot 0, n =
+// 0), the one PREP k_param, then the K planes over the (tile, replicate) waves of k_simulate_survival's grid - which is
+// pair_grid's, a survival handle's tiles starting at guide 0.  mu_t, lpn and gam / gsum are those of draw first_draw (or
+// injected) for every member; member k's baseline u_g (unless eps_u is injected), pi, Dirichlet and categorical draws
+// are those of draw first_draw + k.  No graph; no parameter, moment, gradient, loss_hist entry or loss accumulator is
+// written, and the resume is cleared.
+extern "C" int bean_hip_simulate_survival_members(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                                  void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes,
+                                                  void* stream_) {
+    const std::string name = "bean_hip_simulate_survival_members";
+    if (survival_postfit_admit(c, name)) return -1;
+    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_MEMBERS)
+        return fail(name + ": n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) + "], got " +
+                    std::to_string(n_draws));
+    if (check_bound(c, false, false)) return -1;
+    if (sim_buffers(c, name, "(K, R, B, G) float32 with K = " + std::to_string(n_draws), (uint64_t)n_draws, x_out,
+                    x_bytes, xbc_out, xbc_bytes))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t lds = simulate_survival_lds(c->d.B);
+    if (lds > 65536) {  // beyond 35 timepoints, as bean_hip_simulate_survival
+        const void* fn = with_family_acc(c->d, [](auto fam, auto acc) { return (const void*)k_simulate_survival_members<fam(), acc()>; });
+        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    // (simulate_run hands the sorting simulators' LDS size to its launch: this kernel's own is taken instead)
+    return simulate_run(c, seed, first_draw, (unsigned)n_draws, x_out, xbc_out, nullptr, stream,
+                        [&](auto fam, auto acc, dim3 grid, size_t, const SimArgs& sa) {
+                            hipLaunchKernelGGL((k_simulate_survival_members<fam(), acc()>), grid, dim3(64), lds, stream,
+                                               c->d, sa);
+                        });
 }

@@ -895,6 +895,24 @@ class HipSVI:
             out["alpha"] = al
         return out
 
+    def simulate_survival_members(self, first_draw: int, n_draws: int, seed: int = 101) -> Dict[str, torch.Tensor]:
+        """``n_draws`` replicate screens of a survival fit in one launch (``bean_hip_simulate_survival_members``): ``X``
+        (K, R, B, G) float32 and, where the fit uses the barcode-matched counts, ``X_bcmatch`` - device tensors,
+        member-major.  The per-target and per-guide Normal sites and the Dirichlet-over-all-guides site are those of
+        draw ``first_draw`` (or the injected ones, ``set_noise``) for every member; member k's baseline ``u_g`` (unless
+        ``eps_u`` is injected: then that value for every member), pi, Dirichlet and categorical draws are those of draw
+        ``first_draw + k``: plane 0 is ``simulate_survival(first_draw)``, and with the shared sites injected plane k is
+        ``simulate_survival(first_draw + k)``, bit for bit.  Leaves the fit alone as ``simulate_survival`` does; the
+        next ``run(resume=True)`` is a plain run."""
+        if not self.survival_predictive_supported or not hasattr(self.lib, "bean_hip_simulate_survival_members"):
+            raise PredictiveUnsupported(f"the survival count simulator does not take this engine ({self.family}"
+                                        f"{', survival' if self.survival else ', sorting'}): survival variant Normal / "
+                                        "MixtureNormal, unsharded, no sample covariates, one member, one particle")
+        K = int(n_draws)
+        return self._simulated((max(K, 0),), lambda x, xbc: self._check(self.lib.bean_hip_simulate_survival_members(
+            self._h, int(seed), int(first_draw), K, _ptr(x), _nbytes(x), _ptr(xbc), _nbytes(xbc), self._sptr()),
+            "simulate_survival_members"))
+
     def simulate_members(self, first_draw: int, n_draws: int, seed: int = 101) -> Dict[str, torch.Tensor]:
         """``n_draws`` replicate screens in one launch (``bean_hip_simulate_members``): ``X`` (K, R, B, G) float32 and,
         where the fit uses the barcode-matched counts, ``X_bcmatch`` - device tensors, member-major, what

@@ -214,6 +214,8 @@ def _fit_members(model, guide, data, plan, run, common, report_every, verbose):
     n = len(run)
     seeds = [plan.seeds[k] for k in run]
     spec = _resolve(model)
+    if spec.family in ("MultiMixtureNormal", "ControlNormal") or spec.selection == "survival" or n > MAX_MEMBERS:
+        return None
     extra = {}
     if plan.differ_in:
         screens = [plan.screen(k) for k in run]
@@ -222,8 +224,6 @@ def _fit_members(model, guide, data, plan, run, common, report_every, verbose):
             x, x_bc = stack_counts(screens)
             # (the barcode-matched counts travel only where the fit uses them: build_engine's reading of the model)
             extra["member_counts"] = (x, x_bc if bool(spec.get("use_bcmatch", True)) else None)
-    if spec.family in ("MultiMixtureNormal", "ControlNormal") or spec.selection == "survival" or n > MAX_MEMBERS:
-        return None
     device = torch.device("cuda", torch.cuda.current_device())
     try:
         eng = build_engine(model, guide, data.to(device), device=device, n_guides_total=data.n_guides,
@@ -265,7 +265,7 @@ def _fit_members(model, guide, data, plan, run, common, report_every, verbose):
     return results
 
 
-def _fit_plan(model, guide, data, plan, common, report_every, verbose):
+def _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_first=False):
     """The K fits of a ``MemberPlan`` (``model/jackknife.py``): the list of what ``run_inference`` returns for
     ``plan.screen(k)`` with ``plan.seeds[k]`` - bit for bit.  This is the fit behind ``run_inference_ensemble`` and the
     three jackknives.
@@ -278,7 +278,13 @@ def _fit_plan(model, guide, data, plan, common, report_every, verbose):
     enough for the one-launch stepper) and more than ``MAX_MEMBERS`` members in one run are fitted one after the other
     through ``run_inference``.  A non-finite loss of ANY member halts the fit at the end of its report window with the
     ``ValueError`` of ``run_inference``: the message names ``plan.labels[k]`` and the seed, and the parameters as they
-    were at the start of the window go to ``tmp_result.<plan.tags[k]>.pkl`` together with ``plan.dump_extra[k]``."""
+    were at the start of the window go to ``tmp_result.<plan.tags[k]>.pkl`` together with ``plan.dump_extra[k]``.  (One
+    after the other a halt is ``run_inference``'s own: it dumps to ``tmp_result.pkl``, and with ``plan.label_halts`` the
+    label is appended to its message.)
+
+    ``skip_first``: the caller holds member 0's fit already and gets the fits of members 1 ... K - 1 alone.  An engine
+    run still steps member 0 next to the others - member 0 of every engine is the screen itself - and its result is
+    dropped; one after the other it is not fitted."""
     K = len(plan.seeds)
     results = {}
     for at in range(1, max(K, 2), plan.per_run or K):
@@ -289,9 +295,11 @@ def _fit_plan(model, guide, data, plan, common, report_every, verbose):
         for k, fit in zip(run, fitted):
             results.setdefault(k, fit)  # (member 0: the first run's)
     else:
-        return [results[k] for k in range(K)]
+        return [results[k] for k in range(1 if skip_first else 0, K)]
     results = []  # one after the other
     for k, seed in enumerate(plan.seeds):
+        if skip_first and k == 0:
+            continue
         try:
             results.append(run_inference(model, guide, plan.screen(k), seed=seed, report_every=report_every,
                                          verbose=verbose, **common))
@@ -673,6 +681,106 @@ def run_inference_bootstrap(model, guide, data, n_boot: int = 32, seed: int = SE
     plan = dataclasses.replace(plan, per_run=per_run)
     results = _fit_plan(model, guide, data, plan, common, report_every, verbose)
     return results[0], results[1:]
+
+
+def survival_bootstrap_engine(model, guide, data, param_store) -> HipSVI:
+    """The engine a survival screen's parametric bootstrap draws its screens from: built for ``data`` as
+    ``run_survival_predictive`` builds its own - the same model / guide partials, so the ``mu_negctrl`` location and scale
+    a control fit handed to the model are the fit's - the fitted parameters of ``param_store`` loaded, and the plug-in
+    injected: zero standard-normal draws into ``eps_mu`` and, with accessibility scaling, ``eps_noise`` - every Normal
+    site a survival family has (``sd`` is not a latent of the survival models: the library has no ``eps_sd`` slot for
+    them and refuses to bind one); for the NormalModel ``q_0`` at the mean of its Dirichlet,
+    ``initial_abundance / sum(initial_abundance)`` for every replicate.  ``eps_u`` is NOT injected: the baseline
+    ``u_g ~ Normal(m0, s0)`` of the MixtureNormal model has no variational factor - the model draws it afresh every
+    step - so every screen draws its own, as it draws its own ``pi``.  The caller closes the engine."""
+    device = torch.device("cuda", torch.cuda.current_device())
+    eng = build_engine(model, guide, data.to(device), num_steps=1, device=device, n_guides_total=data.n_guides)
+    try:
+        load_parameters(eng, param_store)
+        zeros = lambda n: torch.zeros(int(n), dtype=torch.float64, device=eng.device)  # noqa: E731
+        noise = {"eps_mu": zeros(eng.T)}
+        if eng.scale_by_accessibility:
+            noise["eps_noise"] = zeros(data.n_guides)
+        if eng.surv_normal:
+            ia = torch.as_tensor(param_store["initial_abundance"]).detach().to(eng.device, torch.float64).reshape(-1)
+            noise["q_0"] = (ia / ia.sum()).expand(data.n_reps, data.n_guides).contiguous()
+        eng.set_noise(noise)
+    except BaseException:
+        eng.close()
+        raise
+    return eng
+
+
+def survival_bootstrap_screens(eng: HipSVI, n_boot: int, boot_seed: int = SEED):
+    """``(X (n_boot, R, B, G), X_bcmatch or None)``, device tensors: screen j is draw j of
+    ``eng.simulate_survival_members(..., seed=boot_seed)`` whatever the batching - calls of at most ``MAX_MEMBERS``
+    screens, each starting at the number of screens already drawn (the batching of ``bootstrap_screens``)."""
+    from .._lib import MAX_MEMBERS
+
+    xs, xbcs = [], []
+    done = 0
+    while done < n_boot:
+        k = min(MAX_MEMBERS, n_boot - done)
+        sim = eng.simulate_survival_members(done, k, seed=boot_seed)
+        xs.append(sim["X"])
+        if "X_bcmatch" in sim:
+            xbcs.append(sim["X_bcmatch"])
+        done += k
+    return torch.cat(xs), (torch.cat(xbcs) if xbcs else None)
+
+
+def run_survival_bootstrap(model, guide, data, n_boot: int = 32, seed: int = SEED, boot_seed: int = SEED, initial_lr=0.01,
+                           gamma=0.1, num_steps=2000, report_every: int = 100, verbose: bool = True):
+    """Parametric bootstrap of a survival screen: fit the screen, draw ``n_boot`` screens from the fitted model on the
+    device in one launch per ``MAX_MEMBERS`` screens (``HipSVI.simulate_survival_members``), and refit every one of them
+    with the same ``seed`` (``model/jackknife.py::bootstrap_plan``) - how far would ``mu`` move if the experiment were
+    repeated under the model just fitted.
+
+    The screens come from the plug-in (``survival_bootstrap_engine``): ``mu`` and the guide noise at their fitted
+    locations, the NormalModel's ``q_0`` at the mean of its Dirichlet; per screen a fresh baseline
+    ``u_g ~ Normal(m0, s0)`` (MixtureNormal: the site has no variational factor), per (replicate, guide) a fresh
+    ``pi ~ q(pi)``, ``p ~ Dirichlet(alpha)`` over the timepoints and ``x ~ Multinomial(n_obs, p)`` with the streams of
+    ``boot_seed``, screen j being draw j.
+
+    Conditioned on - the observed screen's, shared by every refit: both masks; the size factors; ``a0`` /
+    ``a0_bcmatch``; ``pi_a0`` and the control allele counts; every (replicate, guide) total over the timepoints;
+    ``data.X``, which is left untouched - the observed initial abundance of the MixtureNormal engine reads it, and the
+    drawn ``q_0`` does not enter the count concentrations, so the screens carry no information to redraw it from; and the
+    ``mu_negctrl`` location and scale that a control fit handed to the model partial.
+
+    Returns ``(full, boots)``: ``full`` is the first fit, exactly what ``run_inference(..., seed=seed)`` returns,
+    ``boots[j]`` exactly what it returns for a ``copy.copy(data)`` with the counts of draw j - bit for bit.  Survival
+    fits go one after the other (``_fit_plan(skip_first=True)``), so the screen is not fitted a second time as member 0
+    of the plan.  Raises ``PredictiveUnsupported`` - the message names the family - for sorting screens, tiling,
+    ``ControlNormal``, sample covariates and several ranks; ``n_boot < 2`` is a ``ValueError``.  A non-finite loss of a
+    refit halts it as ``run_inference`` halts: the parameters go to ``tmp_result.pkl`` and the message ends with
+    ``(bootstrap screen j)``."""
+    import torch.distributed as dist
+
+    from ..engine import PredictiveUnsupported
+
+    spec = _resolve(model)
+    world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+    why = _survival_predictive_refusal(spec, data, world)
+    if why is not None:
+        raise PredictiveUnsupported(f"a survival bootstrap is not available for {why}: the survival count simulator "
+                                    "serves the survival variant Normal and MixtureNormal models on one GPU")
+    n_boot = int(n_boot)
+    if n_boot < 2:
+        raise ValueError(f"a survival bootstrap needs at least 2 screens, got {n_boot}")
+    common = dict(initial_lr=initial_lr, gamma=gamma, num_steps=num_steps)
+    full = run_inference(model, guide, data, seed=seed, report_every=report_every, verbose=verbose, **common)
+    eng = survival_bootstrap_engine(model, guide, data, full[0])
+    try:
+        x, x_bc = survival_bootstrap_screens(eng, n_boot, boot_seed)
+        torch.cuda.synchronize(eng.device)
+    finally:
+        eng.close()
+    home = lambda t, like: None if t is None else t.to(like.device, like.dtype)  # noqa: E731
+    plan = bootstrap_plan(data, seed, home(x, data.X_masked),
+                          home(x_bc, data.X_bcmatch_masked) if x_bc is not None else None)
+    # member 0 of the plan is the screen itself: `full` is that fit already
+    return full, _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_first=True)
 
 
 def design_depths(depths):

@@ -710,6 +710,41 @@ int bean_hip_survival_predictive_supported(const bean_hip_ctx* ctx);
 int bean_hip_simulate_survival(bean_hip_ctx* ctx, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
                                void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes, void* stream);
 
+/* K replicate screens of a SURVIVAL handle's current parameters in ONE launch: the screens of a survival screen's
+ * parametric bootstrap (k_simulate_survival_members).
+ *
+ *   bean_hip_simulate_survival_members
+ *                                 takes the handles bean_hip_survival_predictive_supported takes, any size, and 1 <=
+ *                                 n_draws <= BEAN_HIP_MAX_MEMBERS.  x_out: (K, R, B, G) float32, K = n_draws,
+ *                                 member-major; xbc_out: the same shape, required exactly when the handle has
+ *                                 BEAN_FLAG_USE_BCMATCH and null (0 bytes) otherwise.  No alpha_out.
+ *                                 Launches: one k_set_step(first_draw, slot 0, n = 0), the one PREP k_param of
+ *                                 bean_hip_simulate_survival, one k_simulate_survival_members with the member on
+ *                                 blockIdx.y.  No graph.
+ *                                 Which draw is whose: mu_t, lpn (the per-target and per-guide Normal sites) and gam /
+ *                                 gsum (the Dirichlet-over-all-guides site) are those of the one PREP launch - draw
+ *                                 first_draw, or the injected *_IN values - and are shared by all K members.  The
+ *                                 baseline u_g (MixtureNormal): with BEAN_BUF_EPS_U_IN that value for every member;
+ *                                 otherwise member k redraws it in the kernel for draw first_draw + k with PREP's own
+ *                                 expression (member 0: the value PREP left).  Member k's pi draw, p ~ Dirichlet(alpha)
+ *                                 and the categorical draws use draw index first_draw + k wherever
+ *                                 bean_hip_simulate_survival uses `draw`.  So plane 0 is bean_hip_simulate_survival(seed,
+ *                                 first_draw) bit for bit, and with the shared sites injected plane k is
+ *                                 bean_hip_simulate_survival(seed, first_draw + k).  BEAN_BUF_PI_IN and BEAN_BUF_X0_IN
+ *                                 are honoured identically for every member; member 0 alone writes PI_OUT (with
+ *                                 BEAN_FLAG_DUMP_PI) and X0_OUT; the kernel writes no u_g, eps_u or EPS_U_OUT (they hold
+ *                                 draw first_draw, from PREP).
+ *                                 State: as bean_hip_simulate_survival - no parameter, moment, gradient, loss_hist entry
+ *                                 or loss accumulator is written, and a following bean_hip_svi_resume does not continue
+ *                                 an earlier window.
+ *
+ * Errors (status < 0, message in bean_hip_last_error(), nothing launched, the handle stays usable): a null handle; a
+ * handle that is not supported (the message names bean_hip_survival_predictive_supported) or not prepared; n_draws
+ * outside [1, BEAN_HIP_MAX_MEMBERS] (the message states the range); byte counts other than 4 K R B G (the message
+ * states K); xbc_out on a handle without BEAN_FLAG_USE_BCMATCH or without it on a handle with the flag. */
+int bean_hip_simulate_survival_members(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                       void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes, void* stream);
+
 /* The same loop for a fit that is stepped in windows (run_inference reports every 100 steps,
  * bean/model/run.py:378): results are those of bean_hip_svi_run, bit for bit, but the call ends with the
  * draw and the tables of step first_step + n_steps already on the device, and a call that continues exactly
