@@ -34,8 +34,7 @@
 #include "bean_grid.hpp"  // the same log joint at given (mu, y) per target and node (bean_hip_marginal_grid)
 #include "bean_jacobi.hpp"  // ... with a Gauss-Jacobi rule for the pairs the predicate leaves out (bean_hip_marginal_grid_tail)
 #include "bean_importance_tail.hpp"  // that rule for the marginal importance weights (bean_hip_log_weights_marginal_tail)
-#include "bean_survival_predictive.hpp"  // replicate counts of a survival screen (bean_hip_simulate_survival)
-#include "bean_survival_members.hpp"     // K such screens in one launch (bean_hip_simulate_survival_members)
+#include "bean_survival_predictive.hpp"  // replicate counts of a survival screen (bean_hip_simulate_survival, _members)
 
 using namespace bean;
 
@@ -2670,7 +2669,7 @@ extern "C" int bean_hip_test_special(int32_t op, uint64_t n, const double* a, co
 }
 
 // ------------------------------------------------------------------ posterior predictive replicate counts
-// (bean_predictive.hpp; at the end of the file, so that every other kernel keeps its place in the code object)
+// (bean_predictive.hpp, bean_survival_predictive.hpp)
 static bool predictive_shape_ok(const bean_hip_ctx* c) {
     const bean_hip_shape& s = c->shape;
     return c->wave_guide && c->wave2 && c->fused_guide && !is_survival(s) && s.n_sample_covariates == 0 &&
@@ -2684,15 +2683,33 @@ extern "C" int bean_hip_predictive_supported(const bean_hip_ctx* c) {
     return predictive_shape_ok(c) ? 1 : 0;
 }
 
+// ... and of survival screens.  Such a handle has no k_guide_wave2 (wave2 is false), so bean_hip_create leaves it
+// g_sh == 0 and n_tiles == (G + 63) / 64: pair_grid() below is the grid of k_guide_survival_wave.
+static bool survival_predictive_shape_ok(const bean_hip_ctx* c) {
+    const bean_hip_shape& s = c->shape;
+    return is_survival(s) && !is_tiling(s) && s.n_sample_covariates == 0 &&
+           (s.family == BEAN_FAMILY_NORMAL || s.family == BEAN_FAMILY_MIXTURE_NORMAL) && s.guide_offset == 0 &&
+           s.target_offset == 0 && (s.n_guides_total == 0 || s.n_guides_total == s.n_guides) &&
+           !(s.flags & BEAN_FLAG_NOT_LOSS_OWNER) && c->n_members == 1 && c->n_particles == 1;
+}
+
+extern "C" int bean_hip_survival_predictive_supported(const bean_hip_ctx* c) {
+    if (!c) return fail("bean_hip_survival_predictive_supported: null handle");
+    return survival_predictive_shape_ok(c) ? 1 : 0;
+}
+
 // ---- what the post-fit entry points share.  Each composes these in its own order: a call that is wrong twice is
 // refused for the first reason the entry point tests.
-// A null handle, a handle predictive_shape_ok() does not take, an unprepared one; `stem` is the entry point's own
-// sentence ("the count simulator does not take this handle").
-static int postfit_admit(const bean_hip_ctx* c, const std::string& name, const char* stem) {
+// A null handle, a handle `ok` does not take, an unprepared one; `stem` is the entry point's own sentence ("the count
+// simulator does not take this handle") and `takes` names the probe of `ok` and the handles it admits.
+static const char* const kSortingHandles = " (bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, "
+                                           "unsharded, no sample covariates, one member, one particle";
+static const char* const kSurvivalHandles = " (bean_hip_survival_predictive_supported): survival variant Normal / "
+                                            "MixtureNormal, unsharded, no sample covariates, one member, one particle";
+static int postfit_admit(const bean_hip_ctx* c, const std::string& name, const char* stem,
+                         bool (*ok)(const bean_hip_ctx*) = predictive_shape_ok, const char* takes = kSortingHandles) {
     if (!c) return fail(name + ": null handle");
-    if (!predictive_shape_ok(c))
-        return fail(name + ": " + stem + " (bean_hip_predictive_supported): sorting variant Normal / MixtureNormal, "
-                    "unsharded, no sample covariates, one member, one particle");
+    if (!ok(c)) return fail(name + ": " + stem + takes);
     if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
     return 0;
 }
@@ -2750,13 +2767,18 @@ static dim3 pair_grid(const DevArgs& d, unsigned planes = 1) {
     return dim3((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, planes);
 }
 
+// A kernel launched with more than 64 KB of dynamic LDS has its limit raised first
+static int raise_lds_limit(const void* fn, size_t lds) {
+    if (lds > 65536) HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return 0;
+}
+
 // What every simulator does once its arguments are checked: the seed, draw `draw` as bean_hip_elbo_grad(seed, step =
-// draw) prepares it (no loss slot is cleared: n = 0), then one launch of `planes` member planes.  `launch(fam, acc,
-// grid, lds, sa)` names the kernel and its further argument struct.  (`auto`: instantiated where it is called, so the
-// kernels keep their place in the code object.)
+// draw) prepares it (no loss slot is cleared: n = 0), then one launch of `planes` member planes with `lds` bytes of
+// dynamic LDS per wave.  `launch(fam, acc, grid, lds, sa)` names the kernel and its further argument struct.
 template <typename Launch>
-static auto simulate_run(bean_hip_ctx* c, uint64_t seed, uint64_t draw, unsigned planes, void* x_out, void* xbc_out,
-                         void* alpha_out, hipStream_t stream, Launch&& launch) {
+static int simulate_run(bean_hip_ctx* c, uint64_t seed, uint64_t draw, unsigned planes, void* x_out, void* xbc_out,
+                        void* alpha_out, hipStream_t stream, size_t lds, Launch&& launch) {
     c->d.seed = seed;
     c->resume_ok = false;  // the workspace now holds this draw and its tables
     launch_set_step(c, stream, draw, 0, 0);
@@ -2767,7 +2789,6 @@ static auto simulate_run(bean_hip_ctx* c, uint64_t seed, uint64_t draw, unsigned
     sa.xbc_out = (float*)xbc_out;
     sa.alpha_out = (double*)alpha_out;
     const dim3 grid = pair_grid(d, planes);
-    const size_t lds = simulate_wave2_lds(d.B);
     with_family_acc(d, [&](auto fam, auto acc) { launch(fam, acc, grid, lds, sa); });
     HIP_OK(hipGetLastError());
     return 0;
@@ -2802,7 +2823,7 @@ extern "C" int bean_hip_simulate(bean_hip_ctx* c, uint64_t seed, uint64_t draw, 
                      16 * (uint64_t)c->d.R * c->d.B * c->d.G))
         return -1;
     hipStream_t stream = (hipStream_t)stream_;
-    return simulate_run(c, seed, draw, 1, x_out, xbc_out, alpha_out, stream,
+    return simulate_run(c, seed, draw, 1, x_out, xbc_out, alpha_out, stream, simulate_wave2_lds(c->d.B),
                         [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
                             hipLaunchKernelGGL((k_simulate_wave2<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa);
                         });
@@ -2824,7 +2845,7 @@ extern "C" int bean_hip_simulate_members(bean_hip_ctx* c, uint64_t seed, uint64_
                     x_bytes, xbc_out, xbc_bytes))
         return -1;
     hipStream_t stream = (hipStream_t)stream_;
-    return simulate_run(c, seed, first_draw, (unsigned)n_draws, x_out, xbc_out, nullptr, stream,
+    return simulate_run(c, seed, first_draw, (unsigned)n_draws, x_out, xbc_out, nullptr, stream, simulate_wave2_lds(c->d.B),
                         [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
                             hipLaunchKernelGGL((k_simulate_members<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa);
                         });
@@ -2850,7 +2871,7 @@ extern "C" int bean_hip_simulate_design(bean_hip_ctx* c, uint64_t seed, uint64_t
                     std::to_string(n_draws), planes, x_out, x_bytes, xbc_out, xbc_bytes))
         return -1;
     hipStream_t stream = (hipStream_t)stream_;
-    return simulate_run(c, seed, first_draw, (unsigned)planes, x_out, xbc_out, nullptr, stream,
+    return simulate_run(c, seed, first_draw, (unsigned)planes, x_out, xbc_out, nullptr, stream, simulate_wave2_lds(c->d.B),
                         [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
                             hipLaunchKernelGGL((k_simulate_design<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa,
                                                dz);
@@ -2879,15 +2900,70 @@ extern "C" int bean_hip_simulate_power(bean_hip_ctx* c, uint64_t seed, uint64_t 
                     std::to_string(n_draws), planes, x_out, x_bytes, xbc_out, xbc_bytes))
         return -1;
     hipStream_t stream = (hipStream_t)stream_;
-    return simulate_run(c, seed, first_draw, (unsigned)planes, x_out, xbc_out, nullptr, stream,
+    return simulate_run(c, seed, first_draw, (unsigned)planes, x_out, xbc_out, nullptr, stream, simulate_wave2_lds(c->d.B),
                         [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
                             hipLaunchKernelGGL((k_simulate_power<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa,
                                                pw);
                         });
 }
 
+static const char* const kSurvSimStem = "the survival count simulator does not take this handle";
+
+// One replicate screen of a survival fit (k_simulate_survival): the signature and buffer rules of bean_hip_simulate,
+// simulate_run's launches over the (tile, replicate) waves of k_guide_survival_wave's grid.
+extern "C" int bean_hip_simulate_survival(bean_hip_ctx* c, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
+                                          void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes,
+                                          void* stream_) {
+    const std::string name = "bean_hip_simulate_survival";
+    if (postfit_admit(c, name, kSurvSimStem, survival_predictive_shape_ok, kSurvivalHandles)) return -1;
+    if (check_bound(c, false, false)) return -1;
+    if (sim_buffers(c, name, "(R, B, G) float32", 1, x_out, x_bytes, xbc_out, xbc_bytes)) return -1;
+    if (buf_optional(name, "alpha_out", "(2, R, B, G) float64", alpha_out, alpha_bytes,
+                     16 * (uint64_t)c->d.R * c->d.B * c->d.G))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t lds = simulate_survival_lds(c->d.B);  // beyond 35 timepoints: more than 64 KB
+    if (raise_lds_limit(with_family_acc(c->d, [](auto fam, auto acc) { return (const void*)k_simulate_survival<fam(), acc()>; }),
+                        lds))
+        return -1;
+    return simulate_run(c, seed, draw, 1, x_out, xbc_out, alpha_out, stream, lds,
+                        [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
+                            hipLaunchKernelGGL((k_simulate_survival<fam(), acc()>), grid, dim3(64), lds, stream, c->d, sa);
+                        });
+}
+
+// K replicate screens of a survival fit in one launch (k_simulate_survival_members: the screens of a survival screen's
+// parametric bootstrap, (K, R, B, G) member-major).  The buffer rules and error contract of bean_hip_simulate_members,
+// the admission of bean_hip_simulate_survival.  mu_t, lpn and gam / gsum are those of draw first_draw (or injected) for
+// every member; member k's baseline u_g (unless eps_u is injected), pi, Dirichlet and categorical draws are those of
+// draw first_draw + k.  No graph; no parameter, moment, gradient, loss_hist entry or loss accumulator is written, and
+// the resume is cleared.
+extern "C" int bean_hip_simulate_survival_members(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
+                                                  void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes,
+                                                  void* stream_) {
+    const std::string name = "bean_hip_simulate_survival_members";
+    if (postfit_admit(c, name, kSurvSimStem, survival_predictive_shape_ok, kSurvivalHandles)) return -1;
+    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_MEMBERS)
+        return fail(name + ": n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) + "], got " +
+                    std::to_string(n_draws));
+    if (check_bound(c, false, false)) return -1;
+    if (sim_buffers(c, name, "(K, R, B, G) float32 with K = " + std::to_string(n_draws), (uint64_t)n_draws, x_out,
+                    x_bytes, xbc_out, xbc_bytes))
+        return -1;
+    hipStream_t stream = (hipStream_t)stream_;
+    const size_t lds = simulate_survival_lds(c->d.B);
+    if (raise_lds_limit(with_family_acc(c->d, [](auto fam, auto acc) { return (const void*)k_simulate_survival_members<fam(), acc()>; }),
+                        lds))
+        return -1;
+    return simulate_run(c, seed, first_draw, (unsigned)n_draws, x_out, xbc_out, nullptr, stream, lds,
+                        [&](auto fam, auto acc, dim3 grid, size_t lds, const SimArgs& sa) {
+                            hipLaunchKernelGGL((k_simulate_survival_members<fam(), acc()>), grid, dim3(64), lds, stream,
+                                               c->d, sa);
+                        });
+}
+
 // ------------------------------------------------------------------ per-target log importance weights
-// (bean_importance.hpp; at the end of the file, so that every other kernel keeps its place in the code object)
+// (bean_importance.hpp)
 // log p(x, z) - log q(z) of draws first_draw .. first_draw + n_draws - 1 of the fitted guide, per target: draw d is the
 // draw bean_hip_elbo_grad(seed, step = d) evaluates, formed by the lanes themselves - three launches per call whatever
 // n_draws (the pairs' data-only constants, the pairs, the targets), no k_set_step, no PREP launch, nothing of the
@@ -3228,102 +3304,4 @@ extern "C" int bean_hip_marginal_tail_nodes(bean_hip_ctx* c, int32_t capacity, v
     tail_nodes_launch(d, ta, stream);
     HIP_OK(hipGetLastError());
     return 0;
-}
-
-// ------------------------------------------------------------------ survival screens: posterior predictive replicate counts
-// (bean_survival_predictive.hpp; at the end of the file, so that every other kernel keeps its place in the code object)
-static bool survival_predictive_shape_ok(const bean_hip_ctx* c) {
-    const bean_hip_shape& s = c->shape;
-    return is_survival(s) && !is_tiling(s) && s.n_sample_covariates == 0 &&
-           (s.family == BEAN_FAMILY_NORMAL || s.family == BEAN_FAMILY_MIXTURE_NORMAL) && s.guide_offset == 0 &&
-           s.target_offset == 0 && (s.n_guides_total == 0 || s.n_guides_total == s.n_guides) &&
-           !(s.flags & BEAN_FLAG_NOT_LOSS_OWNER) && c->n_members == 1 && c->n_particles == 1;
-}
-
-extern "C" int bean_hip_survival_predictive_supported(const bean_hip_ctx* c) {
-    if (!c) return fail("bean_hip_survival_predictive_supported: null handle");
-    return survival_predictive_shape_ok(c) ? 1 : 0;
-}
-
-// postfit_admit for the survival simulators: a null handle, a handle survival_predictive_shape_ok() does not take, an
-// unprepared one
-static int survival_postfit_admit(const bean_hip_ctx* c, const std::string& name) {
-    if (!c) return fail(name + ": null handle");
-    if (!survival_predictive_shape_ok(c))
-        return fail(name + ": the survival count simulator does not take this handle "
-                    "(bean_hip_survival_predictive_supported): survival variant Normal / MixtureNormal, unsharded, no "
-                    "sample covariates, one member, one particle");
-    if (!c->prepared) return fail(name + ": call bean_hip_prepare first");
-    return 0;
-}
-
-// One replicate screen of a survival fit (k_simulate_survival): the signature and buffer rules of bean_hip_simulate,
-// the launch sequence of simulate_run - the seed, draw `draw` as bean_hip_elbo_grad(seed, step = draw) prepares it (no
-// loss slot is cleared: n = 0), then one launch over the (tile, replicate) waves of k_guide_survival_wave's grid.
-extern "C" int bean_hip_simulate_survival(bean_hip_ctx* c, uint64_t seed, uint64_t draw, void* x_out, uint64_t x_bytes,
-                                          void* xbc_out, uint64_t xbc_bytes, void* alpha_out, uint64_t alpha_bytes,
-                                          void* stream_) {
-    const std::string name = "bean_hip_simulate_survival";
-    if (survival_postfit_admit(c, name)) return -1;
-    if (check_bound(c, false, false)) return -1;
-    if (sim_buffers(c, name, "(R, B, G) float32", 1, x_out, x_bytes, xbc_out, xbc_bytes)) return -1;
-    if (buf_optional(name, "alpha_out", "(2, R, B, G) float64", alpha_out, alpha_bytes,
-                     16 * (uint64_t)c->d.R * c->d.B * c->d.G))
-        return -1;
-    hipStream_t stream = (hipStream_t)stream_;
-    const size_t lds = simulate_survival_lds(c->d.B);
-    if (lds > 65536) {  // beyond 35 timepoints: three columns of doubles and one of floats per lane
-        const void* fn = with_family_acc(c->d, [](auto fam, auto acc) { return (const void*)k_simulate_survival<fam(), acc()>; });
-        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    c->d.seed = seed;
-    c->resume_ok = false;  // the workspace now holds this draw and its tables
-    launch_set_step(c, stream, draw, 0, 0);
-    launch_param<false, false, true>(c, stream);
-    const DevArgs& d = c->d;
-    SimArgs sa;
-    sa.x_out = (float*)x_out;
-    sa.xbc_out = (float*)xbc_out;
-    sa.alpha_out = (double*)alpha_out;
-    const int tiles = (d.G + 63) / 64;
-    const dim3 grid((unsigned)((tiles + 7) / 8 * 8) * (unsigned)d.R);
-    with_family_acc(d, [&](auto fam, auto acc) {
-        hipLaunchKernelGGL((k_simulate_survival<fam(), acc()>), grid, dim3(64), lds, stream, d, sa);
-    });
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// K replicate screens of a survival fit in one launch (k_simulate_survival_members: the screens of a survival screen's
-// parametric bootstrap, (K, R, B, G) member-major).  The buffer rules and error contract of bean_hip_simulate_members,
-// the admission of bean_hip_simulate_survival, the launch sequence of simulate_run: k_set_step(first_draw, slot 0, n =
-// 0), the one PREP k_param, then the K planes over the (tile, replicate) waves of k_simulate_survival's grid - which is
-// pair_grid's, a survival handle's tiles starting at guide 0.  mu_t, lpn and gam / gsum are those of draw first_draw (or
-// injected) for every member; member k's baseline u_g (unless eps_u is injected), pi, Dirichlet and categorical draws
-// are those of draw first_draw + k.  No graph; no parameter, moment, gradient, loss_hist entry or loss accumulator is
-// written, and the resume is cleared.
-extern "C" int bean_hip_simulate_survival_members(bean_hip_ctx* c, uint64_t seed, uint64_t first_draw, int32_t n_draws,
-                                                  void* x_out, uint64_t x_bytes, void* xbc_out, uint64_t xbc_bytes,
-                                                  void* stream_) {
-    const std::string name = "bean_hip_simulate_survival_members";
-    if (survival_postfit_admit(c, name)) return -1;
-    if (n_draws < 1 || n_draws > BEAN_HIP_MAX_MEMBERS)
-        return fail(name + ": n_draws must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) + "], got " +
-                    std::to_string(n_draws));
-    if (check_bound(c, false, false)) return -1;
-    if (sim_buffers(c, name, "(K, R, B, G) float32 with K = " + std::to_string(n_draws), (uint64_t)n_draws, x_out,
-                    x_bytes, xbc_out, xbc_bytes))
-        return -1;
-    hipStream_t stream = (hipStream_t)stream_;
-    const size_t lds = simulate_survival_lds(c->d.B);
-    if (lds > 65536) {  // beyond 35 timepoints, as bean_hip_simulate_survival
-        const void* fn = with_family_acc(c->d, [](auto fam, auto acc) { return (const void*)k_simulate_survival_members<fam(), acc()>; });
-        HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    // (simulate_run hands the sorting simulators' LDS size to its launch: this kernel's own is taken instead)
-    return simulate_run(c, seed, first_draw, (unsigned)n_draws, x_out, xbc_out, nullptr, stream,
-                        [&](auto fam, auto acc, dim3 grid, size_t, const SimArgs& sa) {
-                            hipLaunchKernelGGL((k_simulate_survival_members<fam(), acc()>), grid, dim3(64), lds, stream,
-                                               c->d, sa);
-                        });
 }

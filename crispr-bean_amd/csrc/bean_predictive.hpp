@@ -32,6 +32,8 @@
 //     thread-private column: table value, then concentration, gamma, cumulative | [B][64] floats, the counts drawn.
 //     No scratch, no atomics; results leave through plain vector stores.
 // Counter layout: next to RngSite (bean_special.hpp).
+// The Dirichlet and Multinomial steps are dm_draw_tail and the accessibility transform is accessible_pi1: the survival
+// simulators (bean_survival_predictive.hpp) call the same two functions.
 #pragma once
 
 namespace bean {
@@ -49,6 +51,116 @@ constexpr unsigned long long kSimCatWords = 1ull << 24;  // words per (likelihoo
 // kDblMin / 1e-290 = 2e-18 whether floored or not: no read lands there either way, and the draw keeps its bits.
 constexpr double kSimLogBelow = 1e-290;
 static_assert(kBCap <= 2 * kSimPairSlots, "the gamma windows hold kBCap conditions");
+
+// scale_pi_by_accessibility + add_noise_to_pi, A = 2 (utils.py:106-178), as the guide kernels of both selections
+// form it: the edited share scaled by the guide's accessibility factor, the injected or drawn noise `lpn` added to its
+// logit, both clamps.
+__device__ __forceinline__ double accessible_pi1(const double pi1, const double kacc, const double lpn) {
+    const double s1 = pi1 * kacc;
+    const double p1c = fmin(fmax(s1, 1e-3), 1.0 - 1e-3);
+    const double l = flog(p1c * frcp(1.0 - p1c)) + lpn;
+    const double el = exp(l);
+    const double pn = el * frcp(1.0 + el);
+    return fmin(fmax(pn, 1e-3), 1.0 - 1e-3);
+}
+
+// The draw tail of every count simulator: p ~ Dirichlet(alpha), x ~ Multinomial(n_i, p) for one lane.
+//   seed, sub   the call's seed and the lane's subsequence r G_tot + g_off + g
+//   dl          2 draw + likelihood: which window of kSiteSimGamma / kSiteSimCat
+//   col         the lane's column col[b * 64] of B doubles, holding the floored concentrations; left as the cumulative
+//   xs          the lane's column xs[b * 64] of B floats: the counts drawn are left here, the caller stores them
+//   conc(b)     bin b's floored concentration formed again with the caller's operands, for the log branch
+// Reads nothing of DevArgs: the sorting and the survival bodies hand it what it needs.
+template <typename Conc>
+__device__ __forceinline__ void dm_draw_tail(const unsigned long long seed, const unsigned long long sub,
+                                             const unsigned long long dl, const int B, const long n_i, double* col,
+                                             float* xs, const Conc& conc) {
+    // ---- p ~ Dirichlet(alpha): gammas two bins at a time, then the cumulative
+    double gsum = 0.0;
+#pragma unroll 1
+    for (int b = 0; b < B; b += 2) {
+        const bool two = b + 1 < B;
+        const double al0 = col[b * 64], al1 = two ? col[(b + 1) * 64] : 1.0;
+        Rng rng(seed, kSiteSimGamma, sub, (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords);
+        const GammaPair gp = sample_gamma_pair_inl(al0, al1, rng);
+        const double gm0 = fmax(gp.g0, kDblMin);
+        col[b * 64] = gm0;
+        gsum += gm0;
+        if (two) {
+            const double gm1 = fmax(gp.g1, kDblMin);
+            col[(b + 1) * 64] = gm1;
+            gsum += gm1;
+        }
+    }
+    double rs = frcp(gsum);
+    if (gsum < kSimLogBelow) {
+        // every gamma of this pair is at or near the kDblMin floor (concentrations of ~1e-3 and below in every bin):
+        // floored, the bins would share the reads evenly, where the Dirichlet gives nearly all of them to the bin
+        // with the largest gamma.  The same draws again in logs: log gamma = log(Marsaglia-Tsang draw of alpha + 1)
+        // + log U / alpha, from the same counters (the boost's block first, then the rounds), less their maximum.
+        // The column holds the gammas by now, so the caller forms the concentrations again (`conc`).
+        double mx = -INFINITY;
+#pragma unroll 1
+        for (int b = 0; b < B; b += 2) {
+            const bool two = b + 1 < B;
+            const double al0 = conc(b), al1 = two ? conc(b + 1) : 1.0;
+            const bool lo0 = al0 < 1.0, lo1 = al1 < 1.0;
+            const unsigned long long off = (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords;
+            Rng rng(seed, kSiteSimGamma, sub, off + ((lo0 || lo1) ? 4ull : 0ull));
+            const uint4 ub = philox_block(seed, rng.sub, off);
+            const GammaPair gp = sample_gamma_pair_inl(lo0 ? al0 + 1.0 : al0, lo1 ? al1 + 1.0 : al1, rng);
+            const double lg0 = log(gp.g0) + (lo0 ? log(Rng::to_unit(ub.x, ub.y)) / al0 : 0.0);
+            col[b * 64] = lg0;
+            mx = fmax(mx, lg0);
+            if (two) {
+                const double lg1 = log(gp.g1) + (lo1 ? log(Rng::to_unit(ub.z, ub.w)) / al1 : 0.0);
+                col[(b + 1) * 64] = lg1;
+                mx = fmax(mx, lg1);
+            }
+        }
+        gsum = 0.0;
+#pragma unroll 1
+        for (int b = 0; b < B; ++b) {
+            const double w = exp(col[b * 64] - mx);
+            col[b * 64] = w;
+            gsum += w;
+        }
+        rs = 1.0 / gsum;
+    }
+    double cum = 0.0;
+#pragma unroll 1
+    for (int b = 0; b < B; ++b) {
+        cum += col[b * 64] * rs;
+        col[b * 64] = cum;
+        xs[b * 64] = 0.f;
+    }
+    // ---- x_rep ~ Multinomial(n, p): four categorical draws per Philox block
+    const long n_blk = (n_i + 3) >> 2;
+    const unsigned long long cat_sub = ((unsigned long long)kSiteSimCat << 48) + sub;
+    const unsigned long long cat_off = dl * kSimCatWords;
+#pragma unroll 1
+    for (long t = 0; t < n_blk; ++t) {
+        const uint4 w = philox_block(seed, cat_sub, cat_off + 4ull * (unsigned long long)t);
+        const double u0 = ((double)w.x + 0.5) * 2.3283064365386963e-10;
+        const double u1 = ((double)w.y + 0.5) * 2.3283064365386963e-10;
+        const double u2 = ((double)w.z + 0.5) * 2.3283064365386963e-10;
+        const double u3 = ((double)w.w + 0.5) * 2.3283064365386963e-10;
+        int k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+#pragma unroll 1
+        for (int b = 0; b < B - 1; ++b) {
+            const double cb = col[b * 64];
+            k0 += u0 >= cb ? 1 : 0;
+            k1 += u1 >= cb ? 1 : 0;
+            k2 += u2 >= cb ? 1 : 0;
+            k3 += u3 >= cb ? 1 : 0;
+        }
+        const long rem = n_i - 4 * t;
+        xs[k0 * 64] += 1.f;
+        if (rem > 1) xs[k1 * 64] += 1.f;
+        if (rem > 2) xs[k2 * 64] += 1.f;
+        if (rem > 3) xs[k3 * 64] += 1.f;
+    }
+}
 
 __host__ __device__ inline size_t simulate_wave2_lds(int B) {
     return ((size_t)4 * B + (size_t)B * 64) * sizeof(double) + (size_t)B * 64 * sizeof(float);
@@ -121,16 +233,7 @@ __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimAr
             c.pi_out[rgi * 2 + 1] = pi1;
         }
         pe1 = pi1;
-        if (ACC) {
-            // scale_pi_by_accessibility + add_noise_to_pi, A = 2 (utils.py:106-178)
-            const double kacc = c.kacc[g];
-            const double s1 = pi1 * kacc;
-            const double p1c = fmin(fmax(s1, 1e-3), 1.0 - 1e-3);
-            const double l = flog(p1c * frcp(1.0 - p1c)) + c.lpn[g];
-            const double el = exp(l);
-            const double pn = el * frcp(1.0 + el);
-            pe1 = fmin(fmax(pn, 1e-3), 1.0 - 1e-3);
-        }
+        if (ACC) pe1 = accessible_pi1(pi1, c.kacc[g], c.lpn[g]);
     }
     const double w0 = MIX ? (ACC ? 1.0 - pe1 : pi0) : 0.0;  // weight of the wild-type component
     const double w1 = MIX ? (ACC ? pe1 : pi1) : 1.0;        // weight of the edited component
@@ -170,97 +273,13 @@ __device__ __forceinline__ void simulate_pair_body(const DevArgs& c, const SimAr
             col[b * 64] = al;
             if (s.alpha_out) s.alpha_out[(((long)lik * R + r) * B + b) * G + g] = al;
         }
-        // ---- p ~ Dirichlet(alpha): gammas two bins at a time, then the cumulative
-        const unsigned long long dl = ctr.step * 2ull + (unsigned long long)lik;
-        double gsum = 0.0;
-#pragma unroll 1
-        for (int b = 0; b < B; b += 2) {
-            const bool two = b + 1 < B;
-            const double al0 = col[b * 64], al1 = two ? col[(b + 1) * 64] : 1.0;
-            Rng rng(c.seed, kSiteSimGamma, sub, (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords);
-            const GammaPair gp = sample_gamma_pair_inl(al0, al1, rng);
-            const double gm0 = fmax(gp.g0, kDblMin);
-            col[b * 64] = gm0;
-            gsum += gm0;
-            if (two) {
-                const double gm1 = fmax(gp.g1, kDblMin);
-                col[(b + 1) * 64] = gm1;
-                gsum += gm1;
-            }
-        }
-        double rs = frcp(gsum);
-        if (gsum < kSimLogBelow) {
-            // every gamma of this pair is at or near the kDblMin floor (concentrations of ~1e-3 and below in every bin):
-            // floored, the bins would share the reads evenly, where the Dirichlet gives nearly all of them to the bin
-            // with the largest gamma.  The same draws again in logs: log gamma = log(Marsaglia-Tsang draw of alpha + 1)
-            // + log U / alpha, from the same counters (the boost's block first, then the rounds), less their maximum.
-            // The column holds the gammas by now, so the concentrations are formed again: same operands, same bits.
-            const auto conc = [&](int b) {
-                const double ar = alpha_raw(w0, MIX ? c_p0[b] : 0.0, w1, tab(b), sf[b], epsB, ai * c_sm[b]);
-                return ar < kEps ? kEps : ar;
-            };
-            double mx = -INFINITY;
-#pragma unroll 1
-            for (int b = 0; b < B; b += 2) {
-                const bool two = b + 1 < B;
-                const double al0 = conc(b), al1 = two ? conc(b + 1) : 1.0;
-                const bool lo0 = al0 < 1.0, lo1 = al1 < 1.0;
-                const unsigned long long off = (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords;
-                Rng rng(c.seed, kSiteSimGamma, sub, off + ((lo0 || lo1) ? 4ull : 0ull));
-                const uint4 ub = philox_block(c.seed, rng.sub, off);
-                const GammaPair gp = sample_gamma_pair_inl(lo0 ? al0 + 1.0 : al0, lo1 ? al1 + 1.0 : al1, rng);
-                const double lg0 = log(gp.g0) + (lo0 ? log(Rng::to_unit(ub.x, ub.y)) / al0 : 0.0);
-                col[b * 64] = lg0;
-                mx = fmax(mx, lg0);
-                if (two) {
-                    const double lg1 = log(gp.g1) + (lo1 ? log(Rng::to_unit(ub.z, ub.w)) / al1 : 0.0);
-                    col[(b + 1) * 64] = lg1;
-                    mx = fmax(mx, lg1);
-                }
-            }
-            gsum = 0.0;
-#pragma unroll 1
-            for (int b = 0; b < B; ++b) {
-                const double w = exp(col[b * 64] - mx);
-                col[b * 64] = w;
-                gsum += w;
-            }
-            rs = 1.0 / gsum;
-        }
-        double cum = 0.0;
-#pragma unroll 1
-        for (int b = 0; b < B; ++b) {
-            cum += col[b * 64] * rs;
-            col[b * 64] = cum;
-            xs[b * 64] = 0.f;
-        }
-        // ---- x_rep ~ Multinomial(n, p): four categorical draws per Philox block
-        const long n_i = DEPTH ? design_total(n, depth) : (long)n;
-        const long n_blk = (n_i + 3) >> 2;
-        const unsigned long long cat_sub = ((unsigned long long)kSiteSimCat << 48) + sub;
-        const unsigned long long cat_off = dl * kSimCatWords;
-#pragma unroll 1
-        for (long t = 0; t < n_blk; ++t) {
-            const uint4 w = philox_block(c.seed, cat_sub, cat_off + 4ull * (unsigned long long)t);
-            const double u0 = ((double)w.x + 0.5) * 2.3283064365386963e-10;
-            const double u1 = ((double)w.y + 0.5) * 2.3283064365386963e-10;
-            const double u2 = ((double)w.z + 0.5) * 2.3283064365386963e-10;
-            const double u3 = ((double)w.w + 0.5) * 2.3283064365386963e-10;
-            int k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-#pragma unroll 1
-            for (int b = 0; b < B - 1; ++b) {
-                const double cb = col[b * 64];
-                k0 += u0 >= cb ? 1 : 0;
-                k1 += u1 >= cb ? 1 : 0;
-                k2 += u2 >= cb ? 1 : 0;
-                k3 += u3 >= cb ? 1 : 0;
-            }
-            const long rem = n_i - 4 * t;
-            xs[k0 * 64] += 1.f;
-            if (rem > 1) xs[k1 * 64] += 1.f;
-            if (rem > 2) xs[k2 * 64] += 1.f;
-            if (rem > 3) xs[k3 * 64] += 1.f;
-        }
+        // the concentrations again, for the log branch (the column holds the gammas by then): same operands, same bits
+        const auto conc = [&](int b) {
+            const double ar = alpha_raw(w0, MIX ? c_p0[b] : 0.0, w1, tab(b), sf[b], epsB, ai * c_sm[b]);
+            return ar < kEps ? kEps : ar;
+        };
+        dm_draw_tail(c.seed, sub, ctr.step * 2ull + (unsigned long long)lik, B, DEPTH ? design_total(n, depth) : (long)n, col,
+                     xs, conc);
 #pragma unroll 1
         for (int b = 0; b < B; ++b) out[((long)r * B + b) * G + g] = xs[b * 64];
     }

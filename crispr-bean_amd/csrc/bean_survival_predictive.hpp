@@ -6,14 +6,15 @@
 // guides site and their sums, lpn) - every (replicate, guide) forms the Dirichlet-Multinomial concentrations of its
 // likelihoods (X and, with the flag, X_bcmatch) over the TIMEPOINTS as k_guide_survival_wave does, then draws
 //     p ~ Dirichlet(alpha),    x_rep ~ Multinomial(n_obs, p),    n_obs = sum_b x_b of the observed counts
-// as simulate_pair_body (bean_predictive.hpp) draws them: the same sites, counter layout, floors, log branch and
-// inversion.  The draw tail is WRITTEN AGAIN here, not shared through a device function: every kernel that existed
-// before this header keeps its code object byte for byte.
+// through dm_draw_tail (bean_predictive.hpp), the draw tail simulate_pair_body ends in: the same sites, counter layout,
+// floors, log branch and inversion.  k_simulate_survival_members (at the end): K such screens in one launch, the member
+// on blockIdx.y - the screens of a survival screen's parametric bootstrap.  Both kernels are simulate_survival_body.
 //
 //   * grid and lanes as k_guide_survival_wave: a single-wave workgroup is 64 consecutive guides of one replicate,
 //     XCD-aware decode of blockIdx.x, a lane is one (replicate, guide); a lane beyond G writes nothing.
-//   * pi (MixtureNormal): site kSitePi, subsequence r G_tot + g_off + g, offset step * 256, the clamps of the guide
-//     kernel; DevArgs::pi_in is honoured, with BEAN_FLAG_DUMP_PI pi_out is written; accessibility transform with lpn.
+//   * pi (MixtureNormal): guide_pair_draw<FAM> - site kSitePi, subsequence r G_tot + g_off + g, offset step * 256, the
+//     clamps of the guide kernel; DevArgs::pi_in is honoured, with BEAN_FLAG_DUMP_PI pi_out is written; the
+//     accessibility transform with lpn is accessible_pi1, as in the sorting body.
 //   * q_0 (NormalModel, surv_q0lik): x0 = float32-clamped gam / gsum[r], or gam itself with x0_in - the weight of the
 //     one growth column.  x0_out is written where bound (MixtureNormal too, where the draw does not enter the
 //     concentrations: drawn_noise() after the call is then wholly the noise of draw d).
@@ -34,12 +35,13 @@ __host__ __device__ inline size_t simulate_survival_lds(int B) {
     return ((size_t)4 * B + (size_t)3 * B * 64) * sizeof(double) + (size_t)B * 64 * sizeof(float);
 }
 
-template <int FAM, bool ACC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
-void k_simulate_survival(DevArgs c, SimArgs s) {
+// One lane of one screen: (replicate, guide) of the workgroup blockIdx.x, drawn as draw `step` into the planes of `s`.
+// `first` gates the writes of pi_out (BEAN_FLAG_DUMP_PI) and x0_out: one handle has one of each.  MEMBERS: without an
+// injected eps_u the baseline u_g is drawn again for draw `step` (see k_simulate_survival_members); else it is c.u_g.
+template <int FAM, bool ACC, bool MEMBERS>
+__device__ __forceinline__ void simulate_survival_body(const DevArgs& c, const SimArgs& s, const unsigned long long step,
+                                                       const bool first, double* ssl) {
     constexpr bool MIX = FAM == kMixture;
-    extern __shared__ double ssl[];
-    const StepCtr ctr = *c.ctrB;
     const int lane = threadIdx.x;
     const int G = c.G, B = c.B, R = c.R;
     const int wg = blockIdx.x;
@@ -74,52 +76,49 @@ void k_simulate_survival(DevArgs c, SimArgs s) {
     // ---- the pi draw of this step and its transform: the head of k_guide_survival_wave
     double pi0 = 0.0, pi1 = 1.0, pe1 = 1.0;
     if (MIX) {
+        const float api0 = c.p[4][2 * g], api1 = c.p[4][2 * g + 1];
+        const double pa0 = c.pi_a0[g];
+        uint4 philox_first = make_uint4(0u, 0u, 0u, 0u);
+        if (!c.pi_in) philox_first = philox_block(c.seed, ((unsigned long long)kSitePi << 48) + sub, step * 256ull);
+        StepCtr ctr{};
+        ctr.step = step;  // all guide_pair_draw reads of it
+        double cp0, cp1;
+        guide_pair_draw<FAM>(c, ctr, r, g, api0, api1, pa0, &philox_first, &cp0, &cp1, pi0, pi1);
         if (c.pi_in) {
             pi0 = c.pi_in[rgi * 2];
             pi1 = c.pi_in[rgi * 2 + 1];
-        } else {
-            const float api0 = c.p[4][2 * g], api1 = c.p[4][2 * g + 1];
-            const double pa0 = c.pi_a0[g];
-            uint4 philox_first = philox_block(c.seed, ((unsigned long long)kSitePi << 48) + sub, ctr.step * 256ull);
-            const double al0 = (double)expf(api0), al1 = (double)expf(api1);
-            const double rs = frcp(al0 + al1) * pa0;
-            const double cp0 = al0 * rs, cp1 = al1 * rs;
-            const double cq0 = cp0 < 1e-5 ? 1e-5 : cp0, cq1 = cp1 < 1e-5 ? 1e-5 : cp1;
-            Rng rng(c.seed, kSitePi, sub, ctr.step * 256ull);
-            const GammaPair gp = sample_gamma_pair_inl(cq0, cq1, rng, &philox_first);
-            const double gm0 = fmax(gp.g0, kDblMin), gm1 = fmax(gp.g1, kDblMin);
-            const double rs2 = frcp(gm0 + gm1);
-            pi0 = fmin(fmax(gm0 * rs2, kDblMin), kOneMinus);
-            pi1 = fmin(fmax(gm1 * rs2, kDblMin), kOneMinus);
         }
-        if ((c.flags & kDumpPi) && c.pi_out) {
+        if (first && (c.flags & kDumpPi) && c.pi_out) {
             c.pi_out[rgi * 2] = pi0;
             c.pi_out[rgi * 2 + 1] = pi1;
         }
         pe1 = pi1;
-        if (ACC) {
-            const double kacc = c.kacc[g];
-            const double s1 = pi1 * kacc;
-            const double p1c = fmin(fmax(s1, 1e-3), 1.0 - 1e-3);
-            const double l = flog(p1c * frcp(1.0 - p1c)) + c.lpn[g];
-            const double el = exp(l);
-            const double pn = el * frcp(1.0 + el);
-            pe1 = fmin(fmax(pn, 1e-3), 1.0 - 1e-3);
-        }
+        if (ACC) pe1 = accessible_pi1(pi1, c.kacc[g], c.lpn[g]);
     }
     // ---- the draw of the Dirichlet-over-all-guides site: float32 semantics of torch's sampler
     double x0 = 1.0;
     if (MIX || q0lik) {
         const double gam = c.gam[rgi];
         x0 = c.x0_in ? gam : (double)fminf(fmaxf((float)(gam * frcp(c.gsum[r])), 1.17549435e-38f), 0.99999994f);
-        if (c.x0_out) c.x0_out[rgi] = x0;
+        if (first && c.x0_out) c.x0_out[rgi] = x0;
     }
     // ---- growth of the two components over the timepoints
     {
         double mu_t = c.mu_t[c.g2t[g]];
         // survival NormalModel: mu of negative-control guides is forced to 0
         if (q0lik && c.negctrl && c.negctrl[g] != 0) mu_t = 0.0;
-        const double u = MIX ? c.u_g[g] : 0.0;
+        // the baseline: PREP's (drawn or injected), or - a member without an injected one - the draw PREP would make at
+        // this member's step, with PREP's own expression (bean_param_body.hpp, the kSiteAux site)
+        double u = 0.0;
+        if (MIX) {
+            if (!MEMBERS || c.eps_u_in) {
+                u = c.u_g[g];
+            } else {
+                const double eps = (double)normal2_at(c.seed, ((unsigned long long)kSiteAux << 48) + (unsigned long long)(c.g_off + g),
+                                                      step * 4ull).x;
+                u = (double)(float)c.neg_loc + eps * (double)(float)c.neg_scale;
+            }
+        }
         const double mu1 = u + mu_t;
 #pragma unroll 1
         for (int b = 0; b < B; ++b) {
@@ -158,93 +157,49 @@ void k_simulate_survival(DevArgs c, SimArgs s) {
             col[b * 64] = al;
             if (s.alpha_out) s.alpha_out[(((long)lik * R + r) * B + b) * G + g] = al;
         }
-        // ---- p ~ Dirichlet(alpha): gammas two bins at a time, then the cumulative
-        const unsigned long long dl = ctr.step * 2ull + (unsigned long long)lik;
-        double gsum = 0.0;
-#pragma unroll 1
-        for (int b = 0; b < B; b += 2) {
-            const bool two = b + 1 < B;
-            const double al0 = col[b * 64], al1 = two ? col[(b + 1) * 64] : 1.0;
-            Rng rng(c.seed, kSiteSimGamma, sub, (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords);
-            const GammaPair gp = sample_gamma_pair_inl(al0, al1, rng);
-            const double gm0 = fmax(gp.g0, kDblMin);
-            col[b * 64] = gm0;
-            gsum += gm0;
-            if (two) {
-                const double gm1 = fmax(gp.g1, kDblMin);
-                col[(b + 1) * 64] = gm1;
-                gsum += gm1;
-            }
-        }
-        double rs = frcp(gsum);
-        if (gsum < kSimLogBelow) {
-            // every gamma at or near the kDblMin floor: the same draws again in logs, from the same counters (the
-            // boost's block first, then the rounds), less their maximum - see simulate_pair_body
-            double mx = -INFINITY;
-#pragma unroll 1
-            for (int b = 0; b < B; b += 2) {
-                const bool two = b + 1 < B;
-                const double al0 = conc(b), al1 = two ? conc(b + 1) : 1.0;
-                const bool lo0 = al0 < 1.0, lo1 = al1 < 1.0;
-                const unsigned long long off = (dl * kSimPairSlots + (unsigned long long)(b >> 1)) * kSimGammaWords;
-                Rng rng(c.seed, kSiteSimGamma, sub, off + ((lo0 || lo1) ? 4ull : 0ull));
-                const uint4 ub = philox_block(c.seed, rng.sub, off);
-                const GammaPair gp = sample_gamma_pair_inl(lo0 ? al0 + 1.0 : al0, lo1 ? al1 + 1.0 : al1, rng);
-                const double lg0 = log(gp.g0) + (lo0 ? log(Rng::to_unit(ub.x, ub.y)) / al0 : 0.0);
-                col[b * 64] = lg0;
-                mx = fmax(mx, lg0);
-                if (two) {
-                    const double lg1 = log(gp.g1) + (lo1 ? log(Rng::to_unit(ub.z, ub.w)) / al1 : 0.0);
-                    col[(b + 1) * 64] = lg1;
-                    mx = fmax(mx, lg1);
-                }
-            }
-            gsum = 0.0;
-#pragma unroll 1
-            for (int b = 0; b < B; ++b) {
-                const double w = exp(col[b * 64] - mx);
-                col[b * 64] = w;
-                gsum += w;
-            }
-            rs = 1.0 / gsum;
-        }
-        double cum = 0.0;
-#pragma unroll 1
-        for (int b = 0; b < B; ++b) {
-            cum += col[b * 64] * rs;
-            col[b * 64] = cum;
-            xs[b * 64] = 0.f;
-        }
-        // ---- x_rep ~ Multinomial(n, p): four categorical draws per Philox block
-        const long n_i = (long)n;
-        const long n_blk = (n_i + 3) >> 2;
-        const unsigned long long cat_sub = ((unsigned long long)kSiteSimCat << 48) + sub;
-        const unsigned long long cat_off = dl * kSimCatWords;
-#pragma unroll 1
-        for (long t = 0; t < n_blk; ++t) {
-            const uint4 w = philox_block(c.seed, cat_sub, cat_off + 4ull * (unsigned long long)t);
-            const double u0 = ((double)w.x + 0.5) * 2.3283064365386963e-10;
-            const double u1 = ((double)w.y + 0.5) * 2.3283064365386963e-10;
-            const double u2 = ((double)w.z + 0.5) * 2.3283064365386963e-10;
-            const double u3 = ((double)w.w + 0.5) * 2.3283064365386963e-10;
-            int k0 = 0, k1 = 0, k2 = 0, k3 = 0;
-#pragma unroll 1
-            for (int b = 0; b < B - 1; ++b) {
-                const double cb = col[b * 64];
-                k0 += u0 >= cb ? 1 : 0;
-                k1 += u1 >= cb ? 1 : 0;
-                k2 += u2 >= cb ? 1 : 0;
-                k3 += u3 >= cb ? 1 : 0;
-            }
-            const long rem = n_i - 4 * t;
-            xs[k0 * 64] += 1.f;
-            if (rem > 1) xs[k1 * 64] += 1.f;
-            if (rem > 2) xs[k2 * 64] += 1.f;
-            if (rem > 3) xs[k3 * 64] += 1.f;
-        }
+        dm_draw_tail(c.seed, sub, step * 2ull + (unsigned long long)lik, B, (long)n, col, xs, conc);
 #pragma unroll 1
         for (int b = 0; b < B; ++b) out[((long)r * B + b) * G + g] = xs[b * 64];
     }
+}
+
+template <int FAM, bool ACC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
+void k_simulate_survival(DevArgs c, SimArgs s) {
+    extern __shared__ double ssl[];
+    const StepCtr ctr = *c.ctrB;
+    simulate_survival_body<FAM, ACC, false>(c, s, ctr.step, true, ssl);
+}
+
+// k_simulate_survival_members: K replicate screens of one survival fit in one launch.  gridDim.x and lanes as
+// k_simulate_survival; gridDim.y = K and blockIdx.y is the member (the convention of bean_ensemble.hpp and
+// k_simulate_members), so a workgroup is 64 guides of one replicate of one member.  Member k writes plane k of x_out /
+// xbc_out, (K, R, B, G) float32 member-major; there is no alpha_out.
+//
+// WHICH DRAW IS WHOSE.  With ctrB->step = first_draw:
+//   * mu_t, lpn, gam / gsum: those of the ONE PREP k_param launch (draw first_draw, or the injected values), shared by
+//     the K members;
+//   * the baseline u_g (MixtureNormal): with eps_u_in, c.u_g - that value for every member.  Otherwise redrawn in the
+//     body for draw first_draw + k with PREP's own expression, so member 0 equals c.u_g; it is the one survival site
+//     without a variational factor, so a screen of the fitted model gets its own;
+//   * pi (kSitePi), the gammas (kSiteSimGamma) and the categorical draws (kSiteSimCat): draw first_draw + k wherever
+//     k_simulate_survival uses ctr.step;
+//   * pi_in and x0_in are every member's; member 0 alone writes pi_out (BEAN_FLAG_DUMP_PI) and x0_out.  The kernel
+//     writes no u_g, eps_u or eps_u_out.
+// Plane k is therefore bit for bit what k_simulate_survival leaves for draw first_draw + k when the shared sites are
+// injected (and plane 0 whatever is injected).  LDS, scratch, atomics and stores as k_simulate_survival.
+template <int FAM, bool ACC>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BEAN_WAVE_EU)))
+void k_simulate_survival_members(DevArgs c, SimArgs s) {
+    extern __shared__ double ssl[];
+    const StepCtr ctr = *c.ctrB;
+    const unsigned member = blockIdx.y;
+    const size_t plane = (size_t)member * (size_t)c.R * (size_t)c.B * (size_t)c.G;
+    SimArgs sm;
+    sm.x_out = s.x_out + plane;
+    sm.xbc_out = s.xbc_out ? s.xbc_out + plane : nullptr;
+    sm.alpha_out = nullptr;
+    simulate_survival_body<FAM, ACC, true>(c, sm, ctr.step + (unsigned long long)member, member == 0, ssl);
 }
 
 }  // namespace bean

@@ -1,5 +1,5 @@
 """The survival bootstrap on the GPU: K screens of a survival fit in one launch (bean_hip_simulate_survival_members,
-csrc/bean_survival_members.hpp) against the single draws of bean_hip_simulate_survival - which draw is whose - their
+csrc/bean_survival_predictive.hpp) against the single draws of bean_hip_simulate_survival - which draw is whose - their
 batching, totals, odd and large numbers of timepoints, the state the call must leave alone, its refusals, and
 run_survival_bootstrap and `bean run --survival-bootstrap` end to end.  The screens have depth_per_guide = 17: totals
 near 100.  -m gpu."""
