@@ -96,7 +96,7 @@ ENSEMBLE_SYMBOLS = ("bean_hip_ensemble_supported", "bean_hip_set_members", "bean
                     "bean_hip_marginal_grid_tail", "bean_hip_marginal_tail_nodes",
                     "bean_hip_log_weights_marginal_tail",
                     "bean_hip_survival_predictive_supported", "bean_hip_simulate_survival",
-                    "bean_hip_simulate_survival_members")
+                    "bean_hip_simulate_survival_members", "bean_hip_survival_members_supported")
 MAX_LOGW_DRAWS = 4096  # BEAN_HIP_MAX_LOGW_DRAWS
 MARGINAL_NODES = (16, 32, 64)  # n_nodes of bean_hip_log_weights_marginal
 TAIL_NODES = 64 + 48  # kTailNodes + kTailCheckNodes: the nodes bean_hip_marginal_tail_nodes returns per tail pair
@@ -115,6 +115,7 @@ SYMBOLS = [
     ("bean_hip_svi_run", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_int32, c_void_p]),
     ("bean_hip_svi_resume", c_int32, [c_void_p, c_uint64, c_uint64, c_uint64, c_int32, c_void_p]),
     ("bean_hip_ensemble_supported", c_int32, [c_void_p]),
+    ("bean_hip_survival_members_supported", c_int32, [c_void_p]),
     ("bean_hip_set_members", c_int32, [c_void_p, c_int32]),
     ("bean_hip_svi_run_ensemble", c_int32, [c_void_p, POINTER(c_uint64), c_int32, c_uint64, c_uint64, c_int32, c_void_p]),
     ("bean_hip_bind_member_masks", c_int32, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64]),

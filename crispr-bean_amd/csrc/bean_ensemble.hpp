@@ -28,7 +28,9 @@ __global__ __launch_bounds__(256) void k_set_step_ens(const DevArgs* members, un
 template <bool FINISH, bool ADAM, bool PREP, int KIND>
 __global__ __launch_bounds__(kParamBlock) __attribute__((amdgpu_waves_per_eu(1)))
 void k_param_ens(const DevArgs* members, int n_target_blocks) {
-    static_assert(KIND == 0 || KIND == 1, "the sorting variant families run the generic build or KIND 1");
+    static_assert(KIND == 0 || KIND == 1 || KIND == 2,
+                  "the sorting variant families run the generic build or KIND 1, the survival variant ones the generic "
+                  "build or KIND 2 (bean_survival_ensemble.hpp)");
     const DevArgs c = dev_args_in_sgprs(members + blockIdx.y);
 #define BEAN_PARAM_BODY_INCLUDED_BY_KERNEL
 #include "bean_param_body.hpp"

@@ -1025,9 +1025,13 @@ extern "C" int bean_hip_prepare(bean_hip_ctx* c, void* stream_) {
         for (int k = 1; k < n_copies(c); ++k)
             HIP_OK(hipMemcpyAsync(c->member_ws + (size_t)(k - 1) * c->member_ws_stride, c->workspace, c->workspace_bytes,
                                   hipMemcpyDeviceToDevice, stream));
-        const size_t lds = guide_wave2_lds(c->d.B, c->d.tile_targets);
-        const void* fn = with_family_acc(c->d, [](auto fam, auto ac) { return (const void*)k_guide_wave2_ens<fam(), ac()>; });
-        if (lds > 65536) HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        // (survival members: the single-fit launch raises no dynamic LDS limit, so k_guide_survival_wave_ens gets none
+        // either - bean_hip_survival_members_supported refuses the numbers of timepoints that would need one)
+        if (!c->d.survival) {
+            const size_t lds = guide_wave2_lds(c->d.B, c->d.tile_targets);
+            const void* fn = with_family_acc(c->d, [](auto fam, auto ac) { return (const void*)k_guide_wave2_ens<fam(), ac()>; });
+            if (lds > 65536) HIP_OK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
         HIP_OK(hipStreamSynchronize(stream));
         drop_graph(c);
     }
@@ -1865,11 +1869,32 @@ extern "C" int bean_hip_ensemble_supported(const bean_hip_ctx* c) {
     return ensemble_shape_ok(c) ? 1 : 0;
 }
 
+// ---- survival member fits (bean_survival_ensemble.hpp): the survival variant pair path with the same member axis.
+// The wave form only; and a number of timepoints whose dynamic LDS the single-fit launch is made with as it stands:
+// launch_guide_survival_wave raises no kernel's dynamic limit, so neither does the member launch, and more than 64 KB
+// (59 timepoints and up) is refused here.
+static bool survival_members_shape_ok(const bean_hip_ctx* c) {
+    const bean_hip_shape& s = c->shape;
+    return c->surv_wave && is_survival(s) && !is_tiling(s) &&
+           (s.family == BEAN_FAMILY_NORMAL || s.family == BEAN_FAMILY_MIXTURE_NORMAL) && s.n_sample_covariates == 0 &&
+           s.guide_offset == 0 && s.target_offset == 0 && (s.n_guides_total == 0 || s.n_guides_total == s.n_guides) &&
+           !(s.flags & (BEAN_FLAG_NOT_LOSS_OWNER | BEAN_FLAG_DUMP_PI)) && guide_survival_wave_lds(c->d.B) <= 65536;
+}
+
+extern "C" int bean_hip_survival_members_supported(const bean_hip_ctx* c) {
+    if (!c) return fail("bean_hip_survival_members_supported: null handle");
+    return survival_members_shape_ok(c) ? 1 : 0;
+}
+
+// what bean_hip_set_members, the two member binds and bean_hip_svi_run_ensemble admit: either member path.
+// (bean_hip_set_particles keeps asking ensemble_shape_ok alone: particles on survival stay on the caller's loop)
+static bool members_shape_ok(const bean_hip_ctx* c) { return ensemble_shape_ok(c) || survival_members_shape_ok(c); }
+
 extern "C" int bean_hip_set_members(bean_hip_ctx* c, int32_t n_members) {
     if (!c) return fail("bean_hip_set_members: null handle");
     if (n_members < 1 || n_members > BEAN_HIP_MAX_MEMBERS)
         return fail("bean_hip_set_members: n_members must be in [1, " + std::to_string(BEAN_HIP_MAX_MEMBERS) + "]");
-    if (!ensemble_shape_ok(c))
+    if (!members_shape_ok(c))
         return fail("bean_hip_set_members: the batched kernels do not take this shape (bean_hip_ensemble_supported): "
                     "fit its seeds one after the other");
     if (c->bound_any) return fail("bean_hip_set_members: call it after bean_hip_create and before any bean_hip_bind");
@@ -1948,7 +1973,7 @@ static DevArgs member_args(const bean_hip_ctx* c, int k, uint64_t seed) {
 extern "C" int bean_hip_bind_member_masks(bean_hip_ctx* c, const void* repguide, uint64_t repguide_bytes,
                                           const void* sample_mask, uint64_t sample_mask_bytes) {
     if (!c) return fail("bean_hip_bind_member_masks: null handle");
-    if (!ensemble_shape_ok(c))
+    if (!members_shape_ok(c))
         return fail("bean_hip_bind_member_masks: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
     if (!c->members_set) return fail("bean_hip_bind_member_masks: call bean_hip_set_members first");
     if ((repguide == nullptr) != (sample_mask == nullptr))
@@ -1974,7 +1999,7 @@ extern "C" int bean_hip_bind_member_masks(bean_hip_ctx* c, const void* repguide,
 extern "C" int bean_hip_bind_member_counts(bean_hip_ctx* c, const void* x, uint64_t x_bytes, const void* x_bcmatch,
                                            uint64_t x_bcmatch_bytes) {
     if (!c) return fail("bean_hip_bind_member_counts: null handle");
-    if (!ensemble_shape_ok(c))
+    if (!members_shape_ok(c))
         return fail("bean_hip_bind_member_counts: the batched kernels do not take this shape (bean_hip_ensemble_supported)");
     if (!c->members_set) return fail("bean_hip_bind_member_counts: call bean_hip_set_members first");
     if (!x && x_bcmatch) return fail("bean_hip_bind_member_counts: x_bcmatch without x (both null returns to shared counts)");
@@ -2006,7 +2031,11 @@ static int ens_kind(const bean_hip_ctx* c) {
     const DevArgs& d = c->d;
     const bool kind1 = !d.survival && d.family != kMultiMixture && !d.wide_targets && !d.n_cov && d.wrow && d.rows_v2 &&
                        !d.rrow && !d.surv_q0lik && !d.not_loss_owner && d.lpart && (d.dgq || d.family != kMixture) && d.tsum;
-    return (kind1 && !param_generic_only()) ? 1 : 0;
+    // (the survival MixtureNormal build, under launch_param's conditions; a member's tgrad is null: member_args)
+    const bool kind2 = d.survival && d.family == kMixture && !d.surv_q0lik && d.dgq && !d.tsum && !d.wide_targets &&
+                       !d.n_cov && d.wrow && d.rows_v2 && !d.rrow && d.lpart && d.lpt == kLanesPerTargetNarrow;
+    if (param_generic_only()) return 0;
+    return kind1 ? 1 : (kind2 ? 2 : 0);
 }
 
 // (mem, K: the members of an ensemble, or the particles of a fit)
@@ -2015,12 +2044,32 @@ static void launch_param_ens(bean_hip_ctx* c, hipStream_t stream, const DevArgs*
     int ntb, nb;
     grid_param(c, ntb, nb);
     const dim3 grid((unsigned)nb, (unsigned)K), block(kParamBlock);
-    if (ens_kind(c) == 1) hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 1>), grid, block, 0, stream, mem, ntb);
-    else hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 0>), grid, block, 0, stream, mem, ntb);
+    switch (ens_kind(c)) {
+        case 1: hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 1>), grid, block, 0, stream, mem, ntb); break;
+        case 2: hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 2>), grid, block, 0, stream, mem, ntb); break;
+        default: hipLaunchKernelGGL((k_param_ens<FINISH, ADAM, PREP, 0>), grid, block, 0, stream, mem, ntb); break;
+    }
+}
+
+// survival variant families: launch_guide_survival_wave's grid, times K on y (bean_survival_ensemble.hpp)
+static void launch_guide_survival_ens(bean_hip_ctx* c, hipStream_t stream, const DevArgs* mem, int K) {
+    const DevArgs& d = c->d;
+    const int tiles = (d.G + 63) / 64;
+    const dim3 grid((unsigned)((tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)K), block(64);
+    const size_t lds = guide_survival_wave_lds(d.B);
+    with_family_acc(d, [&](auto fam, auto acc) {
+        hipLaunchKernelGGL((k_guide_survival_wave_ens<fam(), acc()>), grid, block, lds, stream, mem);
+    });
+    if (d.surv_q0lik)  // projection term of the G-dimensional Dirichlet's pathwise gradient, per member
+        hipLaunchKernelGGL(k_sum_q_ens, dim3((unsigned)d.R, (unsigned)K), dim3(1024), 0, stream, mem);
 }
 
 static void launch_guide_ens(bean_hip_ctx* c, hipStream_t stream, const DevArgs* mem, int K) {
     const DevArgs& d = c->d;
+    if (d.survival) {
+        launch_guide_survival_ens(c, stream, mem, K);
+        return;
+    }
     const dim3 grid((unsigned)((d.n_tiles + 7) / 8 * 8) * (unsigned)d.R, (unsigned)K), block(64);
     const size_t lds = guide_wave2_lds(d.B, d.tile_targets);
     with_family_acc(d, [&](auto fam, auto acc) {
@@ -2061,9 +2110,12 @@ static int begin_copies(bean_hip_ctx* c, const char* who_, bool particles, const
     if (n_seeds != n)
         return fail(who + ": " + std::to_string(n_seeds) + " seeds for " + std::to_string(n) +
                     (particles ? " particle(s) (bean_hip_set_particles)" : " member(s) (bean_hip_set_members)"));
-    if (!ensemble_shape_ok(c)) return fail(who + ": the batched kernels do not take this shape (bean_hip_ensemble_supported)");
+    if (!(particles ? ensemble_shape_ok(c) : members_shape_ok(c)))
+        return fail(who + ": the batched kernels do not take this shape (bean_hip_ensemble_supported)");
     // (pi_out without kDumpPi refuses here and nowhere else: inherited, not reviewed here)
-    if (per_step_noise(c->d) || c->d.pi_out)
+    // (survival members: the draws and dumps of the survival sites are one buffer for all members, like the others)
+    if (per_step_noise(c->d) || c->d.pi_out ||
+        (c->d.survival && (c->d.x0_in || c->d.x0_out || c->d.eps_u_in || c->d.eps_u_out)))
         return fail(who + ": injected or dumped noise belongs to single " + (particles ? "evaluations" : "fits"));
     if (particles && check_bound(c, true, true)) return -1;  // (the mean gradient goes to the bound gradient buffers)
     return begin_steps(c, who_, first_step, n_steps);
@@ -2076,6 +2128,15 @@ extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds,
     hipStream_t stream = (hipStream_t)stream_;
     c->resume_ok = false;
     const int K = c->n_members;
+    if (c->d.survival && K > 1) {
+        // relocate_private leaves a pointer outside the workspace alone: bound, the members would share these sums
+        for (int slot : {BEAN_BUF_XCHG_GSUM, BEAN_BUF_XCHG_SQ})
+            if (c->slot_ptr[slot])
+                return fail(std::string("bean_hip_svi_run_ensemble: ") +
+                            (slot == BEAN_BUF_XCHG_GSUM ? "BEAN_BUF_XCHG_GSUM" : "BEAN_BUF_XCHG_SQ") + " is bound: " +
+                            std::to_string(K) + " survival members would share the exchange buffer (unbind it, or fit "
+                            "one after the other)");
+    }
     ArgSet& a = c->members;
     if (!a.dev && alloc_args(a, K)) return -1;  // (a handle that never heard of members is an ensemble of one)
     if (refresh_args(a, K, seeds, stream, [&](int k, uint64_t seed) { return member_args(c, k, seed); })) return -1;
@@ -2084,7 +2145,8 @@ extern "C" int bean_hip_svi_run_ensemble(bean_hip_ctx* c, const uint64_t* seeds,
         enqueue_pairs_ens(c, stream, n);
         return 0;
     };
-    // the ladder of bean_hip_svi_run's pair path, of {k_param_ens, k_guide_wave2_ens} pairs
+    // the ladder of bean_hip_svi_run's pair path, of {k_param_ens, k_guide_wave2_ens} pairs (survival members:
+    // {k_param_ens, k_guide_survival_wave_ens[, k_sum_q_ens]})
     if (use_graph && ensure_ladder(c, a, stream, graph_chunk, pairs_n)) return -1;
     launch_set_step_ens(stream, a.dev, K, first_step, n_steps);
     launch_param_ens<false, false, true>(c, stream, a.dev, K);

@@ -2220,18 +2220,11 @@ void k_pi_terms(DevArgs c) {
 #endif  // BEAN_AB_KERNELS
 // ------------------------------------------------------------ survival kernels
 // survival NormalModel: sq[r] = sum_g q_0[r, g] * gq[r, g] (fixed order: strided partials, block tree)
+// (the body is text of its own, bean_sum_q_body.hpp, shared with k_sum_q_ens of bean_survival_ensemble.hpp)
 __global__ __launch_bounds__(1024) void k_sum_q(DevArgs c) {
-    __shared__ double scratch[16];
-    const int r = blockIdx.x;
-    double v = 0.0;
-    for (int g = threadIdx.x; g < c.G; g += blockDim.x) {
-        const double gm = c.gam[(long)r * c.G + g];
-        const double x = c.x0_in ? gm
-                                 : (double)fminf(fmaxf((float)(gm * frcp(c.gsum[r])), 1.17549435e-38f), 0.99999994f);
-        v += x * c.gq[(long)r * c.G + g];
-    }
-    const double tot = block_sum(v, scratch);
-    if (threadIdx.x == 0) c.sq[r] = tot;
+#define BEAN_SUM_Q_BODY_INCLUDED_BY_KERNEL
+#include "bean_sum_q_body.hpp"
+#undef BEAN_SUM_Q_BODY_INCLUDED_BY_KERNEL
 }
 
 #ifdef BEAN_AB_KERNELS
@@ -3473,6 +3466,7 @@ __global__ __launch_bounds__(256) void k_test_special(int op, long n, const doub
 #include "bean_step_v2.hpp"
 #endif
 #include "bean_survival_v2.hpp"
+#include "bean_survival_ensemble.hpp"  // the member axis on the survival variant pair path
 #include "bean_tiling_v2.hpp"
 #ifdef BEAN_AB_KERNELS
 #include "bean_tile_svi.hpp"

@@ -37,7 +37,8 @@ def _quantile_edges(upper: torch.Tensor, lower: torch.Tensor):
 
 
 class EnsembleUnsupported(ValueError):
-    """``HipSVI(..., n_members=K)`` on a shape the batched kernels do not take (``bean_hip_ensemble_supported``)."""
+    """``HipSVI(..., n_members=K)`` on a shape the batched kernels do not take (neither ``bean_hip_ensemble_supported``
+    nor ``bean_hip_survival_members_supported``)."""
 
 
 class PredictiveUnsupported(ValueError):
@@ -281,7 +282,7 @@ class HipSVI:
                 self.lib.bean_hip_destroy(self._h)
                 self._h = None
                 raise ValueError(f"n_members must be in [1, {_lib.MAX_MEMBERS}]")
-            if not self.ensemble_supported:
+            if not (self.ensemble_supported or self.survival_members_supported):
                 self.lib.bean_hip_destroy(self._h)
                 self._h = None
                 raise EnsembleUnsupported(f"the batched kernels do not take this shape ({family}): fit its seeds one "
@@ -816,6 +817,15 @@ class HipSVI:
     def ensemble_supported(self) -> bool:
         """Whether the batched kernels take this engine's shape (``bean_hip_ensemble_supported``)."""
         return self.lib.bean_hip_ensemble_supported(self._h) == 1
+
+    @property
+    def survival_members_supported(self) -> bool:
+        """Whether the survival member kernels take this engine's shape (``bean_hip_survival_members_supported``): the
+        survival variant Normal / MixtureNormal families on the wave-form path, unsharded, no sample covariates.  Such an
+        engine takes ``n_members``, ``member_masks`` and ``member_counts`` as a sorting one does; ``ensemble_supported``
+        stays false for it, and with it the particles stay on the Python loop."""
+        fn = getattr(self.lib, "bean_hip_survival_members_supported", None)
+        return fn is not None and fn(self._h) == 1
 
     @property
     def predictive_supported(self) -> bool:

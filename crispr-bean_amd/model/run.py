@@ -203,10 +203,10 @@ def run_inference(model, guide, data, initial_lr=0.01, gamma=0.1, num_steps=2000
     return store, out
 
 
-def _fit_members(model, guide, data, plan, run, common, report_every, verbose):
+def _fit_members(model, guide, data, plan, run, common, report_every, verbose, batch_survival=False):
     """One engine run of ``_fit_plan``: the members ``run`` of ``plan`` (member i of the engine is member ``run[i]`` of
     the plan).  Returns their ``(param_store, {"loss", "params"})`` pairs, or ``None`` where the batched kernels do not
-    take the shape; halts as ``_fit_plan`` says."""
+    take the shape - a survival screen without ``batch_survival`` among them; halts as ``_fit_plan`` says."""
     from .. import parallel
     from .._lib import MAX_MEMBERS
     from ..engine import EnsembleUnsupported
@@ -214,7 +214,9 @@ def _fit_members(model, guide, data, plan, run, common, report_every, verbose):
     n = len(run)
     seeds = [plan.seeds[k] for k in run]
     spec = _resolve(model)
-    if spec.family in ("MultiMixtureNormal", "ControlNormal") or spec.selection == "survival" or n > MAX_MEMBERS:
+    if spec.family in ("MultiMixtureNormal", "ControlNormal") or n > MAX_MEMBERS:
+        return None
+    if spec.selection == "survival" and not batch_survival:
         return None
     extra = {}
     if plan.differ_in:
@@ -265,7 +267,7 @@ def _fit_members(model, guide, data, plan, run, common, report_every, verbose):
     return results
 
 
-def _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_first=False):
+def _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_first=False, batch_survival=False):
     """The K fits of a ``MemberPlan`` (``model/jackknife.py``): the list of what ``run_inference`` returns for
     ``plan.screen(k)`` with ``plan.seeds[k]`` - bit for bit.  This is the fit behind ``run_inference_ensemble`` and the
     three jackknives.
@@ -274,9 +276,12 @@ def _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_firs
     are members of one engine - with their own masks and counts where the plan's screens differ in them
     (``HipSVI(member_masks=..., member_counts=...)``, member 0 = the screen itself) - stepped by the same launches, in
     report windows.  With ``plan.per_run`` an engine run holds member 0 and at most that many further members; member
-    0's result is the first run's.  Every other family (tiling, survival, ControlNormal, sample covariates, screens large
-    enough for the one-launch stepper) and more than ``MAX_MEMBERS`` members in one run are fitted one after the other
-    through ``run_inference``.  A non-finite loss of ANY member halts the fit at the end of its report window with the
+    0's result is the first run's.  The survival variant Normal / MixtureNormal families have member kernels of their
+    own (``bean_hip_survival_members_supported``) and go the same way where the caller opts in with
+    ``batch_survival=True`` (``run_survival_bootstrap`` does; ``run_inference_ensemble`` and the three jackknives do
+    not yet, and fit a survival screen's members one after the other).  Every other family (tiling, ControlNormal, sample
+    covariates, screens large enough for the one-launch stepper) and more than ``MAX_MEMBERS`` members in one run are
+    fitted one after the other through ``run_inference``.  A non-finite loss of ANY member halts the fit at the end of its report window with the
     ``ValueError`` of ``run_inference``: the message names ``plan.labels[k]`` and the seed, and the parameters as they
     were at the start of the window go to ``tmp_result.<plan.tags[k]>.pkl`` together with ``plan.dump_extra[k]``.  (One
     after the other a halt is ``run_inference``'s own: it dumps to ``tmp_result.pkl``, and with ``plan.label_halts`` the
@@ -289,7 +294,9 @@ def _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_firs
     results = {}
     for at in range(1, max(K, 2), plan.per_run or K):
         run = [0] + list(range(at, min(at + (plan.per_run or K), K)))
-        fitted = _fit_members(model, guide, data, plan, run, common, report_every, verbose)
+        # (the opt-in travels by name, and only where it is given: the call is otherwise the one it has always been)
+        opt_in = {"batch_survival": True} if batch_survival else {}
+        fitted = _fit_members(model, guide, data, plan, run, common, report_every, verbose, **opt_in)
         if fitted is None:
             break
         for k, fit in zip(run, fitted):
@@ -730,7 +737,7 @@ def survival_bootstrap_screens(eng: HipSVI, n_boot: int, boot_seed: int = SEED):
 
 
 def run_survival_bootstrap(model, guide, data, n_boot: int = 32, seed: int = SEED, boot_seed: int = SEED, initial_lr=0.01,
-                           gamma=0.1, num_steps=2000, report_every: int = 100, verbose: bool = True):
+                           gamma=0.1, num_steps=2000, report_every: int = 100, verbose: bool = True, batch_refits: bool = True):
     """Parametric bootstrap of a survival screen: fit the screen, draw ``n_boot`` screens from the fitted model on the
     device in one launch per ``MAX_MEMBERS`` screens (``HipSVI.simulate_survival_members``), and refit every one of them
     with the same ``seed`` (``model/jackknife.py::bootstrap_plan``) - how far would ``mu`` move if the experiment were
@@ -749,12 +756,19 @@ def run_survival_bootstrap(model, guide, data, n_boot: int = 32, seed: int = SEE
     ``mu_negctrl`` location and scale that a control fit handed to the model partial.
 
     Returns ``(full, boots)``: ``full`` is the first fit, exactly what ``run_inference(..., seed=seed)`` returns,
-    ``boots[j]`` exactly what it returns for a ``copy.copy(data)`` with the counts of draw j - bit for bit.  Survival
-    fits go one after the other (``_fit_plan(skip_first=True)``), so the screen is not fitted a second time as member 0
-    of the plan.  Raises ``PredictiveUnsupported`` - the message names the family - for sorting screens, tiling,
+    ``boots[j]`` exactly what it returns for a ``copy.copy(data)`` with the counts of draw j - bit for bit.  The refits
+    are members 1 ... of engines whose member 0 is the screen (``_fit_plan(skip_first=True, batch_survival=True)``, at
+    most 63 screens per engine run): the survival member kernels step them in the same launches
+    (``HipSVI.survival_members_supported``); member 0 is stepped next to them and dropped - ``full`` stays the
+    ``run_inference`` fit.  Where the engine cannot be built (``EnsembleUnsupported``: ``BEAN_HIP_SURVIVAL=block``, more
+    timepoints than the member launch takes) the refits go one after the other through ``run_inference``, the screen
+    not among them; ``batch_refits=False`` asks for that path (same results; the members measured faster at every shape
+    tried, up to 4.6 waves per SIMD in a single fit's guide launch: DESIGN.md section 29).  Raises ``PredictiveUnsupported`` - the message names the family - for sorting screens, tiling,
     ``ControlNormal``, sample covariates and several ranks; ``n_boot < 2`` is a ``ValueError``.  A non-finite loss of a
-    refit halts it as ``run_inference`` halts: the parameters go to ``tmp_result.pkl`` and the message ends with
-    ``(bootstrap screen j)``."""
+    batched refit halts as the sorting bootstrap's do: at the end of its report window, the parameters as they were at
+    its start go to ``tmp_result.bootstrap<j>.pkl`` and the message names ``bootstrap screen j`` and the seed; one after
+    the other it halts as ``run_inference`` halts (``tmp_result.pkl``, the message ends with ``(bootstrap screen
+    j)``)."""
     import torch.distributed as dist
 
     from ..engine import PredictiveUnsupported
@@ -780,7 +794,8 @@ def run_survival_bootstrap(model, guide, data, n_boot: int = 32, seed: int = SEE
     plan = bootstrap_plan(data, seed, home(x, data.X_masked),
                           home(x_bc, data.X_bcmatch_masked) if x_bc is not None else None)
     # member 0 of the plan is the screen itself: `full` is that fit already
-    return full, _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_first=True)
+    return full, _fit_plan(model, guide, data, plan, common, report_every, verbose, skip_first=True,
+                           batch_survival=bool(batch_refits))
 
 
 def design_depths(depths):

@@ -260,7 +260,24 @@ int bean_hip_svi_run(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_step,
  *                                 MixtureNormal with or without accessibility scaling / fit_noise / X_bcmatch /
  *                                 --prior-params), unsharded.  Not: tiling, survival, ControlNormal, sample
  *                                 covariates, screens large enough for the one-launch stepper, BEAN_FLAG_DUMP_PI.
- *                                 Callers fit the seeds of such a shape one after the other.
+ *                                 Callers fit the seeds of such a shape one after the other.  (It also governs
+ *                                 bean_hip_set_particles, and stays 0 for every survival handle.)
+ *   bean_hip_survival_members_supported
+ *                                 1 if the survival member kernels take this handle's shape, 0
+ *                                 if not: survival selection on the wave-form variant path (not
+ *                                 BEAN_HIP_SURVIVAL=block), family Normal or MixtureNormal (with or without
+ *                                 accessibility scaling / X_bcmatch), no sample covariates, unsharded (no guide or
+ *                                 target offset, n_guides_total 0 or n_guides), neither BEAN_FLAG_NOT_LOSS_OWNER nor
+ *                                 BEAN_FLAG_DUMP_PI, and at most 58 timepoints (the dynamic LDS of the single-fit launch
+ *                                 as it is made: 64 KB).  bean_hip_set_members, the two member binds and
+ *                                 bean_hip_svi_run_ensemble admit a handle where EITHER predicate is 1, and everything
+ *                                 said below holds for such a survival handle: member k is, bit for bit,
+ *                                 bean_hip_svi_run(seed = seeds[k]) on a handle of its own with member k's counts and
+ *                                 masks.  bean_hip_svi_run_ensemble on a survival handle with more than one member
+ *                                 refuses while BEAN_BUF_XCHG_GSUM or BEAN_BUF_XCHG_SQ is bound (the members would share
+ *                                 the buffer; the message names it), and the survival draws and dumps (BEAN_BUF_X0_IN /
+ *                                 _OUT, EPS_U_IN / _OUT) count as injected / dumped noise.  bean_hip_set_particles and
+ *                                 bean_hip_simulate_survival* stay refused there (the latter with n_members > 1).
  *   bean_hip_set_members          after bean_hip_create, before ANY bean_hip_bind; 1 <= n_members <=
  *                                 BEAN_HIP_MAX_MEMBERS.  From then on the slots BEAN_BUF_P_*, G_*, M_*, V_* expect
  *                                 n_members times their single-fit size, member-major ((K, T), (K, G, A), ...), and
@@ -325,6 +342,7 @@ int bean_hip_svi_run(bean_hip_ctx* ctx, uint64_t seed, uint64_t first_step,
  * x_bcmatch not.  The handle stays usable after every one of them. */
 #define BEAN_HIP_MAX_MEMBERS 64
 int bean_hip_ensemble_supported(const bean_hip_ctx* ctx);
+int bean_hip_survival_members_supported(const bean_hip_ctx* ctx);
 int bean_hip_set_members(bean_hip_ctx* ctx, int32_t n_members);
 int bean_hip_bind_member_masks(bean_hip_ctx* ctx, const void* repguide, uint64_t repguide_bytes,
                                const void* sample_mask, uint64_t sample_mask_bytes);
